@@ -2,18 +2,24 @@
 """Benchmark of the hot path: one VanillaVAE training step (forward + loss + backward + gradient
 all-reduce (N>1) + Adam) on synthetic 64x64x3 batches, one process per GPU.
 
-    python bench.py --gpus 1 --steps 50 --warmup 10
+    python bench.py --gpus 1 --steps 50 --warmup 10 [--full] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N --steps K --warmup W
 
 Workload = the configuration BASELINE.json's metric is quoted on: VanillaVAE, configs/vae.yaml shapes (in_channels 3,
-latent_dim 128), per-GPU batch 64, fp32 end to end (parity target 1e-4 forces exact-f32 MFMA); the bs=256, MCQ-VAE and
-CT-MCQ-VAE configurations of BASELINE.json ride in the line's `configs` array.  Inputs are resident in HBM
+latent_dim 128), per-GPU batch 64, fp32 end to end (parity target 1e-4 forces exact-f32 MFMA).  Inputs are resident in HBM
 before the timed region (4 rotating synthetic batches); forward/loss/backward (+Adam at N=1) replay as ONE
-hipGraph.  Prints one JSON line (rank 0) with the throughput, a `roofline` object for the dominant kernel
-(HIP-event timed per launch through the library's own profiler, algorithmic FLOPs from the launch geometry)
-and a `cpu_baseline` object (the CPU oracle = pure-torch port of the reference arithmetic, timed on the
-host cores of this box on a bounded sample).
+hipGraph.  A plain run sets up, warms up, times --steps steps and prints one JSON line (rank 0) with the throughput and
+`ms_per_step`.
+
+--full adds what the headline does not need: a `roofline` object for the dominant kernel (HIP-event timed per launch
+through the library's own profiler, algorithmic FLOPs from the launch geometry), the per-kernel tables, the bs=256,
+MCQ-VAE and CT-MCQ-VAE configurations of BASELINE.json in the line's `configs` array, and a `cpu_baseline` object (the
+CPU oracle = pure-torch port of the reference arithmetic, timed on the host cores on a bounded sample).
+
+--dump-outputs DIR writes what the last timed step computed (losses, model outputs, parameters after the optimizer
+step, gradients) as DIR/<name>.npy, float32 / float64, at most 64 MB in all (larger arrays as a fixed seeded sample),
+so that two builds can be compared output for output on identical inputs.
 """
 import argparse
 import json
@@ -47,6 +53,11 @@ def parse():
                     help="CTMCQVAE: ct_mcq_vae.yaml shapes, action-mode pairs (x, y, one-hot action), eager launches "
                          "(the causal-transition layer has data-dependent host control flow)")
     ap.add_argument("--action-dim", type=int, default=12, help="CTMCQVAE: 12 (TShapes3D, the YAML) or 20 (TCelebA-shaped)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline does not need: roofline and per-kernel tables, the `configs` array "
+                         "and the CPU baseline (each can still be dropped with its --no-* option)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed as DIR/<name>.npy (float32/float64, <= 64 MB in all)")
     ap.add_argument("--no-configs", action="store_true", help="skip the `configs` array (bs=64, MCQVAE, CTMCQVAE entries)")
     ap.add_argument("--no-graph", action="store_true", help="launch eagerly instead of replaying a hipGraph")
     ap.add_argument("--overlap", action="store_true",
@@ -62,6 +73,10 @@ def parse():
     ap.add_argument("--cpu-seconds", type=float, default=15.0)
     ap.add_argument("--detail", action="store_true", help="per-shape kernel table on stderr (diagnostic)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if not args.full:
+        args.no_configs = args.no_cpu_baseline = args.no_roofline = True
     if args.batch is None:
         args.batch = {"VanillaVAE": 64, "MCQVAE": 256, "CTMCQVAE": 128}[args.model]
     return args
@@ -191,6 +206,34 @@ def cpu_baseline(model_name, seconds, action_dim=12):
                       f"(oracle/, torch CPU fp32, {threads} threads, {el:.1f} s)"}
 
 
+DUMP_BYTES = 64 * 10 ** 6          # --dump-outputs: all .npy files together, headers included
+OUT_NAMES = {"VanillaVAE": ("recons", "input", "mu", "log_var"), "MCQVAE": ("recons", "input", "vq_loss")}
+
+
+def dump_outputs(out_dir, arrays):
+    """Write {name: tensor} as out_dir/<name>.npy (float64 stays float64, other float types become float32; non-float
+    tensors are skipped).  When the arrays together exceed DUMP_BYTES, the budget is shared out from the smallest array up
+    and an array larger than its share is written as a fixed seeded sample of its flattened elements (sorted indices)."""
+    import numpy as np
+    arrs = {}
+    for name, t in arrays.items():
+        if t is None or not t.is_floating_point():
+            continue
+        a = t.detach().cpu()
+        a = a.numpy() if a.dtype == torch.float64 else a.float().numpy()
+        arrs[name.replace(os.sep, "_")] = a
+    os.makedirs(out_dir, exist_ok=True)
+    left = DUMP_BYTES - 256 * len(arrs)                       # npy header: 128 bytes, twice that as margin
+    for i, (name, a) in enumerate(sorted(arrs.items(), key=lambda kv: (kv[1].nbytes, kv[0]))):
+        share = left // (len(arrs) - i)
+        if a.nbytes > share:
+            k = max(1, share // a.itemsize)
+            idx = np.sort(np.random.default_rng(1265).choice(a.size, size=k, replace=False))
+            a = a.reshape(-1)[idx]
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+        left -= a.nbytes
+
+
 class Workload:
     """One benchmark configuration: model, per-GPU batch (images, or (x, y, action) pairs for CTMCQVAE), action_dim."""
 
@@ -209,9 +252,10 @@ class Workload:
         return f"{self.model} 64x64x3 train step {tail}"
 
 
-def run_workload(wl, args, ctx, want_kernels=False):
+def run_workload(wl, args, ctx, want_kernels=False, dump_dir=None):
     """Build the model of `wl`, capture its step, time exactly args.steps steps (barrier + synchronize on both sides, MAX over
-    ranks) and -- rank 0 -- time its kernels with HIP events.  Returns a dict of measurements."""
+    ranks), -- rank 0 -- write what the last timed step computed to `dump_dir` and time its kernels with HIP events unless
+    --no-roofline.  Returns a dict of measurements."""
     from ctvae_amd import filler, native
     from ctvae_amd import kernels as kernels_mod
     from ctvae_amd.ddp import GradBucketAllReduce
@@ -219,6 +263,9 @@ def run_workload(wl, args, ctx, want_kernels=False):
     rank, world, dev, multi, ddp_on = ctx["rank"], ctx["world"], ctx["dev"], ctx["multi"], ctx["ddp_on"]
     B = wl.batch
     seed = {"VanillaVAE": 1265, "MCQVAE": 1320, "CTMCQVAE": 1250}[wl.model]
+    # torch's default generators start from a per-process seed; the model's noise key (VanillaVAE draws it from them at its
+    # first forward) is fixed here so that the same arguments give the same computation in every run
+    torch.manual_seed(seed + 1000 * rank)
     model = build_model(wl.model, dev, seed, wl.action_dim)
     opt = FlatAdam(model, lr=0.005 if wl.model == "VanillaVAE" else 0.0005)
     ddp = GradBucketAllReduce(model, force=args.rehearse_ddp) if ddp_on else None
@@ -230,11 +277,24 @@ def run_workload(wl, args, ctx, want_kernels=False):
     if wl.model == "CTMCQVAE":
         _, y, act = filler.synthetic_pairs(seed + 1000 * rank, B, wl.action_dim)
         ct_kw = {"mode": ["action"] * B, "input_y": y.to(dev), "action": act.to(dev)}
+    # --dump-outputs: what the latest step handed back (detached; inside a captured step these are the graph's tensors, which
+    # every replay rewrites), the loss terms and the model's outputs.  Without it no reference is held, so that the captured
+    # step's memory pool is laid out as it always was
+    last = {}
+
+    def keep(losses, out=()):
+        if dump_dir is None:
+            return
+        last.clear()
+        last.update({"loss." + k: v.detach() for k, v in losses.items() if torch.is_tensor(v)})
+        names = OUT_NAMES.get(wl.model, ())
+        last.update({(names[i] if i < len(names) else f"out{i}"): v.detach() for i, v in enumerate(out) if torch.is_tensor(v)})
 
     def fwd_bwd():
         model.zero_grad(lazy=True)                 # as the harness does (experiment._GraphedTrainStep): no fill launch, first
         out = model(static_x, **ct_kw) if ct_kw is not None else model(static_x)     # writers overwrite their block
         losses = model.loss_function(*out, M_N=kld_w)
+        keep(losses, out)
         kernels_mod.backward(losses["loss"])       # loss.backward() with a cached root gradient (as the harness does)
         model.gather_torch_grads()                 # zeros for blocks no kernel wrote + autograd-produced gradients (CT layer) into the
                                                    # flat buffer, INSIDE the captured step (as experiment._GraphedTrainStep does)
@@ -257,7 +317,9 @@ def run_workload(wl, args, ctx, want_kernels=False):
 
     def stage1():
         model.zero_grad()
-        return split.stage1(static_x, M_N=kld_w)["loss"].detach()
+        losses = split.stage1(static_x, M_N=kld_w)
+        keep(losses)
+        return losses["loss"].detach()
 
     graph = graph2 = None
     if not args.no_graph:
@@ -336,6 +398,14 @@ def run_workload(wl, args, ctx, want_kernels=False):
     res = {"ms_per_step": elapsed / args.steps * 1e3, "value": B * world * args.steps / elapsed, "elapsed": elapsed,
            "hipgraph": graph is not None, "overlap": bool(split is not None and world > 1), "roofline": None, "kernels": None,
            "hbm_kernels": None, "roofline_ct": None}
+
+    if rank == 0 and dump_dir is not None:
+        # the last timed step's results, before anything below runs more steps: loss terms and outputs, the parameters and
+        # buffers after its optimizer step, the gradients it applied
+        arrays = dict(last)
+        arrays.update({"state." + k: v for k, v in model.state_dict().items()})
+        arrays.update({"grad." + k: p.grad for k, p in model.named_parameters() if p.grad is not None})
+        dump_outputs(dump_dir, arrays)
 
     if rank == 0 and not args.no_roofline:
         # per-kernel HIP-event timing on the launch stream (eager launches; the graph replays the same kernels)
@@ -483,7 +553,7 @@ def main():
     ctx = {"rank": rank, "world": world, "dev": dev, "multi": multi, "ddp_on": ddp_on}
 
     head = Workload(args.model, args.batch, args.action_dim)
-    r = run_workload(head, args, ctx, want_kernels=True)
+    r = run_workload(head, args, ctx, want_kernels=True, dump_dir=args.dump_outputs)
 
     # BASELINE.json configs[1..4] and the metric's own bs=64 wording, measured in the same process so that one driver-run
     # line covers them: same step contents, same timing protocol, DDP exchange included at N>1 (the >= 6x scaling target

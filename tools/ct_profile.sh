@@ -4,8 +4,8 @@ cd $GRAFT_REPO_ROOT
 export TMPDIR=/tmp
 out=gpurun_out/${TAG:-ct}
 mkdir -p $out
-python bench.py --model CTMCQVAE --batch 128 --no-cpu-baseline --no-configs > $out/ct12.json 2> $out/ct12.err
-python bench.py --model CTMCQVAE --batch 128 --action-dim 20 --no-cpu-baseline --no-configs > $out/ct20.json 2> $out/ct20.err
+python bench.py --full --model CTMCQVAE --batch 128 --no-cpu-baseline --no-configs > $out/ct12.json 2> $out/ct12.err
+python bench.py --full --model CTMCQVAE --batch 128 --action-dim 20 --no-cpu-baseline --no-configs > $out/ct20.json 2> $out/ct20.err
 rocprofv3 --kernel-trace --stats -d /tmp/ct_stats_$$ -o run -- python3 bench.py --model CTMCQVAE --batch 128 --no-cpu-baseline --no-configs --no-roofline > $out/ct12_under_rocprof.json 2> $out/ct_stats.log
 python tools/rocpd_export.py /tmp/ct_stats_$$/run_results.db > $out/ct12_kernel_stats.csv
 python - <<PY

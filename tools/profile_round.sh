@@ -10,7 +10,7 @@ parts=${PARTS:-"bench trace pmc"}
 out=gpurun_out/$tag
 mkdir -p $out
 case " $parts " in *" bench "*)
-python bench.py > $out/bench_line.json 2> $out/bench.err
+python bench.py --full > $out/bench_line.json 2> $out/bench.err
 python tools/show_bench.py $out/bench_line.json 6 || true
 ;; esac
 prof() {   # name, bench args...
