@@ -452,10 +452,8 @@ static int conv_backward_impl(int kind, const float* x, const float* dy, const f
   }
   const InXform xf{in_scale, in_shift, in_act};
   const DyXform dyx{dy_bn_y, dy_bn_coef, gy_out, dy_bn_act};
-  // diagnostic: CTVAE_IMG_BWD_FUSED=0 keeps the picture-side conv's weight gradient and data gradient as two kernels
-  static const int img_fused = [] { const char* e = getenv("CTVAE_IMG_BWD_FUSED"); return e ? atoi(e) : 1; }();
   int rc;
-  if (img_fused && bn && bn_act != ACT_TANH && x == bn_y && in_scale != nullptr && in_act == bn_act && mask == nullptr && dy_bn_y == nullptr &&
+  if (bn && bn_act != ACT_TANH && x == bn_y && in_scale != nullptr && in_act == bn_act && mask == nullptr && dy_bn_y == nullptr &&
       img_conv_supported(gw) && img_dgrad_supported(gd) && img_backward_fused_ws_floats(gd) <= half_floats) {
     // picture-side conv behind BatchNorm + activation (final_layer.1-3): the data gradient's pass over y also forms the
     // weight gradient (image.hip img_bwd_fused_kernel) -- x of the weight gradient is act(BN(y)), which that pass computes
@@ -465,9 +463,9 @@ static int conv_backward_impl(int kind, const float* x, const float* dy, const f
     rc = launch_img_backward_fused(gd, dy, w, dx, &f, ws, &part, &pb, &np, dbias != nullptr, st);
     if (!rc) rc = wgrad_finish_slabs(part, dw, 9L * 32 * 3, np, pb, dbias, 3L, accumulate, st);
   } else {
-    // (a finishing launch that carries the BatchNorm finalize of the layer below stays in the chain, without the reduction)
-    static const int defer_bn = [] { const char* e = getenv("CTVAE_DEFER_WITH_BN_RIDER"); return e ? atoi(e) : 0; }();   // diagnostic: 1.615 vs 1.611 ms (VanillaVAE)
-    float* wws = (bn_coef_out == nullptr || defer_bn) ? defer_wgrad_ws(ws, half_floats) : ws;
+    // (a finishing launch that carries the BatchNorm finalize of the layer below stays in the chain, without the reduction:
+    // deferring it too measured 1.615 vs 1.611 ms, VanillaVAE)
+    float* wws = bn_coef_out == nullptr ? defer_wgrad_ws(ws, half_floats) : ws;
     rc = launch_wgrad(gw, x, dy, dw, dbias, wws, half_bytes, accumulate, st, &xf, &dyx);
     defer_wgrad_done();
     if (!rc) {

@@ -755,20 +755,17 @@ __global__ __launch_bounds__(TPB) void bn_fused_bwd_kernel(const BnFusedBwd p) {
 
 // rows / channels the channel-owner kernels take (and the tensor size up to which their strided row accesses pay)
 bool bn_fused_ok(int R, int C) {
-  static const long max_elems = [] { const char* e = getenv("CTVAE_BN_FUSED_MAX"); return e ? atol(e) : (1L << 20); }();   // 0 = off
+  constexpr long max_elems = 1L << 20;
   return R > 0 && R % 4 == 0 && C % 4 == 0 && R <= 4096 && (long)R * C <= max_elems;
 }
 
 // threads = R / 4 rounded up to 64 / 256 / 1024; two channels per workgroup where four would leave most of the chip idle
-
-static int fused_two_below() {
-  static const int v = [] { const char* e = getenv("CTVAE_BN_FUSED_TWO"); return e ? atoi(e) : 256; }();   // diagnostic
-  return v;
-}
+// (fewer than kBnFusedTwoBelow channels)
+constexpr int kBnFusedTwoBelow = 256;
 
 #define CTVAE_BN_FUSED_LAUNCH(KERNEL, P, ST)                                                                      \
   do {                                                                                                            \
-    const bool two = (P).C < fused_two_below();                                                                   \
+    const bool two = (P).C < kBnFusedTwoBelow;                                                                    \
     const dim3 grid((P).C / (two ? 2 : 4));                                                                       \
     if ((P).R <= 256) {                                                                                           \
       if (two) hipLaunchKernelGGL((KERNEL<64, 2, 8>), grid, dim3(64), 0, ST, P);                                  \
@@ -829,17 +826,14 @@ int launch_bn_finish_forward(const float* y, int R, int C, int nparts, const flo
   float* scale = coef_out != nullptr ? coef_out : ws + parts * C * 3;   // coef_out [2][C]: kept by the caller (lazy apply)
   float* shift = scale + C;
   if (training && out != nullptr && nparts >= 1 && nparts <= 128 && C % 32 == 0) {
-    static const int on = [] { const char* e = getenv("CTVAE_BN_FIN_APPLY"); return e ? atoi(e) : 1; }();   // diagnostic: 0 = two launches
-    if (on) {
-      int rsn = 512 / (C / 32);
-      if (rsn > R / 32) rsn = R / 32;
-      if (rsn < 1) rsn = 1;
-      ProfScope ps("bn_finalize_apply_kernel", st, 0.0, 8.0 * (double)R * C + 12.0 * (double)nparts * C * rsn);
-      hipLaunchKernelGGL(bn_finalize_apply_kernel, dim3(C / 32, rsn), dim3(256), 0, st, y, ws, nparts, R, C, gamma, beta, running_mean,
-                         running_var, momentum, eps, save_mean, save_invstd, scale, shift, nbt, out, act);
-      CTVAE_LAUNCH_CHECK();
-      return 0;
-    }
+    int rsn = 512 / (C / 32);
+    if (rsn > R / 32) rsn = R / 32;
+    if (rsn < 1) rsn = 1;
+    ProfScope ps("bn_finalize_apply_kernel", st, 0.0, 8.0 * (double)R * C + 12.0 * (double)nparts * C * rsn);
+    hipLaunchKernelGGL(bn_finalize_apply_kernel, dim3(C / 32, rsn), dim3(256), 0, st, y, ws, nparts, R, C, gamma, beta, running_mean,
+                       running_var, momentum, eps, save_mean, save_invstd, scale, shift, nbt, out, act);
+    CTVAE_LAUNCH_CHECK();
+    return 0;
   }
   if (training) {
     ProfScope ps("bn_finalize_kernel", st, 0.0, 12.0 * (double)nparts * C);
@@ -910,17 +904,14 @@ int launch_bn_backward(const float* ga, const float* beta, const float* y, int R
   }
   CTVAE_LAUNCH_CHECK();
   if (part_in != nullptr && gy != nullptr && coef_out == nullptr && nb <= 256 && C % 32 == 0) {
-    static const int on = [] { const char* e = getenv("CTVAE_BN_BWD_FIN_APPLY"); return e ? atoi(e) : 1; }();   // diagnostic
-    if (on) {
-      int rsn = 512 / (C / 32);
-      if (rsn > R / 32) rsn = R / 32;
-      if (rsn < 1) rsn = 1;
-      ProfScope ps("bn_bwd_finalize_apply_kernel", st, 0.0, 12.0 * (double)R * C + 8.0 * (double)nb * C * rsn);
-      hipLaunchKernelGGL(bn_bwd_finalize_apply_kernel, dim3(C / 32, rsn), dim3(256), 0, st, ga, y, part, nb, R, C, gamma, save_mean,
-                         save_invstd, beta, act, gy, dgamma, dbeta, accumulate);
-      CTVAE_LAUNCH_CHECK();
-      return 0;
-    }
+    int rsn = 512 / (C / 32);
+    if (rsn > R / 32) rsn = R / 32;
+    if (rsn < 1) rsn = 1;
+    ProfScope ps("bn_bwd_finalize_apply_kernel", st, 0.0, 12.0 * (double)R * C + 8.0 * (double)nb * C * rsn);
+    hipLaunchKernelGGL(bn_bwd_finalize_apply_kernel, dim3(C / 32, rsn), dim3(256), 0, st, ga, y, part, nb, R, C, gamma, save_mean,
+                       save_invstd, beta, act, gy, dgamma, dbeta, accumulate);
+    CTVAE_LAUNCH_CHECK();
+    return 0;
   }
   {
     ProfScope ps("bn_bwd_finalize_kernel", st, 0.0, 8.0 * (double)nb * C);

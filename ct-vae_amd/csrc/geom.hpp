@@ -72,16 +72,6 @@ CTVAE_HD int scatter_pix(const ConvGeom& g, int cls, int b, int qy, int qx) {
   return (b * g.sH + qy * g.os + g.py[cls]) * g.sW + qx * g.os + g.px[cls];
 }
 
-// diagnostic: CTVAE_TAP_ORDER=0 keeps the plain (ky, kx) tap order of strided gathers
-inline bool tap_order_grouped() {
-#if defined(__HIP_DEVICE_COMPILE__)
-  return true;
-#else
-  static const int v = [] { const char* e = getenv("CTVAE_TAP_ORDER"); return e ? atoi(e) : 1; }();
-  return v != 0;
-#endif
-}
-
 // ---- host-side builders -------------------------------------------------------------------
 // kind: 0 conv fwd, 1 convT fwd, 2 conv dgrad, 3 convT dgrad.
 // (B,H,W,Ci) is the LAYER's input tensor, Co the layer's output channels; k,s,p,op the layer's
@@ -119,7 +109,7 @@ inline int build_geom(ConvGeom& g, int kind, int B, int H, int W, int Ci, int Co
     g.py[0] = g.px[0] = 0;
     if (k * k > kMaxTaps) return -1;
     int n = 0;
-    if (s == 2 && tap_order_grouped()) {
+    if (s == 2) {
       // Stride 2: taps whose offsets have the same parity read the SAME rows / columns of the gathered tensor, one output
       // pixel apart (ky = 0 and ky = 2 of a 3x3 both read the odd rows).  In plain (ky, kx) order a workgroup comes back to a
       // row several K chunks later -- with ~128 workgroups per L2 that is past the L2's capacity on the large tensors and the

@@ -39,7 +39,6 @@ namespace {
 
 constexpr int TH = 8, TW = 32, PH = 10, PW = 34, NP = PH * PW /*340*/, NPP = 352 /*11 x 32*/;
 constexpr int LDA = 36;          // floats per staged pixel row (32 + 4: ds_read_b128 of 8 rows hits 32 distinct banks)
-constexpr int LDZ = 33;          // floats per Z row (odd: pixel-per-lane reads are conflict-free)
 constexpr int GH = 12, GW = 36;  // zero-ringed gradient grid of the wgrad kernel (tile + 2)
 constexpr int C = 32, NO = 3, NT = 9, NJ = 27;
 constexpr unsigned kOOBi = 0x80000000u;
@@ -108,22 +107,6 @@ struct Patch {
   f32x4 v[NLD];
   unsigned ok;   // bit j: load j is inside the image
 };
-
-// slot arithmetic redone per tile: fewer live registers (img_fwd_kernel runs at 3 waves per SIMD, 170 VGPRs)
-__device__ __forceinline__ void patch_load_calc(const ImgArgs& a, __amdgpu_buffer_rsrc_t rX, const TileXY& t, Patch& p) {
-  unsigned okm = 0;
-#pragma unroll
-  for (int j = 0; j < NLD; ++j) {
-    const int e = threadIdx.x + 256 * j;
-    const int pp = e >> 3, c4 = e & 7;
-    const int py = (pp * 241) >> 13, px = pp - py * PW;   // pp / 34 for pp < 352
-    const int iy = t.y0 - 1 + py, ix = t.x0 - 1 + px;
-    const bool ok = e < NP * 8 && (unsigned)iy < (unsigned)a.H && (unsigned)ix < (unsigned)a.W;
-    p.v[j] = ld4(rX, ok ? (unsigned)(((t.b * a.H + iy) * a.W + ix) * C + 4 * c4) * 4u : kOOBi);
-    okm |= (ok ? 1u : 0u) << j;
-  }
-  p.ok = okm;
-}
 
 // per-thread constants of the 11 patch slots (tile independent): byte offset relative to the patch origin and (py, px)
 struct PatchIdx {
@@ -201,112 +184,11 @@ __device__ __forceinline__ int tap_dx(const ImgArgs& a, int t) {
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(256, 3) void img_fwd_kernel(const ImgArgs a) {
-  kernarg_warm<sizeof(ImgArgs)>();
-  __shared__ __attribute__((aligned(16))) float sA[NPP * LDA];   // patch; reused for Z [340][33]
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, li = lane & 31, lh = lane >> 5;
-  const __amdgpu_buffer_rsrc_t rX = rsrc(a.X, (long)a.B * a.H * a.W * C * 4);
-  const __amdgpu_buffer_rsrc_t rO = rsrc(a.out, (long)a.B * a.H * a.W * NO * 4);
-
-  // B operand, resident for the whole launch: breg[kg*4+q] = W'[ci = kg*8 + 4*lh + q][j = li]
-  float breg[16];
-  {
-    const int t = li / 3, co = li - 3 * t;
-    const int wt = tap_wt(a, t);
-#pragma unroll
-    for (int kk = 0; kk < 16; ++kk) {
-      const int ci = (kk >> 2) * 8 + 4 * lh + (kk & 3);
-      breg[kk] = li < NJ ? a.Wt[(wt * C + ci) * NO + co] : 0.f;
-    }
-  }
-  float bias_r[NO];
-#pragma unroll
-  for (int n = 0; n < NO; ++n) bias_r[n] = a.bias != nullptr ? a.bias[n] : 0.f;
-  int zoff[NT];   // Z row offset of tap t relative to the output pixel's own patch row
-#pragma unroll
-  for (int t = 0; t < NT; ++t) zoff[t] = (a.tdy[t] * PW + a.tdx[t]) * LDZ + 3 * t;
-  for (int e = tid; e < (NPP - NP) * LDA; e += 256) sA[NP * LDA + e] = 0.f;   // MFMA rows beyond the patch
-
-  Patch pt;
-  int tile = blockIdx.x;
-  TileXY cur = tile_xy(a, tile < a.ntiles ? tile : 0);
-  if (tile < a.ntiles) patch_load_calc(a, rX, cur, pt);
-  int it = 0;
-  IPHASE(0);
-  for (; tile < a.ntiles; tile += gridDim.x, ++it) {
-    patch_store(a, pt, sA);
-    IPHASE(1 + 6 * it);
-    __syncthreads();
-    IPHASE(2 + 6 * it);
-    const int next = tile + gridDim.x;
-    const TileXY nxt = tile_xy(a, next < a.ntiles ? next : 0);
-    if (next < a.ntiles) patch_load_calc(a, rX, nxt, pt);   // in flight during the MFMA / gather phases
-
-    IPHASE(3 + 6 * it);
-    // ---- Z = patch x W' : wave w takes the 32-row blocks w, w+4, w+8 ----
-    f32x16 acc[3];
-#pragma unroll
-    for (int i = 0; i < 3; ++i) {
-      const int mt = wave + 4 * i;
-#pragma unroll
-      for (int r = 0; r < 16; ++r) acc[i][r] = 0.f;
-      if (mt < NPP / 32) {
-#pragma unroll
-        for (int kg = 0; kg < 4; ++kg) {
-          const f32x4 af = *reinterpret_cast<const f32x4*>(&sA[(mt * 32 + li) * LDA + kg * 8 + 4 * lh]);
-#pragma unroll
-          for (int q = 0; q < 4; ++q) acc[i] = __builtin_amdgcn_mfma_f32_32x32x2f32(af[q], breg[kg * 4 + q], acc[i], 0, 0, 0);
-        }
-      }
-    }
-    IPHASE(4 + 6 * it);
-    __syncthreads();   // every wave is done reading the patch: its memory becomes Z
-    float* sZ = sA;
-#pragma unroll
-    for (int i = 0; i < 3; ++i) {
-      const int mt = wave + 4 * i;
-      if (mt < NPP / 32 && li < NJ) {
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-          const int row = mt * 32 + 8 * (r >> 2) + 4 * lh + (r & 3);
-          if (row < NP) sZ[row * LDZ + li] = acc[i][r];
-        }
-      }
-    }
-    __syncthreads();
-    IPHASE(5 + 6 * it);
-    // ---- gather: one thread per output pixel ----
-    {
-      const int ly = tid >> 5, lx = tid & 31;
-      const float* z = sZ + ((ly + 1) * PW + lx + 1) * LDZ;
-      float o[NO];
-#pragma unroll
-      for (int n = 0; n < NO; ++n) o[n] = bias_r[n];
-#pragma unroll
-      for (int t = 0; t < NT; ++t)
-#pragma unroll
-        for (int n = 0; n < NO; ++n) o[n] += z[zoff[t] + n];
-      const unsigned off = (unsigned)(((cur.b * a.H + cur.y0 + ly) * a.W + cur.x0 + lx) * NO) * 4u;
-      if (a.act == ACT_TANH) {   // the reference's final layer (vanilla_vae.py:73-75); decided once, not per value
-#pragma unroll
-        for (int n = 0; n < NO; ++n) st1(rO, off + 4u * n, act_fwd(o[n], ACT_TANH));
-      } else {
-#pragma unroll
-        for (int n = 0; n < NO; ++n) st1(rO, off + 4u * n, act_slope_fwd(o[n], act_slope(a.act)));
-      }
-    }
-    IPHASE(6 + 6 * it);
-    __syncthreads();   // Z consumed before the next patch lands
-    cur = nxt;
-  }
-}
-
-// ---------------------------------------------------------------------------------------------------------------------
-// The same forward with the 32-channel operand going from global memory STRAIGHT into the MFMA A registers: lane (pixel li,
+// Forward, with the 32-channel operand going from global memory STRAIGHT into the MFMA A registers: lane (pixel li,
 // half lh) of a 32-pixel block loads channels [16 lh, 16 lh + 16) of its patch pixel with four 16-byte loads (two lanes cover
 // the pixel's 128 bytes), applies the lazy BatchNorm + activation in registers, and the K steps pair channel s with channel
 // 16 + s (the B registers are permuted to match).  No staging of the patch in LDS, no prefetch buffer in registers: LDS holds
-// only Z (340 x 29 floats = 39 KB), so FOUR workgroups fit a CU (img_fwd_kernel: 51 KB and 162 VGPRs -> three), and a wave's
+// only Z (340 x 29 floats = 39 KB), so FOUR workgroups fit a CU (staging the patch in LDS: 51 KB and 162 VGPRs -> three), and a wave's
 // next block is in flight while it multiplies the current one.
 constexpr int LDZ2 = 29;   // odd: the pixel-per-lane gather reads are conflict-free; 4 x 340 x 29 x 4 B = 157.8 KB per CU
 __global__ __launch_bounds__(256, 4) void img_fwd2_kernel(const ImgArgs a) {
@@ -1137,10 +1019,8 @@ int launch_img_enc_wgrad(const ConvGeom& g, const float* X, const float* dY, flo
   return 0;
 }
 
-// persistent grids (diagnostic overrides: CTVAE_IMG_FWD_WGS / CTVAE_IMG_WGRAD_WGS / CTVAE_IMG_DGRAD_WGS)
-static int env_int(const char* name, int dflt) { const char* e = getenv(name); return e ? atoi(e) : dflt; }
-static const int kImgFwdWgs = env_int("CTVAE_IMG_FWD_WGS", 768), kImgWgradWgs = env_int("CTVAE_IMG_WGRAD_WGS", 512),
-                 kImgDgradWgs = env_int("CTVAE_IMG_DGRAD_WGS", 1024);
+// persistent grids
+constexpr int kImgFwd2Wgs = 1024, kImgWgradWgs = 512, kImgDgradWgs = 1024;
 
 int img_wgrad_parts(const ConvGeom& g) {
   const int nt = g.B * (g.sH / TH) * (g.sW / TW);
@@ -1157,16 +1037,10 @@ int launch_img_forward(const ConvGeom& g, const float* X, const float* W, const 
   fill(a, g);
   a.X = X; a.Wt = W; a.bias = bias; a.out = S; a.act = act;
   if (xf != nullptr && xf->scale != nullptr) { a.scale = xf->scale; a.shift = xf->shift; a.in_act = xf->act; }
-  static const int v2 = env_int("CTVAE_IMG_FWD2", 1), wgs2 = env_int("CTVAE_IMG_FWD2_WGS", 1024);   // diagnostic
+  // (profiled under the name of the LDS-staged kernel it replaced)
   ProfScope ps("img_fwd_kernel", st, 2.0 * a.ntiles * TH * TW * NT * C * NO, 4.0 * a.ntiles * TH * TW * (C + NO));
-  if (v2) {   // A operand straight from global memory, four workgroups per CU
-    const int nwg = a.ntiles < wgs2 ? a.ntiles : wgs2;
-    hipLaunchKernelGGL(img_fwd2_kernel, dim3(nwg), dim3(256), 0, st, a);
-    CTVAE_LAUNCH_CHECK();
-    return 0;
-  }
-  const int nwg = a.ntiles < kImgFwdWgs ? a.ntiles : kImgFwdWgs;
-  hipLaunchKernelGGL(img_fwd_kernel, dim3(nwg), dim3(256), 0, st, a);
+  const int nwg = a.ntiles < kImgFwd2Wgs ? a.ntiles : kImgFwd2Wgs;
+  hipLaunchKernelGGL(img_fwd2_kernel, dim3(nwg), dim3(256), 0, st, a);
   CTVAE_LAUNCH_CHECK();
   return 0;
 }

@@ -469,14 +469,13 @@ int launch_pair_mlp_forward(const float* u, const float* v, int ld, const float*
                             int H, float slope, int per_sample, const int* row_of, hipStream_t st) {
   if (B <= 0 || N <= 0 || H <= 0 || ld < H) return kErrBadArg;
   ProfScope ps((N == 64 && H % 4 == 0 && ld % 4 == 0) ? "pair_mlp_fwd64_kernel" : "pair_mlp_fwd_kernel", st, 3.0 * B * (double)N * N * H, 4.0 * B * (2.0 * N * H + (double)N * N));
-  static const bool old_fwd = getenv("CTVAE_PAIR_FWD_OLD") != nullptr;      // diagnostic: the (i, 4 j) kernel
-  if (N == 64 && H % 4 == 0 && ld % 4 == 0 && !old_fwd && (reinterpret_cast<uintptr_t>(w2) & 15) == 0) {   // w2 rows are read as float4
+  if (N == 64 && H % 4 == 0 && ld % 4 == 0 && (reinterpret_cast<uintptr_t>(w2) & 15) == 0) {   // w2 rows are read as float4
     hipLaunchKernelGGL(pair_mlp_fwd64b_kernel, dim3(4, B), dim3(256), 0, st, u, v, w2, b2, out, H, ld, slope, per_sample ? H : 0,
                        per_sample ? 1 : 0, per_sample ? row_of : nullptr);
     CTVAE_LAUNCH_CHECK();
     return 0;
   }
-  if (N == 64 && H % 4 == 0 && ld % 4 == 0) {
+  if (N == 64 && H % 4 == 0 && ld % 4 == 0) {   // unaligned w2: the (i, 4 j) kernel
     hipLaunchKernelGGL(pair_mlp_fwd64_kernel, dim3(4, B), dim3(256), 0, st, u, v, w2, b2, out, H, ld, slope, per_sample ? H : 0,
                        per_sample ? 1 : 0, per_sample ? row_of : nullptr);
     CTVAE_LAUNCH_CHECK();
@@ -492,8 +491,7 @@ int launch_pair_mlp_backward(const float* u, const float* v, int ld, const float
                              float* dU, float* dV, int ldd, float* dw2_part, float* db2_part, int B, int N, int H, float slope,
                              int per_sample, const int* row_of, hipStream_t st) {
   if (B <= 0 || N <= 0 || H <= 0 || N > NMAX || ld < H || ldd < H) return kErrBadArg;
-  static const bool old_bwd = getenv("CTVAE_PAIR_BWD_OLD") != nullptr;      // diagnostic: the any-N kernel at N == 64 too
-  if (N == 64 && !old_bwd) {
+  if (N == 64) {
     ProfScope ps("pair_mlp_bwd64_kernel", st, 5.0 * B * (double)N * N * H,      // clamped add + two fmas per (pair, h)
                  4.0 * B * (4.0 * N * H + 2.0 * N * N));
     // 4-wave workgroups: ceil(nw / 4) per sample.  (5-wave workgroups tile H = 800 exactly but only two of them fit a CU's wave

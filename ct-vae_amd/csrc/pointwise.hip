@@ -371,7 +371,8 @@ size_t adam_state_floats() { return kAdamStateFloats; }
 
 int launch_adam(float* p, const float* g, float* m, float* v, float* state, long n, float grad_scale, hipStream_t st) {
   ProfScope ps("adam_kernel", st, 0.0, 28.0 * (double)n);
-  static const int wgs = [] { const char* e = getenv("CTVAE_ADAM_WGS"); const int w = e ? atoi(e) : 1024; return w > kAdamMaxWgs ? kAdamMaxWgs : w; }();   // diagnostic
+  constexpr int wgs = 1024;
+  static_assert(wgs <= kAdamMaxWgs, "the Adam state is sized for kAdamMaxWgs workgroups");
   const bool vec = ((reinterpret_cast<uintptr_t>(p) | reinterpret_cast<uintptr_t>(g) | reinterpret_cast<uintptr_t>(m) |
                      reinterpret_cast<uintptr_t>(v)) % 16) == 0;
   if (vec) hipLaunchKernelGGL(adam_kernel<true>, dim3(grid_for(n / 4, wgs)), dim3(256), 0, st, p, g, m, v, state, n, grad_scale);

@@ -574,13 +574,11 @@ void tapgemm_plan(const ConvGeom& g, size_t ws_floats, TapGemmPlan& p) {
     const long tiles128 = (long)ceil_div(Mc, 128) * ceil_div(N, 64) * g.ncls;
     // 128-row tiles only for long reductions: with <= 72 K-chunks per workgroup the launch is dominated by its prologue /
     // epilogue phases and twice as many 64-row workgroups hide them better (measured, MI355X: VanillaVAE bs=256 step
-    // 1.913 -> 1.879 ms, MCQVAE 8.15 -> 7.93 ms; CTVAE_SHORT_K overrides the threshold for experiments)
-    static const int short_k = [] { const char* e = getenv("CTVAE_SHORT_K"); return e ? atoi(e) : 72; }();
+    // 1.913 -> 1.879 ms, MCQVAE 8.15 -> 7.93 ms)
+    constexpr int short_k = 72;
     int kch = 1 << 30;
     for (int c = 0; c < g.ncls; ++c) kch = g.ntaps[c] * g.gC / KC < kch ? g.ntaps[c] * g.gC / KC : kch;
     p.BM = (tiles128 >= 512 && kch > short_k) ? 128 : 64;
-    static const int force_bm = [] { const char* e = getenv("CTVAE_FORCE_BM"); return e ? atoi(e) : 0; }();   // diagnostic
-    if (force_bm == 64 || force_bm == 128) p.BM = force_bm;
     p.BN = 64;
   }
   p.mtiles = ceil_div(Mc, p.BM);
@@ -591,30 +589,26 @@ void tapgemm_plan(const ConvGeom& g, size_t ws_floats, TapGemmPlan& p) {
     const int nch = avec ? g.ntaps[c] * g.gC / KC : ceil_div(g.ntaps[c] * g.gC, KC);
     if (nch < nch_min) nch_min = nch;
   }
-  static const int sk_target = [] { const char* e = getenv("CTVAE_SK_TARGET"); return e ? atoi(e) : 768; }();   // diagnostic
+  constexpr int sk_target = 768;
   // a launch that already has a workgroup for every CU is not split (round 3: 384 -> 256; the bs = 64 step's encoder.1 -- 256
   // tiles of 9 chunks -- keeps its BatchNorm statistics in the epilogue instead of three launches behind two slices: -1.4 %
   // there, +-0.3 % on the other configurations)
-  static const int sk_maxwgs = [] { const char* e = getenv("CTVAE_SK_MAXWGS"); return e ? atoi(e) : 256; }();
+  constexpr int sk_maxwgs = 256;
   // a data gradient that shares its launch with the weight gradient (ctvae_conv_backward) does not have to fill the chip
   // on its own: the ~1000 weight-gradient workgroups do.  It is split only as far as its workgroups would otherwise be the
   // launch's long pole -- fewer partial sums to write and finish, and an unsplit launch keeps the fused BatchNorm-backward
   // sums in its epilogue (no bn_bwd_partial pass)
-  static const int pair_target = [] { const char* e = getenv("CTVAE_PAIR_SK_TARGET"); return e ? atoi(e) : 256; }();   // sweep, ms per step: 768 1.804, 512 1.798, 384 1.800, 256 1.796, 128 1.813, no split 1.847
-  static const int pair_maxwgs = [] { const char* e = getenv("CTVAE_PAIR_SK_MAXWGS"); return e ? atoi(e) : 384; }();
+  constexpr int pair_target = 256;   // sweep, ms per step: 768 1.804, 512 1.798, 384 1.800, 256 1.796, 128 1.813, no split 1.847
+  constexpr int pair_maxwgs = 384;
   const bool paired = pair_ctx() != nullptr && g.wT != 0;
-  // small problems (few scattered pixels in all): every slice is another copy of the output to write, flush at the kernel
-  // boundary and sum again -- a lower target (fewer, longer slices) wins there
-  static const int sk_small_m = [] { const char* e = getenv("CTVAE_SK_SMALL_M"); return e ? atoi(e) : 0; }();
-  static const int sk_small_target = [] { const char* e = getenv("CTVAE_SK_SMALL_TARGET"); return e ? atoi(e) : 256; }();
-  const int tgt = paired ? pair_target : ((long)Mc * g.ncls <= sk_small_m ? sk_small_target : sk_target), maxw = paired ? pair_maxwgs : sk_maxwgs;
+  const int tgt = paired ? pair_target : sk_target, maxw = paired ? pair_maxwgs : sk_maxwgs;
   // paired with a reduction of fewer than 16 chunks (K < 512: the Linear heads' data gradient): splitting saves ~1 us of a
   // launch the weight gradient fills anyway and would cost the fused BatchNorm-backward sums of the layer below
-  static const int pair_minch = [] { const char* e = getenv("CTVAE_PAIR_SK_MINCH"); return e ? atoi(e) : 8; }();   // round 3: 16 -> 8 (the slices go to the BatchNorm's channel-owner launch: bs = 64 -0.9 %, bs = 256 -0.3 %)
+  constexpr int pair_minch = 8;   // round 3: 16 -> 8 (the slices go to the BatchNorm's channel-owner launch: bs = 64 -0.9 %, bs = 256 -0.3 %)
   if (avec && bvec && (N % 4) == 0 && wgs < maxw && nch_min >= (paired ? pair_minch : 8)) {
     int sk = (int)((tgt + wgs - 1) / wgs);
     if (sk > nch_min / 4) sk = nch_min / 4;
-    static const int sk_max = [] { const char* e = getenv("CTVAE_SK_MAX"); return e ? atoi(e) : 16; }();   // diagnostic
+    constexpr int sk_max = 16;
     if (sk > sk_max) sk = sk_max;
     const size_t per = (size_t)g.B * g.sH * g.sW * N;
     while (sk > 1 && per * sk > ws_floats) --sk;
@@ -737,11 +731,8 @@ int launch_tapgemm(const ConvGeom& g, const float* G, const float* W, const floa
     rc = launch_masked(a, wt, avec, bvec, st);
   } else {
     // few workgroups per CU -> latency must be hidden inside the workgroup (double-buffered LDS); many -> by occupancy
-    static const long pf_wgs = [] { const char* e = getenv("CTVAE_PF_WGS"); return e ? atol(e) : 1024L; }();   // diagnostic
-    static const int force_pf = [] { const char* e = getenv("CTVAE_FORCE_PF"); return e ? atoi(e) : -1; }();   // diagnostic
-    bool db = (long)plan.mtiles * plan.ntiles * g.ncls * plan.splitk <= pf_wgs;
-    if (force_pf == 0) db = false;
-    if (force_pf == 3) db = true;
+    constexpr long pf_wgs = 1024;
+    const bool db = (long)plan.mtiles * plan.ntiles * g.ncls * plan.splitk <= pf_wgs;
     // measured (bench.py, VanillaVAE bs=256): pipelined double-buffer loop 2.35 ms vs 2.37 (plain double buffer) vs 2.42
     // when the large grids use it too (LDS doubling costs them occupancy)
     rc = launch_tapgemm_fast(a, plan, db ? 3 : 0, st);

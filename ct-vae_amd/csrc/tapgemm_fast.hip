@@ -87,7 +87,7 @@ __global__ __launch_bounds__(256) void tapgemm_fast_kernel(const TapGemmArgs a) 
 // PDA: prefetch depth (chunks) of the data-gradient role's global loads (4 for launches of at most two workgroups per CU)
 template <bool XFB, int PDA = 1>
 __global__ __launch_bounds__(256) void conv_bwd_pair_kernel(const TapGemmArgs a, const WgradArgs w, int lgQw, int lgQhw, int lgC,
-                                                            int nA, int gxA, int gyA, int gxB, int gyB, int role_xcd_on) {
+                                                            int nA, int gxA, int gyA, int gxB, int gyB) {
   // the data-gradient kernel's arrays; the weight-gradient workgroups use the first 8 KB of each for their X / dY chunks
   __shared__ __attribute__((aligned(16))) float sAbuf[2 * 64 * LDK];
   __shared__ __attribute__((aligned(16))) float sBbuf[2 * 64 * LDK];
@@ -101,7 +101,7 @@ __global__ __launch_bounds__(256) void conv_bwd_pair_kernel(const TapGemmArgs a,
   constexpr int kOffW = (sizeof(TapGemmArgs) + 7) / 8 * 8, kOffI = kOffW + sizeof(WgradArgs);
   static_assert(alignof(TapGemmArgs) == 8 && alignof(WgradArgs) == 8 && sizeof(WgradArgs) % 8 == 0, "kernel-argument layout");
   int k_nA, k_gxA, k_gyA;
-  kernarg_warm_get<kOffI + 9 * 4, kOffI + 12, kOffI + 16, kOffI + 20>(k_nA, k_gxA, k_gyA);
+  kernarg_warm_get<kOffI + 8 * 4, kOffI + 12, kOffI + 16, kOffI + 20>(k_nA, k_gxA, k_gyA);
   const int L = blockIdx.x;
   if (L < k_nA) {
     constexpr int WM = 2, WN = 2, TM = 1, TN = 1, PF = 3;
@@ -111,21 +111,12 @@ __global__ __launch_bounds__(256) void conv_bwd_pair_kernel(const TapGemmArgs a,
     const int k_cls_rot = a.cls_rot, k_ntiles = a.ntiles;
 #include "tapgemm_fast_body.inc"
   } else {
+    // (Role-aware XCD placement -- the weight-gradient workgroups of XCD X taking the same eighth of the pixels as the
+    // data-gradient role, slice count rounded to a multiple of 8 -- cut the BatchNorm layers' paired launches' fetch traffic
+    // 51.2 -> 39.7 MB per launch but LOST: VanillaVAE bs = 256 1.599 -> 1.612 ms per step, the rounding costing more than the
+    // L2 hits return to an MFMA-bound launch.  Removed.)
     const int Lb = L - k_nA;
-    // Role-aware XCD placement (round 3).  Workgroups go to the 8 XCDs round-robin by their launch index L.  The data-gradient
-    // role gives XCD X a contiguous eighth of its tiles, i.e. of the dY pixel range it gathers; the weight-gradient role used to
-    // deal its pixel slices to the XCDs by (slice & 7), so every L2 fetched dY once for each role.  With S % 8 == 0 slices the
-    // weight-gradient workgroups of XCD X now take the slices [X*S/8, (X+1)*S/8) -- the same eighth of the pixels -- and all
-    // output tiles of a slice stay on one XCD as before.  Measured (VanillaVAE bs = 256, two --pmc passes each): fetch traffic of
-    // the BatchNorm layers' paired launches 51.2 -> 39.7 MB per launch, 3.35 -> 3.28 GB per step -- and 1.599 -> 1.612 ms per
-    // step (three alternating runs), the slice count rounded to a multiple of 8 costing more than the L2 hits return to an
-    // MFMA-bound launch.  Hence OFF by default (CTVAE_PAIR_ROLE_XCD=1 turns it on, e.g. where the fabric is shared with RCCL).
-    if (gyB % 8 == 0 && role_xcd_on) {
-      const int X = L & 7, j = Lb >> 3, T = gxB;
-      wgrad_fast_body<2, 2, 1, 1, XFB, true>(w, lgQw, lgQhw, lgC, sAbuf, sBbuf, sPix, sMsk, sOutB, j % T, X * (gyB >> 3) + j / T, gxB, gyB);
-    } else {
-      wgrad_fast_body<2, 2, 1, 1, XFB>(w, lgQw, lgQhw, lgC, sAbuf, sBbuf, sPix, sMsk, sOutB, Lb % gxB, Lb / gxB, gxB, gyB);
-    }
+    wgrad_fast_body<2, 2, 1, 1, XFB>(w, lgQw, lgQhw, lgC, sAbuf, sBbuf, sPix, sMsk, sOutB, Lb % gxB, Lb / gxB, gxB, gyB);
   }
 }
 
@@ -148,8 +139,7 @@ static int launch_fast_cfg(const TapGemmArgs& a, int pf, hipStream_t st) {
   // interleaved in groups of 8 workgroups 1.880 ms against 1.849 / 1.857 ms (same box).
   for (int c = 0; c < kMaxCls; ++c) args.cls_order[c] = c;
   args.cls_rot = 0;
-  static const int no_cls_order = [] { const char* e = getenv("CTVAE_NO_CLS_ORDER"); return e ? atoi(e) : 0; }();   // diagnostic
-  if (a.g.ncls == 4 && !no_cls_order) {
+  if (a.g.ncls == 4) {
     int idx[4] = {0, 1, 2, 3};
     for (int i = 1; i < 4; ++i)
       for (int j = i; j > 0 && a.g.ntaps[idx[j]] < a.g.ntaps[idx[j - 1]]; --j) { const int t = idx[j]; idx[j] = idx[j - 1]; idx[j - 1] = t; }
@@ -157,10 +147,6 @@ static int launch_fast_cfg(const TapGemmArgs& a, int pf, hipStream_t st) {
     if (total <= 1024) {
       args.cls_order[0] = idx[0]; args.cls_order[1] = idx[1]; args.cls_order[2] = idx[3]; args.cls_order[3] = idx[2];
       args.cls_rot = grid.z > 1 ? 1 : 0;
-    } else {
-      static const int big = [] { const char* e = getenv("CTVAE_CLS_BIG"); return e ? atoi(e) : 0; }();   // diagnostic: 1 longest first, 2 interleaved -- both measured slower (below)
-      if (big == 1) for (int c = 0; c < 4; ++c) args.cls_order[c] = idx[3 - c];
-      if (big == 2 && grid.x % 8 == 0 && grid.z == 1) args.cls_rot = 2;
     }
   }
   for (int i = 0; i < kMaxCls; ++i) {   // launch-order copies of the tap table (TapGemmArgs::taps_l)
@@ -218,10 +204,9 @@ int pair_flush(PairCtx& c, hipStream_t st) {
   if (c.haveA && c.haveB) {
     const unsigned nA = c.gxA * c.gyA * c.gzA, nB = c.gxB * c.gyB;
     ProfScope ps("conv_bwd_pair_kernel", st, c.flopsA + c.flopsB, c.bytesA + c.bytesB);
-    static const int role_xcd = [] { const char* e = getenv("CTVAE_PAIR_ROLE_XCD"); return e ? atoi(e) : 0; }();   // 1 = role-aware placement (see the kernel)
 #define CTVAE_PAIR(XFB_, PD_)                                                                                                  \
   hipLaunchKernelGGL((conv_bwd_pair_kernel<XFB_, PD_>), dim3(nA + nB), dim3(256), 0, st, c.A, c.B, c.lgQw, c.lgQhw, c.lgC, (int)nA, \
-                     (int)c.gxA, (int)c.gyA, (int)c.gxB, (int)c.gyB, role_xcd)
+                     (int)c.gxA, (int)c.gyA, (int)c.gxB, (int)c.gyB)
     if (c.B.xf_scale != nullptr) CTVAE_PAIR(true, 1);
     else CTVAE_PAIR(false, 1);
 #undef CTVAE_PAIR

@@ -445,8 +445,7 @@ int launch_vq_inds(const float* lat, const float* cb, long long* inds, int B, in
   if (K <= 64 && (Dc == 32 || Dc == 64 || Dc == 128)) {
     // rows per workgroup: the codebook is staged per workgroup (measured at 16 / 32 / 64 rows: 40.8 / 38.2 / 36.9 us for Dc = 128,
     // 25.2 / 24.7 / 25.8 us for Dc = 32)
-    static const int rpw_env = [] { const char* e = getenv("CTVAE_VQ_ROWS"); return e ? atoi(e) : 0; }();   // diagnostic override
-    const int rpw = rpw_env ? rpw_env : (Dc == 128 ? 64 : 16);
+    const int rpw = Dc == 128 ? 64 : 16;
     int nb = ceil_div(P, rpw);
     if (nb > 2048) nb = 2048;
     const int rp = ceil_div(P, nb);

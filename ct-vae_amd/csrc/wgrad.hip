@@ -395,7 +395,7 @@ static int reduce_job_blocks(ReduceJob& j) {
   if (j.n <= 0 || j.S <= 0) return 0;
   j.vec = ((j.n & 3) == 0 && (j.stride & 3) == 0 && (((uintptr_t)j.part | (uintptr_t)j.dst) & 15) == 0) ? 1 : 0;
   const long items = j.vec ? j.n / 4 : j.n;
-  static const long wide_items = [] { const char* e = getenv("CTVAE_REDUCE_WIDE_ITEMS"); return e ? atol(e) : 65536L; }();   // diagnostic
+  constexpr long wide_items = 65536;
   j.small = j.S <= 8 ? 1 : (items >= wide_items ? 2 : 0);
   return (int)(j.small == 1 ? (items + 255) / 256 : (j.small == 2 ? (items + 63) / 64 : (items + 15) / 16));
 }
@@ -596,10 +596,9 @@ static int choose_splits(const ConvGeom& g, int KT, int NT, size_t ws_floats, in
   if (S < 1) S = 1;
   // at least 8 chunks of 32 pixels per split (4 for pixel ranges below 32 chunks: the Linear layers' rows).  Round 3, after the
   // kernels' prologues / epilogues got cheaper, the small-batch step prefers half as many, twice as long weight-gradient workgroups
-  // (CTVAE_WGRAD_MIN_CHUNKS 4 / 6 / 8 / 12 / 16 at bs = 64: 0.7355 / 0.7305 / 0.7226 / 0.7304 / 0.7554 ms; bs = 256 and the
+  // (minimum 4 / 6 / 8 / 12 / 16 chunks at bs = 64: 0.7355 / 0.7305 / 0.7226 / 0.7304 / 0.7554 ms; bs = 256 and the
   // Winograd models are bounded by the workgroup target, not by this)
-  static const int min_chunks_env = [] { const char* e = getenv("CTVAE_WGRAD_MIN_CHUNKS"); return e ? atoi(e) : 0; }();   // diagnostic
-  const int min_chunks = min_chunks_env > 0 ? min_chunks_env : (nchunks >= 32 ? 8 : 4);
+  const int min_chunks = nchunks >= 32 ? 8 : 4;
   int maxS = ceil_div(nchunks, min_chunks);
   if (maxS < 1) maxS = 1;
   if (S > maxS) S = maxS;
@@ -686,8 +685,7 @@ int launch_wgrad(const ConvGeom& g, const float* X, const float* dY, float* dW, 
   const bool xvec = (g.gC % 4) == 0, dvec = (a.N % 4) == 0;
   const bool narrow = a.N <= 32;
   // 128x128 tiles for wide layers whose pixel range still leaves >= 8 chunks per workgroup at ~1024 workgroups
-  static const int no_big = [] { const char* e = getenv("CTVAE_WGRAD_NO_BIG"); return e ? atoi(e) : 0; }();   // diagnostic
-  bool big = !no_big && !has_xf && xvec && dvec && (a.N % 128) == 0 && a.Mc >= 8192;
+  bool big = !has_xf && xvec && dvec && (a.N % 128) == 0 && a.Mc >= 8192;
   if (has_xf) { a.xf_scale = xf->scale; a.xf_shift = xf->shift; a.xf_act = xf->act; }
   for (int c = 0; c < g.ncls && big; ++c) big = (g.ntaps[c] * g.gC) % 128 == 0;
   if (big) {
@@ -706,16 +704,10 @@ int launch_wgrad(const ConvGeom& g, const float* X, const float* dY, float* dW, 
   // data-gradient workgroups (the 1x1 convs of the residual stacks, 8 chunks) or a data gradient that is a round or more by
   // itself (the 4x4 convs of MCQ / CT-MCQ-VAE) the finer split wins.  One target everywhere, 768 / 1024: VanillaVAE bs=256
   // 1.719 / 1.723 ms, MCQVAE bs=256 7.65 / 7.53 ms, CT-MCQ-VAE 128 pairs 7.19 / 7.15 ms.
-  static const int tgt_env = [] { const char* e = getenv("CTVAE_WGRAD_WGS"); return e ? atoi(e) : 0; }();   // diagnostic override
   const PairCtx* pcw = pair_ctx();
   const bool will_pair = pcw != nullptr && !pcw->haveB && xvec && dvec && !narrow && !big;
   const bool coarse = will_pair && pcw->dgrad_wgs > 0 && pcw->dgrad_wgs < 1024 && pcw->dgrad_chunks >= 12;
-  const int tgt_small = tgt_env ? tgt_env : (coarse ? 768 : 1024);
-  int S = choose_splits(g, KT, NT, ws_floats, big ? 512 : tgt_small);
-  // paired launch: a multiple of 8 slices lets the pair kernel give each XCD one contiguous eighth of the pixels in BOTH roles
-  // (conv_bwd_pair_kernel, role-aware placement); rounded down, never below 8 nor above what the workspace / chunk count allow
-  static const int role_xcd = [] { const char* e = getenv("CTVAE_PAIR_ROLE_XCD"); return e ? atoi(e) : 0; }();
-  if (will_pair && role_xcd && S >= 8) S &= ~7;
+  const int S = choose_splits(g, KT, NT, ws_floats, big ? 512 : (coarse ? 768 : 1024));
   if (wgrad_workspace_floats(g, S) > ws_floats) return kErrWorkspace;
   a.S = S;
   const int nchunks = ceil_div(a.Mc, MC);

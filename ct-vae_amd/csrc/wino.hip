@@ -1135,18 +1135,12 @@ bool wino_block(const ConvGeom& g, int& bh, int& bw, int& nb) {
 
 }  // namespace
 
-// process-wide switch (ctvae_winograd_enable): on unless the environment says CTVAE_NO_WINOGRAD=1
-static int g_wino_on = -1;
-bool wino_enabled() {
-  if (g_wino_on < 0) {
-    const char* e = getenv("CTVAE_NO_WINOGRAD");
-    g_wino_on = (e != nullptr && e[0] == '1') ? 0 : 1;
-  }
-  return g_wino_on != 0;
-}
+// process-wide switch (ctvae_winograd_enable): on by default, tests turn it off to compare against the direct kernels
+static bool g_wino_on = true;
+bool wino_enabled() { return g_wino_on; }
 int wino_set_enabled(int on) {
-  const int prev = wino_enabled() ? 1 : 0;
-  g_wino_on = on ? 1 : 0;
+  const int prev = g_wino_on ? 1 : 0;
+  g_wino_on = on != 0;
   return prev;
 }
 

@@ -12,7 +12,6 @@ Conventions
 * No op here has a PyTorch/CPU fallback: a missing library or a CPU tensor raises.
 """
 import math
-import os
 import weakref
 from dataclasses import dataclass
 
@@ -67,9 +66,6 @@ def grad_target(p):
         blk.fresh = False
         return p.grad, 0
     return p.grad, 1
-
-
-LAZY_ZERO_GRAD = os.environ.get("CTVAE_NO_LAZY_ZERO", "0") != "1"     # diagnostic: zero_grad(lazy=True) fills like zero_grad()
 
 
 # ---------------------------------------------------------------------------------------------------
@@ -157,7 +153,7 @@ class _WinoFilterCache:
 
 
 wino_cache = _WinoFilterCache()
-_WINO_BATCH = os.environ.get("CTVAE_NO_WINO_BATCH", "0") != "1"     # diagnostic: one filter-transform launch per layer
+_WINO_BATCH = True     # False: one filter-transform launch per layer (tests compare the two)
 
 
 def _wino_filters_for(ctx_needs_grad, w, spec, B, H, W_):
@@ -188,7 +184,7 @@ class BNLink:
     """Hand-over between a train-mode ConvBNAct layer and the layer that consumes its output ``a``.
 
     The consumer's data-gradient kernel produces g_a; given the BatchNorm's y/mean/invstd/gamma/beta it also emits the
-    per-tile backward sums (ctvae_conv_dgrad_bn), which the BatchNorm's own backward then takes instead of running a
+    per-tile backward sums (ctvae_conv_backward), which the BatchNorm's own backward then takes instead of running a
     separate pass over (g_a, y).  The sums are only used when the gradient tensor that arrives is exactly the one the
     dgrad wrote (same storage pointer, same version counter): if autograd summed several contributions, or anything
     modified it in place, the BatchNorm falls back to its own pass."""
@@ -372,7 +368,7 @@ def bn_apply_is_separate(spec, B, H, W) -> bool:
 def lazy_bn_input_supported(spec, B, H, W) -> bool:
     """Can a train-mode ConvBNAct layer of this geometry read its input through the previous block's BatchNorm + activation
     (forward tile kernel and weight-gradient kernel both transform on load: ctvae_conv_input_transform_supported)?"""
-    return _LAZY_BN and input_transform_supported(spec, B, H, W)      # (the tile kernels form max(t, slope*t): LeakyReLU / ReLU / none)
+    return input_transform_supported(spec, B, H, W)      # (the tile kernels form max(t, slope*t): LeakyReLU / ReLU / none)
 
 
 def pop_bn_link():
@@ -401,27 +397,6 @@ def link_of(x):
 _bn_rows_cache = {}
 
 
-def conv_dgrad_bn_raw(dy, w, spec: ConvSpec, in_hw, link: BNLink):
-    """dgrad + fused BatchNorm-backward sums of the layer that produced this layer's input; None if not fusable."""
-    B = dy.shape[0]
-    H, W = in_hw
-    ws = native.workspace(dy.device)
-    key = (spec.kind, B, H, W, spec.ci, spec.co, spec.k, spec.stride, spec.pad, spec.out_pad, ws.numel())
-    rows = _bn_rows_cache.get(key)
-    if rows is None:
-        rows = _bn_rows_cache[key] = native.load().ctvae_conv_dgrad_bn_rows(*key[:-1], ws.numel() * 4)
-    if rows <= 0 or tuple(link.y.shape) != (B, H, W, spec.ci):
-        return None
-    dx = torch.empty((B, H, W, spec.ci), dtype=torch.float32, device=dy.device)
-    part = torch.empty(rows * spec.ci * 2, dtype=torch.float32, device=dy.device)
-    native.call("ctvae_conv_dgrad_bn", spec.kind, dy.data_ptr(), w.data_ptr(), None, None, ACT_NONE, dx.data_ptr(),
-                B, H, W, spec.ci, spec.co, spec.k, spec.stride, spec.pad, spec.out_pad, link.y.data_ptr(),
-                link.mean.data_ptr(), link.invstd.data_ptr(), link.gamma.data_ptr(), link.beta.data_ptr(), link.act,
-                part.data_ptr(), rows, ws.data_ptr(), ws.numel() * 4)
-    link.publish(dx, part, rows)
-    return dx
-
-
 def conv_wgrad_raw(x, dy, w_param, b_param, spec: ConvSpec, in_coef=None, in_act=ACT_NONE, dy_bn=None, bn_commit=None):
     """dy_bn = (y, coef[5][Co], act, gy_out): dy is g_a of the BatchNorm behind this layer; g_y is formed on load and
     written to gy_out (ctvae_conv_wgrad dy_bn_*).  gy_out None + bn_commit = (dgamma, dbeta, accumulate): the layer with no
@@ -447,17 +422,7 @@ def conv_wgrad_raw(x, dy, w_param, b_param, spec: ConvSpec, in_coef=None, in_act
                 by, bc, bact, bgy, cg, cb, cacc, ws.data_ptr(), ws.numel() * 4)
 
 
-_PAIR = os.environ.get("CTVAE_NO_PAIR", "0") != "1"     # diagnostic: separate wgrad / dgrad launches
-_BN_RIDER = os.environ.get("CTVAE_NO_BN_RIDER", "0") != "1"   # diagnostic: BatchNorm-backward finalize as its own launch
-_OUT_ACT_LINK = os.environ.get("CTVAE_NO_OUT_ACT_LINK", "0") != "1"   # diagnostic: final Tanh backward as its own launch
-# diagnostic, default off (0 = the finalize always rides in the consumer's finishing launch): with 128 the three deepest BatchNorm
-# layers finalize in their own apply launch and their consumers' slab reductions leave the chain -- 1.5992 / 1.5986 ms against
-# 1.5996 / 1.5988 ms (VanillaVAE bs = 256, same box): neutral, the one deferred launch grows by what the three removed ones took
-_BN_BWD_MERGE_ROWS = int(os.environ.get("CTVAE_BN_BWD_MERGE_ROWS", "0"))
-_GRAD_SLICES = os.environ.get("CTVAE_NO_GRAD_SLICES", "0") != "1"   # diagnostic: every split-K result is summed by its own finish launch
-_LAZY_BN = os.environ.get("CTVAE_NO_LAZY_BN_APPLY", "0") != "1"   # diagnostic: every BatchNorm + activation output is materialised
-_BN_LAZY = os.environ.get("CTVAE_NO_BN_LAZY", "0") != "1"     # diagnostic: small layers' data gradients summed by splitk_finish as before
-_ENC_BN_ON_LOAD = os.environ.get("CTVAE_NO_ENC_BN_ON_LOAD", "0") != "1"   # diagnostic: encoder.0's BatchNorm-backward apply as its own launch
+_PAIR = True     # a layer's weight and data gradients share one call (ctvae_conv_backward); tests read the plan it implies
 
 
 def conv_backward_raw(x, dy, w_param, b_param, spec: ConvSpec, link=None, mask=None, mask_act=ACT_NONE, wino_filters=None,
@@ -482,7 +447,7 @@ def conv_backward_raw(x, dy, w_param, b_param, spec: ConvSpec, link=None, mask=N
             acc = 1
     dx = torch.empty((B, H, W, spec.ci), dtype=torch.float32, device=dy.device)
     part, rows = None, 0
-    if (link is not None and link.sole and _BN_LAZY and tuple(link.y.shape) == (B, H, W, spec.ci) and mask is None and wino_filters is None
+    if (link is not None and link.sole and tuple(link.y.shape) == (B, H, W, spec.ci) and mask is None and wino_filters is None
             and dy_bn is None and bn_commit is None):
         key = (spec.kind, B, H, W, spec.ci, spec.co, spec.k, spec.stride, spec.pad, spec.out_pad, ws.numel(), "lazy")
         n = _bn_rows_cache.get(key)
@@ -497,8 +462,7 @@ def conv_backward_raw(x, dy, w_param, b_param, spec: ConvSpec, link=None, mask=N
                         in_coef.data_ptr() + 4 * spec.ci if in_coef is not None else None, in_act, 0, ws.data_ptr(), ws.numel() * 4)
             link.publish_lazy(dx, slices, n, key[:10])
             return dx
-    if (grad_slices and _GRAD_SLICES and link is None and mask is None and wino_filters is None and dy_bn is None
-            and bn_commit is None):
+    if grad_slices and link is None and mask is None and wino_filters is None and dy_bn is None and bn_commit is None:
         key = (spec.kind, B, H, W, spec.ci, spec.co, spec.k, spec.stride, spec.pad, spec.out_pad, ws.numel(), "slices")
         n = _bn_rows_cache.get(key)
         if n is None:
@@ -522,10 +486,7 @@ def conv_backward_raw(x, dy, w_param, b_param, spec: ConvSpec, link=None, mask=N
         else:
             rows = 0
     bn = link if part is not None else None
-    # few rows of sums (the deep layers): the BatchNorm's own launch finalizes AND applies (bn_bwd_finalize_apply_kernel), so this
-    # call's finishing launch carries no finalize and its slab reduction can leave the chain (kernels.backward's deferral)
-    rider = bn is not None and _BN_RIDER and not (0 < rows <= _BN_BWD_MERGE_ROWS and spec.ci % 32 == 0 and bn_commit is None)
-    coef = torch.empty(7 * spec.ci, dtype=torch.float32, device=dy.device) if rider else None
+    coef = torch.empty(7 * spec.ci, dtype=torch.float32, device=dy.device) if bn is not None else None   # the finalize rides along
     sc = in_coef.data_ptr() if in_coef is not None else None
     sh = in_coef.data_ptr() + 4 * spec.ci if in_coef is not None else None
     by, bc, bact, bgy = (dy_bn[0].data_ptr(), dy_bn[1].data_ptr(), dy_bn[2], dy_bn[3].data_ptr()) if dy_bn is not None else (None, None, 0, None)
@@ -550,17 +511,11 @@ def wgrad_then_dgrad(x, g, w_param, b_param, spec, need_dgrad, link=None, wino_f
     end of backward) is SLOWER than back-to-back launches (2.43 vs 2.32 ms/step) -- each GEMM launch already covers
     every CU, and the fork/join edges cost more than the overlap of prologue/epilogue phases returns.  What does pay is
     ONE launch for both GEMMs (ctvae_conv_backward / conv_bwd_pair_kernel)."""
-    if need_dgrad and _PAIR:
+    if need_dgrad:
         return conv_backward_raw(x, g, w_param, b_param, spec, link=link, wino_filters=wino_filters, in_coef=in_coef, in_act=in_act,
                                  grad_slices=grad_slices)
     conv_wgrad_raw(x, g, w_param, b_param, spec, in_coef=in_coef, in_act=in_act)
-    if not need_dgrad:
-        return None
-    if link is not None:
-        dx = conv_dgrad_bn_raw(g, w_param, spec, (x.shape[1], x.shape[2]), link)
-        if dx is not None:
-            return dx
-    return conv_dgrad_raw(g, w_param, spec, (x.shape[1], x.shape[2]), wino_filters=wino_filters)
+    return None
 
 
 def act_backward_raw(g_out, out, act):
@@ -608,12 +563,9 @@ class LinearToNHWC(Function):
     the consumer's split-K slices on the way when it arrives as slices), then the Linear's paired backward launch."""
 
     _ok = {}
-    _on = os.environ.get("CTVAE_LINEAR_NHWC", "1") != "0"     # diagnostic: 0 = the two-launch path
 
     @staticmethod
     def supported(B, ci, C, P, device):
-        if not LinearToNHWC._on:
-            return False
         key = (B, ci, C, P)
         ok = LinearToNHWC._ok.get(key)
         if ok is None:
@@ -800,7 +752,7 @@ class ConvAct(Function):
         _req_cuda(x, w)
         ctx.link_in = link_of(x)
         ctx.x_slices_ok = bool(getattr(x, "_ctvae_grad_slices_ok", False))
-        if lazy_slices and _GRAD_SLICES and aux is None and add is None and spec.act == ACT_NONE and x.is_contiguous():
+        if lazy_slices and aux is None and add is None and spec.act == ACT_NONE and x.is_contiguous():
             B, H, W_, _ = x.shape
             ws = native.workspace(x.device)
             key = (spec.kind, B, H, W_, spec.ci, spec.co, spec.k, spec.stride, spec.pad, spec.out_pad, ws.numel(), "fwd-slices")
@@ -864,11 +816,7 @@ class ConvAct(Function):
             g_pre = act_backward_raw(g_y, y, spec.act)
         if ctx.act_in is not None and ctx.needs_input_grad[0] and ctx.link_in is None:
             # x is the activated output of the producer and this layer is its only consumer: dgrad * act'(x) in one launch
-            if _PAIR:
-                g_x = conv_backward_raw(x, g_pre, ctx.w, ctx.b, spec, mask=x, mask_act=ctx.act_in.act)
-            else:
-                conv_wgrad_raw(x, g_pre, ctx.w, ctx.b, spec)
-                g_x = conv_dgrad_raw(g_pre, ctx.w, spec, (x.shape[1], x.shape[2]), mask=x, mask_act=ctx.act_in.act)
+            g_x = conv_backward_raw(x, g_pre, ctx.w, ctx.b, spec, mask=x, mask_act=ctx.act_in.act)
             ctx.act_in.publish_done(g_x)
         else:
             g_x = wgrad_then_dgrad(x, g_pre, ctx.w, ctx.b, spec, ctx.needs_input_grad[0], ctx.link_in, ctx.wino_u,
@@ -921,11 +869,7 @@ class ResBlock(Function):
         x, h, out = ctx.saved_tensors
         g_out = _c(g_out)
         g_pre = act_backward_raw(g_out, out, spec1.act) if spec1.act != ACT_NONE else g_out
-        if _PAIR:
-            g_h = conv_backward_raw(h, g_pre, w1, None, spec1, mask=h, mask_act=spec3.act)
-        else:
-            conv_wgrad_raw(h, g_pre, w1, None, spec1)
-            g_h = conv_dgrad_raw(g_pre, w1, spec1, (h.shape[1], h.shape[2]), mask=h, mask_act=spec3.act)
+        g_h = conv_backward_raw(h, g_pre, w1, None, spec1, mask=h, mask_act=spec3.act)
         conv_wgrad_raw(x, g_h, w3, None, spec3)
         g_x = None
         if ctx.needs_input_grad[0]:
@@ -1005,7 +949,7 @@ class ConvBNAct(Function):
         part, rows, coef = ctx.link_out.take(g_a) if ctx.link_out is not None else (None, 0, None)
         if coef is not None:
             part, rows = None, 0         # finalized by the consumer's finishing launch: apply + commit only
-            if not ctx.needs_input_grad[0] and _ENC_BN_ON_LOAD and wgrad_bn_apply_mode(spec, x.shape[0], x.shape[1], x.shape[2]) == 2:
+            if not ctx.needs_input_grad[0] and wgrad_bn_apply_mode(spec, x.shape[0], x.shape[1], x.shape[2]) == 2:
                 # the first layer of the encoder: no data gradient follows, so g_y is only the weight gradient's operand -- formed
                 # on load from (g_a, y, coef); the apply launch and its 33 MB output are not needed
                 conv_wgrad_raw(x, g_a, w, b, spec, dy_bn=(y, coef, ctx.bn_act, None), bn_commit=(gg, gbt, accg))
@@ -1080,7 +1024,7 @@ class ConvBNActConvAct(Function):
                     lazy_in[0].data_ptr() + 4 * spec1.ci if lazy_in is not None else None,
                     lazy_in[1] if lazy_in is not None else ACT_NONE, ws.data_ptr(), ws.numel() * 4)
         r = conv_forward_raw(y1, w2, b2, spec2, in_coef=coef, in_act=bn_act)
-        ctx.act_out = offer_out_act_link(r, spec2.act) if (training and spec2.act != ACT_NONE and _OUT_ACT_LINK) else None
+        ctx.act_out = offer_out_act_link(r, spec2.act) if (training and spec2.act != ACT_NONE) else None
         ctx.specs, ctx.bn_act, ctx.training = (spec1, spec2), bn_act, training
         ctx.params = (w1, b1, gamma, beta, w2, b2)
         ctx.save_for_backward(x, y1, r, coef, save_mean, save_invstd)
@@ -1108,22 +1052,14 @@ class ConvBNActConvAct(Function):
             accg = 1
         lazy = wgrad_bn_apply_supported(spec1, x.shape[0], x.shape[1], x.shape[2])
         g_y = torch.empty_like(y1)
-        one_call = ran = _PAIR and _BN_RIDER
-        if one_call:
-            # conv2's weight gradient, its data gradient (which emits the BatchNorm's backward sums) and the BatchNorm's
-            # finalize in one call: the finalize rides in the slab-reduction launch (the link is local to this node, so the
-            # rider commits d gamma / d beta itself when no apply launch follows)
-            g_a = conv_backward_raw(y1, g_pre, w2, b2, spec2, link=link, in_coef=coef, in_act=ctx.bn_act,
-                                    bn_commit=(gg, gbt, accg) if lazy else None)
-            part, rows, c7 = link.take(g_a)
-            one_call = c7 is not None
-        if not one_call:
-            if not ran:
-                conv_wgrad_raw(y1, g_pre, w2, b2, spec2, in_coef=coef, in_act=ctx.bn_act)
-                g_a = conv_dgrad_bn_raw(g_pre, w2, spec2, (H, W), link)
-                if g_a is None:
-                    g_a = conv_dgrad_raw(g_pre, w2, spec2, (H, W))
-                part, rows, _ = link.take(g_a)
+        # conv2's weight gradient, its data gradient (which emits the BatchNorm's backward sums) and the BatchNorm's
+        # finalize in one call: the finalize rides in the slab-reduction launch (the link is local to this node, so the
+        # rider commits d gamma / d beta itself when no apply launch follows)
+        g_a = conv_backward_raw(y1, g_pre, w2, b2, spec2, link=link, in_coef=coef, in_act=ctx.bn_act,
+                                bn_commit=(gg, gbt, accg) if lazy else None)
+        part, rows, c7 = link.take(g_a)
+        if c7 is None:
+            # the rider declined (no sums from the data gradient): the BatchNorm's own launch finalizes
             bcoef = torch.empty(5 * C, dtype=torch.float32, device=x.device) if lazy else None
             native.call("ctvae_bn_backward", g_a.data_ptr(), beta.data_ptr(), y1.data_ptr(), B * H * W, C, gamma.data_ptr(),
                         save_mean.data_ptr(), save_invstd.data_ptr(), ctx.bn_act, None if lazy else g_y.data_ptr(), gg.data_ptr(),
@@ -1137,16 +1073,12 @@ class ConvBNActConvAct(Function):
         in_coef, in_act = (ctx.lazy_in[0], ctx.lazy_in[1]) if ctx.lazy_in is not None else (None, ACT_NONE)
         if lazy:
             # the weight-gradient kernel turns g_a into g_y on load and leaves g_y behind for the data gradient
-            if ctx.needs_input_grad[0] and _PAIR:
+            if ctx.needs_input_grad[0]:
                 g_x = conv_backward_raw(x, g_a, w1, b1, spec1, link=ctx.link_in, dy_bn=(y1, bcoef, ctx.bn_act, g_y),
                                         in_coef=in_coef, in_act=in_act)
             else:
                 conv_wgrad_raw(x, g_a, w1, b1, spec1, dy_bn=(y1, bcoef, ctx.bn_act, g_y), in_coef=in_coef, in_act=in_act)
                 g_x = None
-                if ctx.needs_input_grad[0]:
-                    g_x = None if ctx.link_in is None else conv_dgrad_bn_raw(g_y, w1, spec1, (x.shape[1], x.shape[2]), ctx.link_in)
-                    if g_x is None:
-                        g_x = conv_dgrad_raw(g_y, w1, spec1, (x.shape[1], x.shape[2]))
         else:
             g_x = wgrad_then_dgrad(x, g_y, w1, b1, spec1, ctx.needs_input_grad[0], ctx.link_in, in_coef=in_coef, in_act=in_act)
         return (g_x,) + (None,) * 13
@@ -1322,7 +1254,7 @@ class VAELoss(Function):
             native.call("ctvae_logcosh_loss_forward", recons.data_ptr(), x.data_ptr(), recons.numel(), float(logcosh_alpha),
                         native.ptr(mu_), mrs, native.ptr(lv_), lrs, B, L, float(M_N), out.data_ptr(), ws.data_ptr(), ws.numel() * 4)
         else:
-            if (_LOSS_GRAD_IN_FWD and mu is not None and ctx.needs_input_grad[0] and ctx.needs_input_grad[2] and ctx.needs_input_grad[3]):
+            if mu is not None and ctx.needs_input_grad[0] and ctx.needs_input_grad[2] and ctx.needs_input_grad[3]:
                 # the gradients for a unit upstream gradient come out of the same pass (ctvae_loss_forward_grad); backward hands
                 # them over as they are when the loss is the root of the pass (kernels.backward), else it runs its own kernel
                 ctx.act_link = claim_out_act_link(recons)
@@ -1773,7 +1705,6 @@ class DIPLoss(Function):
 
 
 _ones = {}
-_LOSS_GRAD_IN_FWD = os.environ.get("CTVAE_NO_LOSS_GRAD_IN_FWD", "0") != "1"   # diagnostic: the loss gradient always from its own launch
 
 
 def _is_cached_root(g):
@@ -1810,8 +1741,8 @@ class capture_graph:
                 gc.enable()
 
 
-_DEFER_REDUCE = os.environ.get("CTVAE_NO_DEFER_REDUCE", "0") != "1"   # diagnostic: every slab reduction in the backward chain
-_DEFER_ARENA_BYTES = int(os.environ.get("CTVAE_DEFER_ARENA_MB", "2048")) << 20
+_DEFER_REDUCE = True     # kernels.backward defers the slab reductions to one launch (False: plain loss.backward(); tests assert it is on)
+_DEFER_ARENA_BYTES = 2048 << 20     # slab arena of the deferred weight-gradient reductions: 2 GB of the 288
 _defer_arena = {}
 
 
@@ -1931,7 +1862,6 @@ def banked(params) -> bool:
 
 _flat_buffers = []     # [(weakref(flat parameter buffer), weakref(flat gradient buffer))] of the live FlatParamMixin models
 _alias_given = {}
-_GRAD_ALIAS = os.environ.get("CTVAE_NO_GRAD_ALIAS", "0") != "1"   # diagnostic: bank gradients in tensors of their own, copied by gather
 
 
 def register_flat_buffers(flat, gflat):
@@ -1960,7 +1890,7 @@ def flat_grad_alias(t):
     of it as the parameters' .grad and gather_torch_grads() has nothing to copy (CT-MCQ-VAE: two multi-tensor copies of 21 and
     18 us per step).  Only in the epoch a zero_grad opened, and once per range: a second writer gets None and a tensor of its
     own, which autograd adds to the first."""
-    if not _GRAD_ALIAS or t is None or not t.is_contiguous() or _alias_epoch[0] != _param_epoch[0]:
+    if t is None or not t.is_contiguous() or _alias_epoch[0] != _param_epoch[0]:
         return None
     for fr, gr in _flat_buffers:
         f, g = fr(), gr()

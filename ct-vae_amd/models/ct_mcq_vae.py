@@ -5,7 +5,6 @@ a textual copy of mcq_vae.py:161-239); the causal-transition layer between index
 lookup is ``causal.CausalTransition`` (torch-level + HIP Gumbel kernel; parity unpinned, see its header).
 Modes, return lists, loss-dict keys and ``state_dict`` keys follow the reference.
 """
-import os
 from typing import List, Union
 
 import torch
@@ -18,7 +17,7 @@ from .causal import CausalTransition
 from .mcq_vae import MultipleCodebookVectorQuantizer, build_mcq_decoder, build_mcq_encoder
 from .types_ import Tensor
 
-_PAIR_ENCODE = os.environ.get("CTVAE_NO_PAIR_ENCODE", "0") != "1"    # diagnostic: x and y through separate encoder passes
+_PAIR_ENCODE = True    # x and y through one encoder pass (tests set False for the two-pass reference)
 
 
 class CTMCQVAE(BaseVAE):

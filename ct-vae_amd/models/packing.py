@@ -284,7 +284,7 @@ class FlatParamMixin:
         _K.bump_param_epoch()          # a new step: transformed Winograd filters are remade once for all layers (kernels.wino_cache)
         if getattr(self, "_flat_grads", None) is not None:
             prezeroed = False
-            if lazy and _K.LAZY_ZERO_GRAD:
+            if lazy:
                 for blk in self._grad_blocks:
                     blk.fresh = True
                 self._lazy_zero = True

@@ -573,8 +573,8 @@ int ctvae_crop_resize_u8(const uint8_t* images, const int64_t* rows, float* out,
 
 /* 3x3 / stride-1 / pad-1 layers with at least 64 channels run Winograd F(2x2,3x3) (forward, data gradient) and
  * F(3x3,2x2) (weight and bias gradient) instead of the direct tap-GEMM (csrc/wino.hip): 2.25x fewer MFMA
- * operations, results within a few 1e-6 of the direct kernels.  This switch (default on; environment
- * CTVAE_NO_WINOGRAD=1 turns it off) selects the direct kernels for A/B parity checks.  Returns the previous setting. */
+ * operations, results within a few 1e-6 of the direct kernels.  This switch (default on) selects the direct kernels
+ * for A/B parity checks.  Returns the previous setting. */
 int ctvae_winograd_enable(int on);
 
 /* Measurement aid (bench.py roofline leg): when enabled every launcher brackets its kernels with HIP events
