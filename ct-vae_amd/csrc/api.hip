@@ -123,6 +123,9 @@ int launch_reparam_bwd(const float* gz, const float* lv, long lv_rs, const float
                        hipStream_t st);
 int launch_adam(float* p, const float* g, float* m, float* v, float* state, long n, float grad_scale, hipStream_t st);
 size_t adam_state_floats();
+int launch_adam_clipped(float* p, const float* g, float* m, float* v, float* state, long n, float grad_scale, int algorithm,
+                        float clip, float* ws, float* norm_out, hipStream_t st);
+size_t grad_clip_workspace_floats();
 int launch_ssim_forward(const float* a, const float* b, const float* window, float* part, float* loss, float* coef, int B, int C, int H,
                         int W, const float* weights, hipStream_t st);
 int launch_ssim_backward(const float* a, const float* b, const float* window, const float* coef, const float* g_loss, float* g_a, int B,
@@ -1042,6 +1045,17 @@ int ctvae_adam_step(float* params, const float* grads, float* exp_avg, float* ex
                     float grad_scale, void* stream) {
   if (!params || !grads || !exp_avg || !exp_avg_sq || !state || n <= 0) return kErrBadArg;
   return launch_adam(params, grads, exp_avg, exp_avg_sq, state, n, grad_scale, (hipStream_t)stream);
+}
+
+size_t ctvae_grad_clip_workspace_floats(void) { return grad_clip_workspace_floats(); }
+
+int ctvae_adam_step_clipped(float* params, const float* grads, float* exp_avg, float* exp_avg_sq, float* state, long n,
+                            float grad_scale, int algorithm, float clip_val, float* workspace, float* norm_out, void* stream) {
+  if (!params || !grads || !exp_avg || !exp_avg_sq || !state || n <= 0 || !(clip_val > 0.f)) return kErrBadArg;
+  if (algorithm != CTVAE_CLIP_NORM && algorithm != CTVAE_CLIP_VALUE) return kErrBadArg;
+  if (algorithm == CTVAE_CLIP_NORM && !workspace) return kErrBadArg;
+  return launch_adam_clipped(params, grads, exp_avg, exp_avg_sq, state, n, grad_scale, algorithm, clip_val, workspace, norm_out,
+                             (hipStream_t)stream);
 }
 
 }  // extern "C"

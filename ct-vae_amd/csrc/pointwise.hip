@@ -281,6 +281,152 @@ __global__ __launch_bounds__(256) void adam_kernel(float* __restrict__ p, const 
   }
 }
 
+// ---- gradient clipping in front of the Adam step -------------------------------------------------------
+// torch.nn.utils.clip_grad_norm_(max_norm = clip, norm_type = 2) / clip_grad_value_(clip) on the DDP-averaged gradient
+// g * grad_scale, then Adam on the clipped gradient (weight decay added after the clip, as torch.optim.Adam does).
+// Norm mode is two launches: grad_sqnorm_kernel writes one fp32 partial of sum (g * grad_scale)^2 per workgroup, and every
+// workgroup of adam_clip_kernel merges those partials itself, from L2: the kernel boundary makes them visible, no in-launch
+// hand-over.  The grid, the elements each thread adds, their order and the reduction tree depend on n only -- the 16-byte
+// and the scalar variant add the same elements in the same order -- so the norm is bit-reproducible run to run, between
+// eager and graph replay and across DDP ranks holding the same all-reduced gradient.  Value mode is adam_clip_kernel alone.
+constexpr int kClipMaxWgs = 1024, kClipNorm = 0, kClipValue = 1;
+
+// Sum over the 256 threads of a workgroup, the same in every thread: xor butterfly per wave, then the four wave sums in a
+// fixed order.  lds: 4 floats.
+__device__ inline float block_sum256(float v, float* lds) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+  if ((threadIdx.x & 63) == 0) lds[threadIdx.x >> 6] = v;
+  __syncthreads();
+  return (lds[0] + lds[1]) + (lds[2] + lds[3]);
+}
+
+// Thread t of workgroup b adds the quads b*256 + t + k*gridDim.x*256 (k = 0, 1, ...) element by element, then the n % 4
+// trailing elements go to the first threads of workgroup 0.
+template <bool VEC>
+__global__ __launch_bounds__(256) void grad_sqnorm_kernel(const float* __restrict__ g, long n, float grad_scale,
+                                                          float* __restrict__ partial) {
+  __shared__ float lds[4];
+  const long nq = n / 4, stride = (long)gridDim.x * 256, t = (long)blockIdx.x * 256 + threadIdx.x;
+  auto quad = [&](long q) -> f32x4 {
+    if constexpr (VEC) return reinterpret_cast<const f32x4*>(g)[q];
+    else return f32x4{g[4 * q], g[4 * q + 1], g[4 * q + 2], g[4 * q + 3]};
+  };
+  float acc = 0.f;
+  for (long i = t; i < nq; i += 2 * stride) {   // two quads in flight per thread
+    const long i2 = i + stride;
+    const f32x4 a = quad(i);
+    const f32x4 b = i2 < nq ? quad(i2) : f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+      const float x = a[q] * grad_scale;
+      acc = fmaf(x, x, acc);
+    }
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+      const float x = b[q] * grad_scale;
+      acc = fmaf(x, x, acc);
+    }
+  }
+  if (t < n - 4 * nq) {
+    const float x = g[4 * nq + t] * grad_scale;
+    acc = fmaf(x, x, acc);
+  }
+  const float s = block_sum256(acc, lds);
+  if (threadIdx.x == 0) partial[blockIdx.x] = s;
+}
+
+// adam_kernel with the clip folded in.  Norm mode: c = clip / (||g * grad_scale|| + 1e-6) clamped to 1 the way torch forms
+// it (reciprocal times max_norm; a NaN norm gives c = NaN, an infinite one c = 0), every gradient is multiplied by c, also
+// when c == 1.  Value mode: clamp(g * grad_scale, -clip, clip), NaN stays NaN.  With grad_scale == 1 and c == 1 the update
+// is bit-identical to adam_kernel's.  Workgroup 0 writes the pre-clip norm to norm_out (when not NULL).
+template <bool VEC, int MODE>
+__global__ __launch_bounds__(256) void adam_clip_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
+                                                        float* __restrict__ v, float* state, long n, float grad_scale,
+                                                        float clip, const float* partial, int nparts, float* norm_out) {
+  const float lr = state[1], b1 = state[2], b2 = state[3], eps = state[4], wd = state[5];
+  const float b1t = state[6] * b1, b2t = state[7] * b2;
+  const float bc1 = 1.f - b1t, bc2 = 1.f - b2t;
+  const float step_size = lr / bc1, bc2s = sqrtf(bc2);
+  float c = 1.f;
+  if constexpr (MODE == kClipNorm) {
+    __shared__ float lds[4];
+    float s = 0.f;
+    for (int k = threadIdx.x; k < nparts; k += 256) s += partial[k];
+    const float total = sqrtf(block_sum256(s, lds));
+    c = (1.f / (total + 1e-6f)) * clip;
+    c = c > 1.f ? 1.f : c;                     // not fminf: a NaN coefficient must stay NaN
+    if (norm_out != nullptr && blockIdx.x == 0 && threadIdx.x == 0) *norm_out = total;
+  }
+  const long stride = (long)gridDim.x * 256;
+  // In norm mode the weight decay joins the clipped gradient with the roundings adam_kernel's `gi * grad_scale + wd * pi`
+  // compiles to -- fma(g, grad_scale, wd * p) in its 16-byte loop, fma(wd, p, g * grad_scale) in its scalar loops -- so that
+  // c == 1 with grad_scale == 1 reproduces its update bit for bit on every path.
+  auto upd = [&](float& pi, float gi, float& mi, float& vi, bool quad) {
+    if constexpr (MODE == kClipNorm) {
+      gi = quad ? fmaf(gi * grad_scale, c, wd * pi) : fmaf(wd, pi, (gi * grad_scale) * c);
+    } else {
+      gi = gi * grad_scale;
+      gi = gi < -clip ? -clip : (gi > clip ? clip : gi);   // comparisons, not fminf / fmaxf: NaN stays NaN
+      gi = fmaf(wd, pi, gi);
+    }
+    mi = b1 * mi + (1.f - b1) * gi;
+    vi = b2 * vi + (1.f - b2) * gi * gi;
+    pi = pi - step_size * (mi / (sqrtf(vi) / bc2s + eps));
+  };
+  const long n4 = VEC ? n / 4 : 0;
+  if constexpr (VEC) {
+    f32x4* p4 = reinterpret_cast<f32x4*>(p);
+    const f32x4* g4 = reinterpret_cast<const f32x4*>(g);
+    f32x4* m4 = reinterpret_cast<f32x4*>(m);
+    f32x4* v4 = reinterpret_cast<f32x4*>(v);
+    for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n4; i += 2 * stride) {
+      const long i2 = i + stride;
+      const bool two = i2 < n4;
+      f32x4 pa = p4[i], ga = g4[i], ma = m4[i], va = v4[i];
+      f32x4 pb = two ? p4[i2] : pa, gb = two ? g4[i2] : ga, mb = two ? m4[i2] : ma, vb = two ? v4[i2] : va;
+#pragma unroll
+      for (int q = 0; q < 4; ++q) {
+        float pq = pa[q], mq = ma[q], vq = va[q];
+        upd(pq, ga[q], mq, vq, true);
+        pa[q] = pq; ma[q] = mq; va[q] = vq;
+      }
+      m4[i] = ma; v4[i] = va; p4[i] = pa;
+      if (two) {
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+          float pq = pb[q], mq = mb[q], vq = vb[q];
+          upd(pq, gb[q], mq, vq, true);
+          pb[q] = pq; mb[q] = mq; vb[q] = vq;
+        }
+        m4[i2] = mb; v4[i2] = vb; p4[i2] = pb;
+      }
+    }
+  }
+  for (long i = n4 * 4 + (long)blockIdx.x * 256 + threadIdx.x; i < n; i += stride) {
+    float pi = p[i], mi = m[i], vi = v[i];
+    upd(pi, g[i], mi, vi, false);
+    m[i] = mi;
+    v[i] = vi;
+    p[i] = pi;
+  }
+  __syncthreads();   // every thread of this workgroup holds its copy of the state
+  if (threadIdx.x == 0) {   // adam_kernel's two-level ticket: the last workgroup advances the step counter
+    unsigned* tk = reinterpret_cast<unsigned*>(state + kAdamTicketOffset);
+    const unsigned grp = blockIdx.x >> 5, ngrp = (gridDim.x + 31) >> 5;
+    const unsigned gsize = gridDim.x - grp * 32 < 32 ? gridDim.x - grp * 32 : 32;
+    if (atomicAdd(tk + 16 * (1 + grp), 1u) == gsize - 1) {
+      atomicExch(tk + 16 * (1 + grp), 0u);
+      if (atomicAdd(tk, 1u) == ngrp - 1) {
+        atomicExch(tk, 0u);
+        state[0] += 1.f;
+        state[6] = b1t;
+        state[7] = b2t;
+      }
+    }
+  }
+}
+
 // Straight-through Bernoulli sample through a 2-class Gumbel-softmax (tau = 1, hard) of
 // log(clamp([1-p, p], 1e-4)) (ct_mcq_vae.py:126,177-183).  noise = 2 standard Gumbel draws/element.
 __global__ __launch_bounds__(256) void gumbel_st_fwd_kernel(const float* __restrict__ p, const float* __restrict__ noise,
@@ -377,6 +523,40 @@ int launch_adam(float* p, const float* g, float* m, float* v, float* state, long
                      reinterpret_cast<uintptr_t>(v)) % 16) == 0;
   if (vec) hipLaunchKernelGGL(adam_kernel<true>, dim3(grid_for(n / 4, wgs)), dim3(256), 0, st, p, g, m, v, state, n, grad_scale);
   else hipLaunchKernelGGL(adam_kernel<false>, dim3(grid_for(n, wgs)), dim3(256), 0, st, p, g, m, v, state, n, grad_scale);
+  CTVAE_LAUNCH_CHECK();
+  return 0;
+}
+
+size_t grad_clip_workspace_floats() { return kClipMaxWgs; }
+
+int launch_adam_clipped(float* p, const float* g, float* m, float* v, float* state, long n, float grad_scale, int algorithm,
+                        float clip, float* ws, float* norm_out, hipStream_t st) {
+  constexpr int wgs = 1024;
+  static_assert(wgs <= kAdamMaxWgs, "the Adam state is sized for kAdamMaxWgs workgroups");
+  const bool vec = ((reinterpret_cast<uintptr_t>(p) | reinterpret_cast<uintptr_t>(g) | reinterpret_cast<uintptr_t>(m) |
+                     reinterpret_cast<uintptr_t>(v)) % 16) == 0;
+  const dim3 grid(vec ? grid_for(n / 4, wgs) : grid_for(n, wgs));
+  int nparts = 0;
+  if (algorithm == kClipNorm) {
+    nparts = (int)grid_for(n / 4, kClipMaxWgs);     // a function of n alone: the reduction order does not follow alignment
+    ProfScope ps("grad_sqnorm_kernel", st, 0.0, 4.0 * (double)n + 4.0 * nparts);
+    if (reinterpret_cast<uintptr_t>(g) % 16 == 0)
+      hipLaunchKernelGGL(grad_sqnorm_kernel<true>, dim3(nparts), dim3(256), 0, st, g, n, grad_scale, ws);
+    else hipLaunchKernelGGL(grad_sqnorm_kernel<false>, dim3(nparts), dim3(256), 0, st, g, n, grad_scale, ws);
+    CTVAE_LAUNCH_CHECK();
+  }
+  ProfScope ps("adam_clip_kernel", st, 0.0, 28.0 * (double)n + 4.0 * nparts);
+  if (algorithm == kClipNorm) {
+    if (vec) hipLaunchKernelGGL((adam_clip_kernel<true, kClipNorm>), grid, dim3(256), 0, st, p, g, m, v, state, n, grad_scale, clip,
+                                ws, nparts, norm_out);
+    else hipLaunchKernelGGL((adam_clip_kernel<false, kClipNorm>), grid, dim3(256), 0, st, p, g, m, v, state, n, grad_scale, clip,
+                            ws, nparts, norm_out);
+  } else {
+    if (vec) hipLaunchKernelGGL((adam_clip_kernel<true, kClipValue>), grid, dim3(256), 0, st, p, g, m, v, state, n, grad_scale,
+                                clip, nullptr, 0, nullptr);
+    else hipLaunchKernelGGL((adam_clip_kernel<false, kClipValue>), grid, dim3(256), 0, st, p, g, m, v, state, n, grad_scale,
+                            clip, nullptr, 0, nullptr);
+  }
   CTVAE_LAUNCH_CHECK();
   return 0;
 }

@@ -3,7 +3,8 @@
 ``VAEXperiment`` keeps the reference's step semantics: batch unpacking ``(real_img, labels, *options)``,
 ``model(real_img, labels=..., **options)``, ``loss_function(*results, M_N=kld_weight)`` for training and
 ``M_N=1.0`` with a ``val_`` key prefix for validation, Adam(lr=LR, weight_decay) + ExponentialLR(gamma)
-over ``model.parameters()`` or ``getattr(model, update_parameters).parameters()``.  What changes is the
+over ``model.parameters()`` or ``getattr(model, update_parameters).parameters()``, with the Trainer's gradient clipping
+(``gradient_clip_val`` / ``gradient_clip_algorithm``, see optim.py) in front of the step.  What changes is the
 machinery: one flat fused Adam launch, one bucketed RCCL all-reduce, and scalars fetched with ONE device
 -> host copy every ``log_every`` steps instead of one ``.item()`` sync per key per step (experiment.py:95-96).
 """
@@ -15,7 +16,7 @@ import torch
 
 from . import kernels as K
 from .ddp import GradBucketAllReduce
-from .optim import ExponentialLR, FlatAdam
+from .optim import ExponentialLR, FlatAdam, clip_settings
 
 
 def _graph_key(real_img, kwargs):
@@ -102,7 +103,9 @@ class _GraphedTrainStep:
 
 class VAEXperiment:
 
-    def __init__(self, vae_model, params: dict, ddp: GradBucketAllReduce = None, log_every: int = 50, log_file=None):
+    def __init__(self, vae_model, params: dict, ddp: GradBucketAllReduce = None, log_every: int = 50, log_file=None,
+                 gradient_clip_val=None, gradient_clip_algorithm=None):
+        self.gradient_clip_val, self.gradient_clip_algorithm = clip_settings(gradient_clip_val, gradient_clip_algorithm)
         self.model = vae_model
         self.params = params
         self.ddp = ddp
@@ -170,7 +173,8 @@ class VAEXperiment:
         sl = None
         if "update_parameters" in self.params:
             sl = self.model.flat_range(self.params["update_parameters"])
-        opt = FlatAdam(self.model, lr=self.params['LR'], weight_decay=self.params.get('weight_decay', 0.0), params_slice=sl)
+        opt = FlatAdam(self.model, lr=self.params['LR'], weight_decay=self.params.get('weight_decay', 0.0), params_slice=sl,
+                       clip_val=self.gradient_clip_val, clip_algorithm=self.gradient_clip_algorithm)
         sched = None
         if self.params.get('scheduler_gamma') is not None:
             sched = ExponentialLR(opt, self.params['scheduler_gamma'])

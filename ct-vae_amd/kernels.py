@@ -2504,3 +2504,26 @@ def adam_step(flat_params, flat_grads, exp_avg, exp_avg_sq, state, grad_scale=1.
     bump_param_epoch()
     native.call("ctvae_adam_step", flat_params.data_ptr(), flat_grads.data_ptr(), exp_avg.data_ptr(), exp_avg_sq.data_ptr(),
                 state.data_ptr(), flat_params.numel(), float(grad_scale))
+
+
+CLIP_ALGORITHMS = {"norm": 0, "value": 1}          # CTVAE_CLIP_NORM / CTVAE_CLIP_VALUE
+
+
+def grad_clip_workspace(device):
+    """The partial sums of ctvae_adam_step_clipped's norm pass (ctvae_grad_clip_workspace_floats() floats).  On the CPU (the
+    gloo tests run a test double of the kernel): an empty tensor."""
+    dev = torch.device(device)
+    if dev.type != "cuda":
+        return torch.zeros(0, dtype=torch.float32, device=dev)
+    return torch.zeros(int(native.load().ctvae_grad_clip_workspace_floats()), dtype=torch.float32, device=dev)
+
+
+def adam_step_clipped(flat_params, flat_grads, exp_avg, exp_avg_sq, state, grad_scale, algorithm, clip_val, workspace=None,
+                      norm_out=None):
+    """adam_step on the gradient clipped as torch.nn.utils.clip_grad_norm_ (algorithm "norm": the pre-clip norm of
+    flat_grads * grad_scale goes to norm_out, a one-float device tensor) or clip_grad_value_ ("value") would clip it."""
+    _req_cuda(flat_params, flat_grads)
+    bump_param_epoch()
+    native.call("ctvae_adam_step_clipped", flat_params.data_ptr(), flat_grads.data_ptr(), exp_avg.data_ptr(),
+                exp_avg_sq.data_ptr(), state.data_ptr(), flat_params.numel(), float(grad_scale), CLIP_ALGORITHMS[algorithm],
+                float(clip_val), native.ptr(workspace), native.ptr(norm_out))

@@ -7,6 +7,8 @@ One process per GPU (launch with ``python -m torch.distributed.run``); Lightning
 Checkpoints: top-k on ``val_Reconstruction_Loss`` + ``last.ckpt`` with ``state_dict`` keys prefixed ``model.``
 so they interchange with the reference's (run.py:85-97), plus a ``trainer`` entry (optimizer moments, scheduler, epoch, global
 step, random streams) for ``trainer_params.resume_from_checkpoint`` without ``load_weights_only`` (run.py:85-101: full resume).
+``trainer_params.gradient_clip_val`` / ``gradient_clip_algorithm`` clip the gradients before every optimizer step as the
+Lightning Trainer does (configs/gammavae.yaml); without them the step is unchanged.
 """
 import argparse
 import json
@@ -166,7 +168,9 @@ def main(argv=None):
     log_dir = os.path.join(config['logging_params'].get('save_dir', 'logs/'), config['logging_params'].get('name', mp['name']))
     os.makedirs(os.path.join(log_dir, "checkpoints"), exist_ok=True)
     log_file = open(os.path.join(log_dir, f"metrics_rank{rank}.jsonl"), "a") if rank == 0 else None
-    exp = VAEXperiment(model, config['exp_params'], ddp=ddp, log_file=log_file)
+    tp = config['trainer_params']
+    exp = VAEXperiment(model, config['exp_params'], ddp=ddp, log_file=log_file, gradient_clip_val=tp.get('gradient_clip_val'),
+                       gradient_clip_algorithm=tp.get('gradient_clip_algorithm'))
     if config['data_params'].get('hbm_images'):
         data = HbmData(config['data_params'], mp, dev, rank, world, seed)
     else:

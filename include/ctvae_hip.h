@@ -564,6 +564,25 @@ size_t ctvae_adam_state_floats(void);
 int ctvae_adam_step(float* params, const float* grads, float* exp_avg, float* exp_avg_sq, float* state, long n,
                     float grad_scale, void* stream);
 
+/* ctvae_adam_step with gradient clipping in front of it (Lightning's gradient_clip_val / gradient_clip_algorithm, 32-bit):
+ * the gradient g * grad_scale (grad_scale: the DDP 1/world factor, applied before the clip) is clipped, then Adam adds the
+ * weight decay to the clipped gradient and steps exactly as ctvae_adam_step does (same state, same step counter advance).
+ *   CTVAE_CLIP_NORM  torch.nn.utils.clip_grad_norm_(max_norm = clip_val, norm_type = 2): total = ||g * grad_scale||_2 over
+ *                    the n elements, c = clip_val / (total + 1e-6) clamped to at most 1, every gradient multiplied by c (also
+ *                    when c == 1).  A NaN norm makes c and every updated element NaN; an infinite norm gives c = 0.  Two
+ *                    launches: a streaming sum of squares into one partial per workgroup in `workspace`
+ *                    (ctvae_grad_clip_workspace_floats() floats, device), and the Adam update, whose every workgroup merges
+ *                    the partials.  The norm is bit-reproducible for a given n.  total is written to norm_out (device, one
+ *                    float; may be NULL).
+ *   CTVAE_CLIP_VALUE torch.nn.utils.clip_grad_value_(clip_val): clamp(g * grad_scale, -clip_val, clip_val), NaN stays NaN.
+ *                    One launch; workspace and norm_out are not used (may be NULL).
+ * clip_val must be > 0 (no clipping: call ctvae_adam_step). */
+#define CTVAE_CLIP_NORM 0
+#define CTVAE_CLIP_VALUE 1
+size_t ctvae_grad_clip_workspace_floats(void);
+int ctvae_adam_step_clipped(float* params, const float* grads, float* exp_avg, float* exp_avg_sq, float* state, long n,
+                            float grad_scale, int algorithm, float clip_val, float* workspace, float* norm_out, void* stream);
+
 /* Input side: the reference's per-sample pipeline ToTensor -> CenterCrop(crop) -> Resize(size)
  * (dataset.py:72-80; bilinear, align_corners=False, no antialias -- what transforms.Resize does to a tensor; images smaller
  * than the crop are zero-padded as torchvision's center_crop does) for a batch of rows of a uint8 dataset
