@@ -1,6 +1,6 @@
 // Paired backward launch (ctvae_conv_backward): while a PairCtx is installed for the calling thread, the data-gradient
-// launcher (tapgemm_fast.hip, 64x64 pipelined tile kernel) and the weight-gradient launcher (wgrad.hip, lean 64x64 kernel)
-// RECORD their main launch instead of issuing it, and every finishing launch behind them (split-K finish, slab
+// launcher (tapgemm_fast.hip, 64x64 or 128x32 pipelined tile kernel) and the weight-gradient launcher (wgrad.hip, lean 64x64
+// kernel or plain-load 128x32 kernel) RECORD their main launch instead of issuing it, and every finishing launch behind them (split-K finish, slab
 // reduction) is queued; pair_flush() then issues ONE conv_bwd_pair_kernel for both GEMMs (or the single recorded kernel,
 // if only one side took its pairable path) followed by the queued launches in order.  Launches of any other path are
 // issued immediately as usual -- the two GEMMs are independent and work in disjoint halves of the workspace.
@@ -19,9 +19,11 @@ struct PairCtx {
   long dgrad_wgs = 0;          // workgroups of the data gradient and K chunks of its longest one (planned before the weight
   int dgrad_chunks = 0;        // gradient is sized)
   TapGemmArgs A;
+  int wmA = 2;                 // data-gradient tile: 2 = 64 x 64, 4 = 128 x 32
   unsigned gxA = 0, gyA = 0, gzA = 0;
   double flopsA = 0, bytesA = 0;
   WgradArgs B;
+  int wkB = 2;                 // weight-gradient tile: 2 = 64 x 64, 4 = 128 x 32
   int lgQw = -1, lgQhw = -1, lgC = -1;
   unsigned gxB = 0, gyB = 0;
   double flopsB = 0, bytesB = 0;
@@ -40,7 +42,7 @@ struct PairCtx {
 
 PairCtx*& pair_ctx();                                    // tapgemm_fast.hip (thread-local, null = not pairing)
 int pair_flush(PairCtx& c, hipStream_t st);              // tapgemm_fast.hip
-int launch_wgrad_fast_recorded(const PairCtx& c, hipStream_t st);   // wgrad.hip: the recorded weight-gradient kernel on its own
+int launch_wgrad_recorded(const PairCtx& c, hipStream_t st);        // wgrad.hip: the recorded weight-gradient kernel on its own
 int launch_finish_recorded(const PairCtx& c, hipStream_t st);       // wgrad.hip: recorded reduction (+ split-K finish) in one launch
 int launch_splitk_recorded(const PairCtx& c, hipStream_t st);       // tapgemm.hip: recorded split-K finish on its own
 int launch_bn_bwd_finalize_job(const BnFinJob& j, hipStream_t st);  // bn.hip: the finalize job as a launch of its own

@@ -79,23 +79,29 @@ __global__ __launch_bounds__(256) void tapgemm_fast_kernel(const TapGemmArgs a) 
 }
 
 // One launch for the two independent GEMMs of a layer's backward pass: workgroups [0, nA) run the data-gradient tile kernel
-// (64 x 64 tiles, pipelined loop), the others the weight-gradient kernel (64 x 64 tiles of dW per pixel slice).  Both
-// launches on their own are one lock-step round of workgroups that pays the kernel boundary (previous kernel's L2
-// write-back, launch gap, prologue, store burst: ~6.5 us) for ~20 us of MFMA work; sharing a launch
-// pays it once and lets the weight-gradient workgroups start while the data-gradient's stores drain.
-// XFB: the weight-gradient role applies the previous block's BatchNorm + activation to its X operand on load
+// (pipelined loop), the others the weight-gradient kernel (tiles of dW per pixel slice).  Both launches on their own are one
+// lock-step round of workgroups that pays the kernel boundary (previous kernel's L2 write-back, launch gap, prologue, store
+// burst: ~6.5 us) for ~20 us of MFMA work; sharing a launch pays it once and lets the weight-gradient
+// workgroups start while the data-gradient's stores drain.
+// XFB: the 64 x 64 weight-gradient role applies the previous block's BatchNorm + activation to its X operand on load (the
+//      128 x 32 role, wgrad_plain_body, decides that at run time)
 // PDA: prefetch depth (chunks) of the data-gradient role's global loads (4 for launches of at most two workgroups per CU)
-template <bool XFB, int PDA = 1>
+// AWM: the data-gradient role's tile, (AWM * 32) x (128 / AWM): 2 = 64 x 64, 4 = 128 x 32 (N <= 32)
+// BWK: the weight-gradient role's tile of dW, (BWK * 32) x (128 / BWK): 2 = 64 x 64 (lean body), 4 = 128 x 32 (plain-load body)
+template <bool XFB, int PDA = 1, int AWM = 2, int BWK = 2>
 __global__ __launch_bounds__(256) void conv_bwd_pair_kernel(const TapGemmArgs a, const WgradArgs w, int lgQw, int lgQhw, int lgC,
                                                             int nA, int gxA, int gyA, int gxB, int gyB) {
-  // the data-gradient kernel's arrays; the weight-gradient workgroups use the first 8 KB of each for their X / dY chunks
-  __shared__ __attribute__((aligned(16))) float sAbuf[2 * 64 * LDK];
-  __shared__ __attribute__((aligned(16))) float sBbuf[2 * 64 * LDK];
-  __shared__ __attribute__((aligned(16))) int sOut[64];
+  static_assert((AWM == 2 || AWM == 4) && (BWK == 2 || BWK == 4), "64 x 64 or 128 x 32 tiles");
+  constexpr int ABM = AWM * 32, ABN = (4 / AWM) * 32;   // data-gradient tile
+  constexpr int BKT = BWK * 32, BNT = (4 / BWK) * 32;   // weight-gradient tile
+  // the data-gradient kernel's arrays; the weight-gradient workgroups use the front of each for their X / dY chunks
+  __shared__ __attribute__((aligned(16))) float sAbuf[2 * ABM * LDK];
+  __shared__ __attribute__((aligned(16))) float sBbuf[2 * ABN * LDK];
+  __shared__ __attribute__((aligned(16))) int sOut[ABM];
   __shared__ unsigned sPix[2][MC];
   __shared__ unsigned sMsk[2][MC];
   __shared__ unsigned sOutB[2][MC];
-  static_assert(2 * 64 * LDK >= MC * 64, "chunk buffers of the weight-gradient kernel fit");
+  static_assert(2 * ABM * LDK >= MC * BKT && 2 * ABN * LDK >= MC * BNT, "chunk buffers of the weight-gradient kernel fit");
   // both roles read their arguments behind ONE batch of scalar loads (kernarg_warm); the three the data-gradient role
   // branches on first come back with it
   constexpr int kOffW = (sizeof(TapGemmArgs) + 7) / 8 * 8, kOffI = kOffW + sizeof(WgradArgs);
@@ -104,7 +110,7 @@ __global__ __launch_bounds__(256) void conv_bwd_pair_kernel(const TapGemmArgs a,
   kernarg_warm_get<kOffI + 8 * 4, kOffI + 12, kOffI + 16, kOffI + 20>(k_nA, k_gxA, k_gyA);
   const int L = blockIdx.x;
   if (L < k_nA) {
-    constexpr int WM = 2, WN = 2, TM = 1, TN = 1, PF = 3;
+    constexpr int WM = AWM, WN = 4 / AWM, TM = 1, TN = 1, PF = 3;
     constexpr bool WT = true, XF = false;
     constexpr int PD = PDA;
     const int vbx = L % k_gxA, vr = L / k_gxA, vby = vr % k_gyA, vbz = vr / k_gyA, vgx = k_gxA;
@@ -116,7 +122,12 @@ __global__ __launch_bounds__(256) void conv_bwd_pair_kernel(const TapGemmArgs a,
     // 51.2 -> 39.7 MB per launch but LOST: VanillaVAE bs = 256 1.599 -> 1.612 ms per step, the rounding costing more than the
     // L2 hits return to an MFMA-bound launch.  Removed.)
     const int Lb = L - k_nA;
-    wgrad_fast_body<2, 2, 1, 1, XFB>(w, lgQw, lgQhw, lgC, sAbuf, sBbuf, sPix, sMsk, sOutB, Lb % gxB, Lb / gxB, gxB, gyB);
+    if constexpr (BWK == 4) {   // int views of the row tables (same object, signedness variant: no aliasing question)
+      wgrad_plain_body<4, 1, true, true>(w, sAbuf, sBbuf, reinterpret_cast<int(*)[MC]>(sPix), reinterpret_cast<int(*)[MC]>(sMsk),
+                                         reinterpret_cast<int(*)[MC]>(sOutB), Lb % gxB, Lb / gxB, gxB, gyB);
+    } else {
+      wgrad_fast_body<2, 2, 1, 1, XFB>(w, lgQw, lgQhw, lgC, sAbuf, sBbuf, sPix, sMsk, sOutB, Lb % gxB, Lb / gxB, gxB, gyB);
+    }
   }
 }
 
@@ -162,10 +173,11 @@ static int launch_fast_cfg(const TapGemmArgs& a, int pf, hipStream_t st) {
            (!wt && a.xf_scale != nullptr) ? ",true" : (deep ? ",false,4" : ""));
   double macs = 0;
   for (int c = 0; c < a.g.ncls; ++c) macs += (double)a.Mc * a.N * a.g.ntaps[c] * a.g.gC;
-  if constexpr (WM == 2 && WN == 2 && TM == 1 && TN == 1) {
+  if constexpr (TM == 1 && TN == 1) {   // 64 x 64 and 128 x 32 tiles
     PairCtx* pc = pair_ctx();
     if (pc != nullptr && wt && pf == 3 && !pc->haveA) {   // ctvae_conv_backward: issued by pair_flush()
       pc->haveA = true;
+      pc->wmA = WM;
       pc->A = args;
       pc->gxA = grid.x; pc->gyA = grid.y; pc->gzA = grid.z;
       pc->flopsA = 2.0 * macs;
@@ -204,19 +216,30 @@ int pair_flush(PairCtx& c, hipStream_t st) {
   if (c.haveA && c.haveB) {
     const unsigned nA = c.gxA * c.gyA * c.gzA, nB = c.gxB * c.gyB;
     ProfScope ps("conv_bwd_pair_kernel", st, c.flopsA + c.flopsB, c.bytesA + c.bytesB);
-#define CTVAE_PAIR(XFB_, PD_)                                                                                                  \
-  hipLaunchKernelGGL((conv_bwd_pair_kernel<XFB_, PD_>), dim3(nA + nB), dim3(256), 0, st, c.A, c.B, c.lgQw, c.lgQhw, c.lgC, (int)nA, \
-                     (int)c.gxA, (int)c.gyA, (int)c.gxB, (int)c.gyB)
-    if (c.B.xf_scale != nullptr) CTVAE_PAIR(true, 1);
-    else CTVAE_PAIR(false, 1);
+#define CTVAE_PAIR(XFB_, AWM_, BWK_)                                                                                                  \
+  hipLaunchKernelGGL((conv_bwd_pair_kernel<XFB_, 1, AWM_, BWK_>), dim3(nA + nB), dim3(256), 0, st, c.A, c.B, c.lgQw, c.lgQhw, c.lgC, \
+                     (int)nA, (int)c.gxA, (int)c.gyA, (int)c.gxB, (int)c.gyB)
+    const bool xfb = c.B.xf_scale != nullptr;
+    if (c.wkB == 4) {   // 128 x 32 weight-gradient tiles (N <= 32)
+      if (c.wmA == 4) CTVAE_PAIR(false, 4, 4);
+      else CTVAE_PAIR(false, 2, 4);
+    } else if (c.wmA == 4) {   // 128 x 32 data-gradient tiles
+      if (xfb) CTVAE_PAIR(true, 4, 2);
+      else CTVAE_PAIR(false, 4, 2);
+    } else if (xfb) {
+      CTVAE_PAIR(true, 2, 2);
+    } else {
+      CTVAE_PAIR(false, 2, 2);
+    }
 #undef CTVAE_PAIR
     CTVAE_LAUNCH_CHECK();
   } else if (c.haveA) {
-    ProfScope ps("tapgemm_fast_kernel<2,2,1,1,true,3>", st, c.flopsA, c.bytesA);
-    hipLaunchKernelGGL((tapgemm_fast_kernel<2, 2, 1, 1, true, 3>), dim3(c.gxA, c.gyA, c.gzA), dim3(256), 0, st, c.A);
+    ProfScope ps(c.wmA == 4 ? "tapgemm_fast_kernel<4,1,1,1,true,3>" : "tapgemm_fast_kernel<2,2,1,1,true,3>", st, c.flopsA, c.bytesA);
+    if (c.wmA == 4) hipLaunchKernelGGL((tapgemm_fast_kernel<4, 1, 1, 1, true, 3>), dim3(c.gxA, c.gyA, c.gzA), dim3(256), 0, st, c.A);
+    else hipLaunchKernelGGL((tapgemm_fast_kernel<2, 2, 1, 1, true, 3>), dim3(c.gxA, c.gyA, c.gzA), dim3(256), 0, st, c.A);
     CTVAE_LAUNCH_CHECK();
   } else if (c.haveB) {
-    const int rc = launch_wgrad_fast_recorded(c, st);
+    const int rc = launch_wgrad_recorded(c, st);
     if (rc) return rc;
   }
   if (c.haveRed || (c.haveSK && c.haveBF)) {   // slab reduction, with the data gradient's split-K finish (and the BatchNorm-backward finalize of

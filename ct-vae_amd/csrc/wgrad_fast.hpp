@@ -1,5 +1,6 @@
-// Lean weight-gradient kernel body (moved out of wgrad.hip so that tapgemm_fast.hip can pair it with a data-gradient
-// tile kernel in ONE launch, see conv_bwd_pair_kernel).  wgrad.hip documents the algorithm.
+// Weight-gradient kernel bodies (moved out of wgrad.hip so that tapgemm_fast.hip can pair them with a data-gradient tile
+// kernel in ONE launch, see conv_bwd_pair_kernel): the lean body (64 x 64 / 128 x 128 tiles) and the plain-load body (128 x 32
+// tiles of the layers with N <= 32, and the scalar fallbacks).  wgrad.hip documents the algorithm.
 #pragma once
 #include "common.hpp"
 
@@ -294,6 +295,259 @@ __device__ __forceinline__ void wgrad_fast_body(const WgradArgs& a, int lgQw, in
   __builtin_amdgcn_s_waitcnt(0);
   WPHASE(5);
 #endif
+}
+
+// ---- plain-load variant (wgrad_kernel; the 128 x 32 weight-gradient role of conv_bwd_pair_kernel) --------------------------
+// WK x WN waves, one 32x32 MFMA tile each.  sXbuf[MC*WK*32], sDbuf[MC*WN*32], sRowPix / sRowYX / sRowOut [2][MC]: the calling
+// kernel's LDS.  vbx, vby / vgx, vgy: the workgroup's position in / the size of the kernel's own (tile, slice) grid.
+template <int WK, int WN, bool XVEC, bool DVEC>
+__device__ __forceinline__ void wgrad_plain_body(const WgradArgs& a, float* sXbuf, float* sDbuf, int (*sRowPix)[MC],
+                                                 int (*sRowYX)[MC], int (*sRowOut)[MC], int vbx, int vby, int vgx, int vgy) {
+  constexpr int KT = WK * 32, NT = WN * 32;
+  static_assert(WK * WN == 4, "4 waves");
+
+  const ConvGeom& g = a.g;
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int wk = wave / WN, wn = wave % WN;
+  const int li = lane & 31, lh = lane >> 5;
+  // XCD-aware order (see wgrad_fast_body): the output tiles of one pixel slice share one L2
+  int split = vby, xtile = vbx;
+  {
+    const int T = vgx, L = vby * T + vbx, full = (vgy >> 3) * 8 * T;
+    if (L < full) {
+      const int grp = L / (8 * T), r = L - grp * 8 * T;
+      split = grp * 8 + (r & 7);
+      xtile = r >> 3;
+    }
+  }
+  const int ktg = xtile / a.ntiles, nt = xtile - ktg * a.ntiles;
+  int cls = 0;
+#pragma unroll
+  for (int c = 1; c < kMaxCls; ++c)
+    if (c < g.ncls && ktg >= a.ktile_start[c]) cls = c;
+  const int kt0 = (ktg - a.ktile_start[cls]) * KT;
+  const int n0 = nt * NT;
+  const int gC = g.gC;
+  const int Ktot = g.ntaps[cls] * gC;
+  const int N = a.N;
+
+  const int cbeg = split * a.chunks_per_split;
+  const int nchunks_all = (a.Mc + MC - 1) / MC;
+  int cend = cbeg + a.chunks_per_split;
+  if (cend > nchunks_all) cend = nchunks_all;
+  const int nch = cend - cbeg;
+
+  auto rowinfo = [&](int c, int buf) {
+    if (tid < MC) {
+      int m = (cbeg + c) * MC + tid;
+      if (m < a.Mc) {
+        int b, qy, qx;
+        decode_m(g, m, b, qy, qx);
+        sRowPix[buf][tid] = (b * g.gH + qy * g.is) * g.gW + qx * g.is;
+        sRowYX[buf][tid] = ((qy * g.is) << 16) | (qx * g.is);
+        sRowOut[buf][tid] = scatter_pix(g, cls, b, qy, qx);
+      } else {
+        sRowPix[buf][tid] = -1;
+        sRowYX[buf][tid] = 0;
+        sRowOut[buf][tid] = -1;
+      }
+    }
+  };
+
+  // per-thread fixed k column(s) of the X tile
+  constexpr int XQ = KT / 4;            // float4 per row
+  constexpr int X_V = (MC * XQ) / 256;  // float4 per thread
+  constexpr int X_S = (MC * KT) / 256;  // scalars per thread
+  constexpr int DQ = NT / 4;
+  constexpr int D_V = (MC * DQ) / 256 > 0 ? (MC * DQ) / 256 : 1;
+  constexpr int D_S = (MC * NT) / 256;
+
+  int x_dy = 0, x_dx = 0, x_c = 0;
+  bool x_kok = false;
+  {
+    int kcol = XVEC ? 4 * (tid % XQ) : (tid % KT);
+    int k = kt0 + kcol;
+    x_kok = k < Ktot;
+    int t = x_kok ? k / gC : 0;
+    x_c = k - t * gC;
+    Tap tp = g.taps[cls][t];
+    x_dy = tp.dy;
+    x_dx = tp.dx;
+  }
+
+  const bool xf_on = XVEC && a.xf_scale != nullptr && x_kok;
+  const f32x4 xf_sc = xf_on ? *reinterpret_cast<const f32x4*>(a.xf_scale + x_c) : f32x4{0.f, 0.f, 0.f, 0.f};
+  const f32x4 xf_sh = xf_on ? *reinterpret_cast<const f32x4*>(a.xf_shift + x_c) : f32x4{0.f, 0.f, 0.f, 0.f};
+  const float xf_ns = a.xf_act == ACT_LRELU ? kLeaky : (a.xf_act == ACT_RELU ? 0.f : 1.f);
+  f32x4 rx[XVEC ? X_V : 1];
+  [[maybe_unused]] float rx_in[XVEC ? X_V : 1];      // 1 where the loaded pixel lies inside the image (the shift applies), else 0
+  float rxs[XVEC ? 1 : X_S];
+  f32x4 rd[DVEC ? D_V : 1];
+  [[maybe_unused]] bool rd_ok[DVEC ? D_V : 1];
+  float rds[DVEC ? 1 : D_S];
+
+  auto load_chunk = [&](int buf) {
+    if constexpr (XVEC) {
+      // table reads first, then UNCONDITIONAL loads at a clamped address (the tensor's first pixel for a tap outside the image; the
+      // zero is selected when the chunk is stored): `if (ok) v = load` is a branch per load, behind which the compiler waits
+      // vmcnt(0) -- the chunk's loads went out one memory round trip at a time
+      int pixv[X_V], yxv[X_V];
+#pragma unroll
+      for (int j = 0; j < X_V; ++j) {
+        const int r = tid / XQ + (256 / XQ) * j;
+        pixv[j] = sRowPix[buf][r];
+        yxv[j] = sRowYX[buf][r];
+      }
+#pragma unroll
+      for (int j = 0; j < X_V; ++j) {
+        const int iy = (yxv[j] >> 16) + x_dy, ix = (yxv[j] & 0xffff) + x_dx;
+        const bool ok = x_kok && pixv[j] >= 0 && (unsigned)iy < (unsigned)g.gH && (unsigned)ix < (unsigned)g.gW;
+        const long off = ok ? (long)(pixv[j] + x_dy * g.gW + x_dx) * gC + x_c : 0L;
+        rx[j] = *reinterpret_cast<const f32x4*>(a.X + off);
+        rx_in[j] = ok ? 1.f : 0.f;      // zero / lazy BatchNorm apply when the chunk is STORED (applied here it consumed every load at once)
+      }
+    } else {
+#pragma unroll
+      for (int j = 0; j < X_S; ++j) {
+        int r = tid / KT + (256 / KT) * j;
+        int pix = sRowPix[buf][r], yx = sRowYX[buf][r];
+        int iy = (yx >> 16) + x_dy, ix = (yx & 0xffff) + x_dx;
+        bool ok = x_kok && pix >= 0 && (unsigned)iy < (unsigned)g.gH && (unsigned)ix < (unsigned)g.gW;
+        rxs[j] = ok ? a.X[(long)(pix + x_dy * g.gW + x_dx) * gC + x_c] : 0.f;
+      }
+    }
+    if constexpr (DVEC) {
+      int spv[D_V];
+#pragma unroll
+      for (int j = 0; j < D_V; ++j) {
+        const int r = (tid + 256 * j) / DQ;
+        spv[j] = sRowOut[buf][r < MC ? r : 0];
+      }
+#pragma unroll
+      for (int j = 0; j < D_V; ++j) {
+        const int f = tid + 256 * j;
+        const int r = f / DQ, nq = f - r * DQ;
+        const int n = n0 + 4 * nq;
+        const bool ok = r < MC && spv[j] >= 0 && n < N;
+        rd[j] = *reinterpret_cast<const f32x4*>(a.dY + (ok ? (long)spv[j] * N + n : 0L));     // unconditional, clamped (see above)
+        rd_ok[j] = ok;
+      }
+    } else {
+#pragma unroll
+      for (int j = 0; j < D_S; ++j) {
+        int e = tid + 256 * j;
+        int r = e / NT, nn = e - r * NT;
+        int sp = sRowOut[buf][r];
+        int n = n0 + nn;
+        rds[j] = (sp >= 0 && n < N) ? a.dY[(long)sp * N + n] : 0.f;
+      }
+    }
+  };
+
+  auto store_chunk = [&]() {
+    float* sX = sXbuf;
+    float* sD = sDbuf;
+    if constexpr (XVEC) {
+#pragma unroll
+      for (int j = 0; j < X_V; ++j)
+        if (rx_in[j] == 0.f) rx[j] = f32x4{0.f, 0.f, 0.f, 0.f};       // tap outside the image / row beyond the tensor (clamped load)
+      if (xf_on) {   // lazy BatchNorm apply of the previous block (InXform); padding stays 0
+#pragma unroll
+        for (int j = 0; j < X_V; ++j)
+#pragma unroll
+          for (int e = 0; e < 4; ++e) {
+            const float t = rx[j][e] * xf_sc[e] + xf_sh[e] * rx_in[j];
+            rx[j][e] = fmaxf(t, t * xf_ns);
+          }
+      }
+#pragma unroll
+      for (int j = 0; j < X_V; ++j) {
+        int r = tid / XQ + (256 / XQ) * j;
+        *reinterpret_cast<f32x4*>(&sX[r * KT + 4 * (tid % XQ)]) = rx[j];
+      }
+    } else {
+#pragma unroll
+      for (int j = 0; j < X_S; ++j) sX[(tid / KT + (256 / KT) * j) * KT + (tid % KT)] = rxs[j];
+    }
+    if constexpr (DVEC) {
+#pragma unroll
+      for (int j = 0; j < D_V; ++j) {
+        int f = tid + 256 * j;
+        int r = f / DQ, nq = f - r * DQ;
+        if (r < MC) *reinterpret_cast<f32x4*>(&sD[r * NT + 4 * nq]) = rd_ok[j] ? rd[j] : f32x4{0.f, 0.f, 0.f, 0.f};
+      }
+    } else {
+#pragma unroll
+      for (int j = 0; j < D_S; ++j) sD[tid + 256 * j] = rds[j];
+    }
+  };
+
+  f32x16 acc;
+#pragma unroll
+  for (int r = 0; r < 16; ++r) acc[r] = 0.f;
+  float bsum = 0.f;
+  const bool do_bias = (a.pbias != nullptr) && (kt0 == 0) && (tid < NT);
+
+  if (nch > 0) {
+    rowinfo(0, 0);
+    __syncthreads();
+    load_chunk(0);
+    if (nch > 1) rowinfo(1, 1);
+    store_chunk();
+    __syncthreads();
+    for (int c = 0; c < nch; ++c) {
+      const float* sX = sXbuf;
+      const float* sD = sDbuf;
+      if (c + 1 < nch) load_chunk((c + 1) & 1);
+      if (c + 2 < nch) rowinfo(c + 2, c & 1);
+      {   // fragments one group of four steps ahead, MFMA / LDS-read order pinned (as in wgrad_fast_body)
+        constexpr int GS = 4, NG = (MC / 2) / GS;
+        float fa[2][GS], fb[2][GS];
+        auto rdg = [&](int gi, int set) {
+#pragma unroll
+          for (int q = 0; q < GS; ++q) {
+            const int s = gi * GS + q;
+            fa[set][q] = sX[(2 * s + lh) * KT + wk * 32 + li];
+            fb[set][q] = sD[(2 * s + lh) * NT + wn * 32 + li];
+          }
+        };
+        rdg(0, 0);
+#pragma unroll
+        for (int gi = 0; gi < NG; ++gi) {
+          if (gi + 1 < NG) rdg(gi + 1, (gi + 1) & 1);
+#pragma unroll
+          for (int q = 0; q < GS; ++q) acc = __builtin_amdgcn_mfma_f32_32x32x2f32(fa[gi & 1][q], fb[gi & 1][q], acc, 0, 0, 0);
+#pragma unroll
+          for (int q = 0; q < GS; ++q) {
+            __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
+            __builtin_amdgcn_sched_group_barrier(0x100, 2, 0);
+          }
+        }
+      }
+      if (do_bias) {
+#pragma unroll 8
+        for (int r = 0; r < MC; ++r) bsum += sD[r * NT + tid];
+      }
+      __syncthreads();
+      if (c + 1 < nch) {
+        store_chunk();
+        __syncthreads();
+      }
+    }
+  }
+
+  // ---- write partial tile ---------------------------------------------------------------------
+  const int col = n0 + wn * 32 + li;
+#pragma unroll
+  for (int r = 0; r < 16; ++r) {
+    int k = kt0 + wk * 32 + 8 * (r >> 2) + 4 * lh + (r & 3);
+    if (k < Ktot && col < N) {
+      int t = k / gC, c = k - t * gC;
+      int wrow = g.taps[cls][t].wtap * (g.wts / g.wCo) + c * (g.wrs / g.wCo);   // row of the [rows][N] weight block (geom.hpp wts / wrs)
+      a.part[((long)split * a.rows_total + wrow) * N + col] = acc[r];
+    }
+  }
+  if (do_bias && n0 + tid < N) a.pbias[(long)(split * g.ncls + cls) * N + n0 + tid] = bsum;
 }
 
 }  // namespace ctvae
