@@ -441,8 +441,9 @@ int launch_vq_inds(const float* lat, const float* cb, long long* inds, int B, in
     (void)hipFuncSetAttribute(reinterpret_cast<const void*>(vq_inds_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024);
     attr_set = true;
   }
-  ProfScope ps("vq_inds_kernel", st, 2.0 * (double)P * K * D, 4.0 * (double)P * D + 8.0 * (double)P * C);
-  if (K <= 64 && (Dc == 32 || Dc == 64 || Dc == 128)) {
+  const bool reg = K <= 64 && (Dc == 32 || Dc == 64 || Dc == 128);
+  ProfScope ps(reg ? "vq_inds_reg_kernel" : "vq_inds_kernel", st, 2.0 * (double)P * K * D, 4.0 * (double)P * D + 8.0 * (double)P * C);
+  if (reg) {
     // rows per workgroup: the codebook is staged per workgroup (measured at 16 / 32 / 64 rows: 40.8 / 38.2 / 36.9 us for Dc = 128,
     // 25.2 / 24.7 / 25.8 us for Dc = 32)
     const int rpw = Dc == 128 ? 64 : 16;
@@ -505,10 +506,13 @@ int launch_vq_backward(const float* gq, const float* gvq, const float* lat, cons
                                     hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
           attr_set = true;
         }
-        ProfScope ps("vq_bwd_codebook_pos_kernel", st, 0.0, 4.0 * (double)P * D + 8.0 * (double)P * C + 4.0 * S * n_all);
-        hipLaunchKernelGGL(vq_bwd_codebook_pos_kernel, dim3(S, C), dim3(256), smem, st, gvq, lat, cb, inds, ws, P, D, K, Dc, C,
-                           HW, Ps);
-        CTVAE_LAUNCH_CHECK();
+        {
+          ProfScope ps("vq_bwd_codebook_pos_kernel", st, 0.0, 4.0 * (double)P * D + 8.0 * (double)P * C + 4.0 * S * n_all);
+          hipLaunchKernelGGL(vq_bwd_codebook_pos_kernel, dim3(S, C), dim3(256), smem, st, gvq, lat, cb, inds, ws, P, D, K, Dc,
+                             C, HW, Ps);
+          CTVAE_LAUNCH_CHECK();
+        }
+        ProfScope pr("vq_cb_reduce_kernel", st, 0.0, 4.0 * (S + 1.0) * n_all);
         hipLaunchKernelGGL(vq_cb_reduce_kernel, dim3(ceil_div((int)n_all, 256)), dim3(256), 0, st, ws, dcb, (int)n_all, S,
                            accumulate);
         CTVAE_LAUNCH_CHECK();
@@ -530,10 +534,13 @@ int launch_vq_backward(const float* gq, const float* gvq, const float* lat, cons
                                     hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
           attr_set_w = true;
         }
-        ProfScope ps("vq_bwd_codebook_posw_kernel", st, 0.0, 4.0 * (double)P * D + 8.0 * (double)P * C + 4.0 * S * n_all);
-        hipLaunchKernelGGL(vq_bwd_codebook_posw_kernel, dim3(S, C), dim3(256), smem, st, gvq, lat, cb, inds, ws, P, D, K, Dc, C,
-                           HW, Ps);
-        CTVAE_LAUNCH_CHECK();
+        {
+          ProfScope ps("vq_bwd_codebook_posw_kernel", st, 0.0, 4.0 * (double)P * D + 8.0 * (double)P * C + 4.0 * S * n_all);
+          hipLaunchKernelGGL(vq_bwd_codebook_posw_kernel, dim3(S, C), dim3(256), smem, st, gvq, lat, cb, inds, ws, P, D, K, Dc,
+                             C, HW, Ps);
+          CTVAE_LAUNCH_CHECK();
+        }
+        ProfScope pr("vq_cb_reduce_kernel", st, 0.0, 4.0 * (S + 1.0) * n_all);
         hipLaunchKernelGGL(vq_cb_reduce_kernel, dim3(ceil_div((int)n_all, 256)), dim3(256), 0, st, ws, dcb, (int)n_all, S,
                            accumulate);
         CTVAE_LAUNCH_CHECK();
@@ -546,11 +553,14 @@ int launch_vq_backward(const float* gq, const float* gvq, const float* lat, cons
     const size_t n = (size_t)C * K * Dc;
     if (ws == nullptr || S < 2 || ws_bytes / sizeof(float) < (size_t)S * n) S = 1;
     const int Ps = ceil_div(P, S);
-    ProfScope ps("vq_bwd_codebook_kernel", st, 0.0, 4.0 * (double)P * D + 8.0 * (double)P * C * (double)K / S);
-    hipLaunchKernelGGL(vq_bwd_codebook_kernel, dim3(K, C, S), dim3(256), 0, st, gvq, lat, cb, inds, dcb, P, D, K, Dc, C, HW,
-                       accumulate, S > 1 ? ws : nullptr, Ps);
-    CTVAE_LAUNCH_CHECK();
+    {
+      ProfScope ps("vq_bwd_codebook_kernel", st, 0.0, 4.0 * (double)P * D + 8.0 * (double)P * C * (double)K / S);
+      hipLaunchKernelGGL(vq_bwd_codebook_kernel, dim3(K, C, S), dim3(256), 0, st, gvq, lat, cb, inds, dcb, P, D, K, Dc, C, HW,
+                         accumulate, S > 1 ? ws : nullptr, Ps);
+      CTVAE_LAUNCH_CHECK();
+    }
     if (S > 1) {
+      ProfScope pr("vq_cb_reduce_kernel", st, 0.0, 4.0 * (S + 1.0) * n);
       hipLaunchKernelGGL(vq_cb_reduce_kernel, dim3(ceil_div((int)n, 256)), dim3(256), 0, st, ws, dcb, (int)n, S, accumulate);
       CTVAE_LAUNCH_CHECK();
     }
