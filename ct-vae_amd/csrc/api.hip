@@ -348,31 +348,6 @@ int ctvae_conv_dgrad(int kind, const float* dy, const float* w, const float* add
                         (hipStream_t)stream, nullptr, nullptr, &wf);
 }
 
-int ctvae_conv_dgrad_bn_rows(int kind, int B, int H, int W, int Ci, int Co, int k, int stride, int pad, int out_pad,
-                             size_t ws_bytes) {
-  if (!conv_kind_ok(kind)) return 0;
-  ConvGeom g;
-  if (conv_geom(g, kind, 2, B, H, W, Ci, Co, k, stride, pad, out_pad)) return 0;
-  return tapgemm_bnb_rows(g, ws_bytes / sizeof(float));
-}
-
-int ctvae_conv_dgrad_bn(int kind, const float* dy, const float* w, const float* add, const float* mask, int mask_act,
-                        float* dx, int B, int H, int W, int Ci, int Co, int k, int stride, int pad, int out_pad,
-                        const float* bn_y, const float* bn_mean, const float* bn_invstd, const float* bn_gamma,
-                        const float* bn_beta, int bn_act, float* bn_part, int bn_part_rows, float* ws, size_t ws_bytes,
-                        void* stream) {
-  if (!dy || !w || !dx || !conv_kind_ok(kind)) return kErrBadArg;
-  if (!bn_y || !bn_mean || !bn_invstd || !bn_gamma || !bn_beta || !bn_part) return kErrBadArg;
-  ConvGeom g;
-  if (conv_geom(g, kind, 2, B, H, W, Ci, Co, k, stride, pad, out_pad)) return kErrBadArg;
-  const int rows = tapgemm_bnb_rows(g, ws_bytes / sizeof(float));
-  if (rows <= 0 || rows != bn_part_rows) return kErrBadArg;
-  if (img_dgrad_supported(g) && (add != nullptr || mask != nullptr)) return kErrBadArg;   // image kernel has no add/mask
-  const BnBwdFuse f{bn_y, bn_mean, bn_invstd, bn_gamma, bn_beta, bn_act, bn_part};
-  return launch_tapgemm(g, dy, w, nullptr, add, mask, mask_act, dx, ACT_NONE, nullptr, ws, ws_bytes / sizeof(float),
-                        (hipStream_t)stream, &f);
-}
-
 int ctvae_conv_wgrad(int kind, const float* x, const float* dy, float* dw, float* dbias, int B, int H, int W, int Ci,
                      int Co, int k, int stride, int pad, int out_pad, int accumulate, const float* in_scale,
                      const float* in_shift, int in_act, const float* dy_bn_y, const float* dy_bn_coef, int dy_bn_act,

@@ -43,6 +43,10 @@ class ConvSpec:
         return ((h - 1) * self.stride - 2 * self.pad + self.k + self.out_pad,
                 (w - 1) * self.stride - 2 * self.pad + self.k + self.out_pad)
 
+    def geom(self, B, H, W):
+        """The ten integers by which every convolution entry point of the C ABI names a layer, in its order."""
+        return (self.kind, B, H, W, self.ci, self.co, self.k, self.stride, self.pad, self.out_pad)
+
 
 def _req_cuda(*ts):
     for t in ts:
@@ -68,19 +72,47 @@ def grad_target(p):
     return p.grad, 1
 
 
+def _grad_targets(p, q):
+    """grad_target of two parameters one kernel call writes (q may be None) under ONE accumulate flag: (gp, gq, accumulate).
+    Where only one of them is fresh it is materialised as zeros and both accumulate.  p is asked first: the first asker
+    consumes a lazily zeroed block's flag."""
+    gp, acc = grad_target(p)
+    if q is None:
+        return gp, None, acc
+    gq, accq = grad_target(q)
+    if accq != acc:
+        (gp if acc == 0 else gq).zero_()
+        acc = 1
+    return gp, gq, acc
+
+
 # ---------------------------------------------------------------------------------------------------
 # low level launch helpers (no autograd)
 # ---------------------------------------------------------------------------------------------------
-_wino_floats_cache = {}
+_geom_answers = {}
+
+
+def _geom_query(name, geom, *extra, tag=None):
+    """What the library's query entry point ``name`` answers for one layer geometry, name(*geom, *extra), asked once.
+    tag: library state the answer depends on besides its arguments."""
+    key = (name, geom, extra, tag)
+    v = _geom_answers.get(key)
+    if v is None:
+        v = _geom_answers[key] = getattr(native.load(), name)(*geom, *extra)
+    return v
 
 
 def wino_filter_floats(spec: ConvSpec, B, H, W, ws_numel) -> int:
     """Size of the Winograd filter hand-over buffer of this layer (0: its forward / data gradient are not both Winograd)."""
-    key = (spec.kind, B, H, W, spec.ci, spec.co, spec.k, spec.stride, spec.pad, spec.out_pad, ws_numel, native.winograd_enabled())
-    n = _wino_floats_cache.get(key)
-    if n is None:
-        n = _wino_floats_cache[key] = int(native.load().ctvae_conv_wino_filter_floats(*key[:10], ws_numel * 4))
-    return n
+    return int(_geom_query("ctvae_conv_wino_filter_floats", spec.geom(B, H, W), ws_numel * 4, tag=native.winograd_enabled()))
+
+
+def _coef_ptrs(in_coef, ci):
+    """(scale, shift) pointers into a [2][Ci] (or longer) coefficient block; (None, None) without one."""
+    if in_coef is None:
+        return None, None
+    p = in_coef.data_ptr()
+    return p, p + 4 * ci
 
 
 def conv_forward_raw(x, w, b, spec: ConvSpec, add=None, act=None, in_coef=None, in_act=ACT_NONE, wino_out=None, wino_ready=None):
@@ -91,11 +123,10 @@ def conv_forward_raw(x, w, b, spec: ConvSpec, add=None, act=None, in_coef=None, 
     ho, wo = spec.out_hw(H, W)
     y = torch.empty((B, ho, wo, spec.co), dtype=torch.float32, device=x.device)
     ws = native.workspace(x.device)
-    sc = in_coef.data_ptr() if in_coef is not None else None
-    sh = in_coef.data_ptr() + 4 * spec.ci if in_coef is not None else None
-    native.call("ctvae_conv_forward", spec.kind, x.data_ptr(), w.data_ptr(), native.ptr(b), native.ptr(add), y.data_ptr(),
-                B, H, W, spec.ci, spec.co, spec.k, spec.stride, spec.pad, spec.out_pad, spec.act if act is None else act,
-                sc, sh, in_act, native.ptr(wino_out), native.ptr(wino_ready), ws.data_ptr(), ws.numel() * 4)
+    g = spec.geom(B, H, W)
+    native.call("ctvae_conv_forward", g[0], x.data_ptr(), w.data_ptr(), native.ptr(b), native.ptr(add), y.data_ptr(),
+                *g[1:], spec.act if act is None else act, *_coef_ptrs(in_coef, spec.ci), in_act,
+                native.ptr(wino_out), native.ptr(wino_ready), ws.data_ptr(), ws.numel() * 4)
     return y
 
 
@@ -172,12 +203,22 @@ def conv_dgrad_raw(dy, w, spec: ConvSpec, in_hw, add=None, mask=None, mask_act=A
     H, W = in_hw
     dx = torch.empty((B, H, W, spec.ci), dtype=torch.float32, device=dy.device)
     ws = native.workspace(dy.device)
+    # this data gradient owns the whole workspace (conv_backward_raw asks with half of it)
     if wino_filters is not None and wino_filter_floats(spec, B, H, W, ws.numel()) != wino_filters.numel():
-        wino_filters = None        # the switch was flipped between forward and backward
-    native.call("ctvae_conv_dgrad", spec.kind, dy.data_ptr(), w.data_ptr(), native.ptr(add), native.ptr(mask), mask_act,
-                dx.data_ptr(), B, H, W, spec.ci, spec.co, spec.k, spec.stride, spec.pad, spec.out_pad,
-                native.ptr(wino_filters), ws.data_ptr(), ws.numel() * 4)
+        wino_filters = None        # made for another row count or Winograd setting: the data gradient picks its own kernel and filters
+    g = spec.geom(B, H, W)
+    native.call("ctvae_conv_dgrad", g[0], dy.data_ptr(), w.data_ptr(), native.ptr(add), native.ptr(mask), mask_act,
+                dx.data_ptr(), *g[1:], native.ptr(wino_filters), ws.data_ptr(), ws.numel() * 4)
     return dx
+
+
+def _stamp(t):
+    """Identity of a tensor as it is now: a hand-over is honoured only for the tensor it was made for, untouched since."""
+    return t.data_ptr(), t._version, tuple(t.shape)
+
+
+def _same(t, stamp):
+    return stamp is not None and _stamp(t) == stamp
 
 
 class BNLink:
@@ -188,7 +229,7 @@ class BNLink:
     separate pass over (g_a, y).  The sums are only used when the gradient tensor that arrives is exactly the one the
     dgrad wrote (same storage pointer, same version counter): if autograd summed several contributions, or anything
     modified it in place, the BatchNorm falls back to its own pass."""
-    __slots__ = ("y", "mean", "invstd", "gamma", "beta", "act", "part", "rows", "coef", "g_ptr", "g_ver", "g_shape", "slices", "sole", "g_hold")
+    __slots__ = ("y", "mean", "invstd", "gamma", "beta", "act", "part", "rows", "coef", "g", "slices", "sole", "g_hold")
 
     def __init__(self, y, mean, invstd, gamma, beta, act):
         self.y, self.mean, self.invstd, self.gamma, self.beta, self.act = y, mean, invstd, gamma, beta, act
@@ -198,16 +239,17 @@ class BNLink:
         self.rows = 0
         self.coef = None
         self.slices = None
-        self.g_ptr = self.g_ver = self.g_shape = None
+        self.g = None           # _stamp of the gradient tensor the published sums / slices belong to
 
     def publish_lazy(self, g, slices, n, geom):
         """Small layers (ctvae_conv_backward_lazy): the consumer's data gradient ran split-K and left its n raw slices
-        (channel-major, rows in that launch's own order: geom = its (kind, B, H, W, Ci, Co, k, stride, pad, out_pad)) in ``slices``; ``g`` is a placeholder that was never written -- the BatchNorm's backward sums the slices
-        itself (ctvae_bn_backward_fused).  Nothing else may consume g: take_lazy raises if another tensor arrives."""
+        (channel-major, rows in that launch's own order: geom = its ConvSpec.geom) in ``slices``; ``g`` is a placeholder that
+        was never written -- the BatchNorm's backward sums the slices itself (ctvae_bn_backward_fused).  Nothing else may
+        consume g: take_lazy raises if another tensor arrives."""
         self.slices = (slices, n, geom)
         self.g_hold = g
         self.part, self.rows, self.coef = None, 0, None
-        self.g_ptr, self.g_ver, self.g_shape = g.data_ptr(), g._version, tuple(g.shape)
+        self.g = _stamp(g)
 
     def take_lazy(self, g):
         """(slices, n, geom) when the consumer left its data gradient as raw slices, else None.  One use only."""
@@ -215,7 +257,7 @@ class BNLink:
         self.g_hold = None
         if sl is None:
             return None
-        if g.data_ptr() != self.g_ptr or g._version != self.g_ver or tuple(g.shape) != self.g_shape:
+        if not _same(g, self.g):
             raise RuntimeError("BNLink: the consumer left its data gradient as split-K slices for this BatchNorm's backward pass "
                                "(sole consumer of the layer's output), but a different gradient tensor arrived")
         return sl
@@ -224,43 +266,43 @@ class BNLink:
         """coef [7][C]: the consumer's finishing launch already ran this BatchNorm's backward finalize on the sums
         (ctvae_conv_backward bn_coef_out)."""
         self.part, self.rows, self.coef = part, rows, coef
-        self.g_ptr, self.g_ver, self.g_shape = g.data_ptr(), g._version, tuple(g.shape)
+        self.g = _stamp(g)
 
     def take(self, g):
         """(part, rows, coef) when ``g`` is the tensor the sums were computed for, else (None, 0, None).  One use only."""
         part, rows, coef = self.part, self.rows, self.coef
         self.part, self.rows, self.coef = None, 0, None
-        if part is None or g.data_ptr() != self.g_ptr or g._version != self.g_ver or tuple(g.shape) != self.g_shape:
+        if part is None or not _same(g, self.g):
             return None, 0, None
         return part, rows, coef
 
 
 class ActLink:
-    """Hand-over between a ConvAct layer with a fused activation and the SOLE consumer of its output h (declared by the
-    model code, e.g. blocks.ResidualLayer where h never leaves forward()).  The consumer's data gradient multiplies by
-    act'(h) in its epilogue (the ``mask`` operand of ctvae_conv_dgrad), so the tensor that arrives at the producer's
-    backward is already the gradient w.r.t. its pre-activation and the separate activation-backward pass is skipped.
-    The producer checks that it received exactly that tensor; anything else cannot be repaired and raises."""
-    __slots__ = ("act", "g_ptr", "g_ver", "g_shape", "done", "out_ref", "out_ver")
+    """Hand-over between a producer whose output r = act(pre) ends in a fused activation (ConvBNActConvAct: final_layer's
+    Tanh) and the consumer that claimed the link offered for r (offer_out_act_link / claim_out_act_link: the reconstruction
+    loss).  The consumer's backward multiplies by act'(r) itself and says so (publish_done), so the tensor that arrives at
+    the producer's backward is already the gradient w.r.t. its pre-activation and the separate activation-backward pass is
+    skipped.  The producer checks that it received exactly that tensor; anything else cannot be repaired and raises."""
+    __slots__ = ("act", "g", "done", "out_ref", "out_ver")
 
     def __init__(self, act):
         self.act = act
         self.done = False
-        self.g_ptr = self.g_ver = self.g_shape = None
+        self.g = None           # _stamp of the gradient tensor that carries the activation derivative
         self.out_ref = self.out_ver = None
 
     def publish_done(self, g):
         self.done = True
-        self.g_ptr, self.g_ver, self.g_shape = g.data_ptr(), g._version, tuple(g.shape)
+        self.g = _stamp(g)
 
     def take(self, g):
         """True when ``g`` already carries the activation derivative.  One use only."""
         done, self.done = self.done, False
         if not done:
             return False
-        if g.data_ptr() != self.g_ptr or g._version != self.g_ver or tuple(g.shape) != self.g_shape:
-            raise RuntimeError("ActLink: the activation backward was folded into the consumer's data gradient (sole "
-                               "consumer promised), but a different gradient tensor arrived")
+        if not _same(g, self.g):
+            raise RuntimeError("ActLink: the activation backward was folded into the consumer's backward pass (it claimed "
+                               "the link), but a different gradient tensor arrived")
         return True
 
 
@@ -304,7 +346,8 @@ def offer_lazy_grad(g, slices, n):
     if len(_lazy_grads) > 16:
         _lazy_grads.clear()
     # the entry keeps the placeholder alive: its address cannot be handed to another tensor while the entry exists, so a match
-    # on (address, version, size) below IS the placeholder (or a view of it), never a newcomer at a recycled address
+    # on (address, version, size) below IS the placeholder (or a view of it), never a newcomer at a recycled address.  Size, not
+    # shape as in _stamp: the placeholder reaches its consumer through a reshape's backward, i.e. as a view of another shape
     _lazy_grads[g.data_ptr()] = (slices, n, g._version, g.numel(), g)
 
 
@@ -320,15 +363,6 @@ def grad_slices_ok(t):
     """Model code: the gradient w.r.t. ``t`` is consumed by ONE backward that can sum split-K slices (see _lazy_grads)."""
     t._ctvae_grad_slices_ok = True
     return t
-
-
-_last_act_link = None  # set by ConvAct.forward (fused activation), picked up by the caller of .apply right after
-
-
-def pop_act_link():
-    global _last_act_link
-    link, _last_act_link = _last_act_link, None
-    return link
 
 
 _last_link = None     # set by ConvBNAct.forward, picked up by the caller of .apply (models/blocks.py) right after
@@ -350,19 +384,12 @@ def pop_lazy_bn():
     return lz
 
 
-_apply_sep_cache = {}
-
-
 def bn_apply_is_separate(spec, B, H, W) -> bool:
     """Does a training ConvBNAct of this geometry run its BatchNorm apply as a launch of its own (ctvae_conv_bn_act_apply_is_separate)?
     Only then is it worth handing the consumer the raw tensor: applying on load costs the consumer's tile kernels ~4 vector
     instructions per element next to their f32 MFMAs (+10-16 % per launch, measured)."""
     ws = native.workspace(torch.device("cuda", torch.cuda.current_device()))
-    key = (spec.kind, B, H, W, spec.ci, spec.co, spec.k, spec.stride, spec.pad, spec.out_pad, ws.numel())
-    v = _apply_sep_cache.get(key)
-    if v is None:
-        v = _apply_sep_cache[key] = bool(native.load().ctvae_conv_bn_act_apply_is_separate(*key[:10], ws.numel() * 4))
-    return v
+    return bool(_geom_query("ctvae_conv_bn_act_apply_is_separate", spec.geom(B, H, W), ws.numel() * 4))
 
 
 def lazy_bn_input_supported(spec, B, H, W) -> bool:
@@ -394,7 +421,14 @@ def link_of(x):
     return link if (link is not None and x.is_contiguous()) else None
 
 
-_bn_rows_cache = {}
+def _dy_bn_args(dy_bn):
+    """The weight gradient's dy_bn_y, dy_bn_coef, dy_bn_act, gy_out arguments of dy_bn = (y, coef, act, gy_out or None)."""
+    return (dy_bn[0].data_ptr(), dy_bn[1].data_ptr(), dy_bn[2], native.ptr(dy_bn[3])) if dy_bn is not None else (None, None, 0, None)
+
+
+def _bn_commit_args(bn_commit):
+    """bn_dgamma, bn_dbeta, bn_accumulate of bn_commit = (dgamma, dbeta, accumulate)."""
+    return (bn_commit[0].data_ptr(), bn_commit[1].data_ptr(), bn_commit[2]) if bn_commit is not None else (None, None, 0)
 
 
 def conv_wgrad_raw(x, dy, w_param, b_param, spec: ConvSpec, in_coef=None, in_act=ACT_NONE, dy_bn=None, bn_commit=None):
@@ -403,26 +437,30 @@ def conv_wgrad_raw(x, dy, w_param, b_param, spec: ConvSpec, in_coef=None, in_act
     data gradient (encoder.0) -- g_y is never written and the kernel commits the BatchNorm's parameter gradients."""
     B, H, W, _ = x.shape
     ws = native.workspace(x.device)
-    gw, acc = grad_target(w_param)
-    gb = None
-    if b_param is not None:
-        gb, accb = grad_target(b_param)
-        if accb != acc:   # keep one accumulate flag per call: materialise the fresh one as zeros
-            if acc == 0:
-                gw.zero_()
-            else:
-                gb.zero_()
-            acc = 1
-    sc = in_coef.data_ptr() if in_coef is not None else None
-    sh = in_coef.data_ptr() + 4 * spec.ci if in_coef is not None else None
-    by, bc, bact, bgy = (dy_bn[0].data_ptr(), dy_bn[1].data_ptr(), dy_bn[2], native.ptr(dy_bn[3])) if dy_bn is not None else (None, None, 0, None)
-    cg, cb, cacc = (bn_commit[0].data_ptr(), bn_commit[1].data_ptr(), bn_commit[2]) if bn_commit is not None else (None, None, 0)
-    native.call("ctvae_conv_wgrad", spec.kind, x.data_ptr(), dy.data_ptr(), gw.data_ptr(), native.ptr(gb),
-                B, H, W, spec.ci, spec.co, spec.k, spec.stride, spec.pad, spec.out_pad, acc, sc, sh, in_act,
-                by, bc, bact, bgy, cg, cb, cacc, ws.data_ptr(), ws.numel() * 4)
+    gw, gb, acc = _grad_targets(w_param, b_param)
+    g = spec.geom(B, H, W)
+    native.call("ctvae_conv_wgrad", g[0], x.data_ptr(), dy.data_ptr(), gw.data_ptr(), native.ptr(gb), *g[1:], acc,
+                *_coef_ptrs(in_coef, spec.ci), in_act, *_dy_bn_args(dy_bn), *_bn_commit_args(bn_commit),
+                ws.data_ptr(), ws.numel() * 4)
 
 
 _PAIR = True     # a layer's weight and data gradients share one call (ctvae_conv_backward); tests read the plan it implies
+
+
+def _conv_backward_lazy(x, dy, w_param, gw, gb, acc, spec, in_coef, in_act, pixel_major):
+    """ctvae_conv_backward_lazy where the data gradient of this geometry splits K: the weight (+ bias) gradient, and the data
+    gradient left as n raw slices -- channel-major for a BatchNorm's backward launch (pixel_major 0), pixel-major for an
+    element-wise consumer (1).  Returns (slices, n), or None where that form does not apply and nothing was launched."""
+    B, H, W, _ = x.shape
+    ws = native.workspace(x.device)
+    g = spec.geom(B, H, W)
+    n = _geom_query("ctvae_conv_backward_lazy_slices", g, 0 if pixel_major else 1, ws.numel() * 4)
+    if n <= 1:
+        return None
+    slices = torch.empty(n * B * H * W * spec.ci, dtype=torch.float32, device=dy.device)
+    native.call("ctvae_conv_backward_lazy", g[0], x.data_ptr(), dy.data_ptr(), w_param.data_ptr(), gw.data_ptr(), native.ptr(gb),
+                slices.data_ptr(), *g[1:], acc, *_coef_ptrs(in_coef, spec.ci), in_act, pixel_major, ws.data_ptr(), ws.numel() * 4)
+    return slices, n
 
 
 def conv_backward_raw(x, dy, w_param, b_param, spec: ConvSpec, link=None, mask=None, mask_act=ACT_NONE, wino_filters=None,
@@ -434,71 +472,43 @@ def conv_backward_raw(x, dy, w_param, b_param, spec: ConvSpec, link=None, mask=N
     accumulate): the rider also commits that BatchNorm's parameter gradients (only where no apply launch follows)."""
     B, H, W, _ = x.shape
     ws = native.workspace(x.device)
+    g = spec.geom(B, H, W)
+    # each GEMM of the paired call owns half the workspace (conv_dgrad_raw asks with all of it)
     if wino_filters is not None and wino_filter_floats(spec, B, H, W, ws.numel() // 2) != wino_filters.numel():
         # the forward pass ran Winograd over more rows than this backward pass sees (companion rows: x and y through one launch,
-        # only x differentiated), or the switch was flipped in between: the data gradient picks its own kernel and filters
+        # only x differentiated), or under another Winograd setting: the data gradient picks its own kernel and filters
         wino_filters = None
-    gw, acc = grad_target(w_param)
-    gb = None
-    if b_param is not None:
-        gb, accb = grad_target(b_param)
-        if accb != acc:
-            (gw if acc == 0 else gb).zero_()
-            acc = 1
+    gw, gb, acc = _grad_targets(w_param, b_param)
     dx = torch.empty((B, H, W, spec.ci), dtype=torch.float32, device=dy.device)
-    part, rows = None, 0
     if (link is not None and link.sole and tuple(link.y.shape) == (B, H, W, spec.ci) and mask is None and wino_filters is None
             and dy_bn is None and bn_commit is None):
-        key = (spec.kind, B, H, W, spec.ci, spec.co, spec.k, spec.stride, spec.pad, spec.out_pad, ws.numel(), "lazy")
-        n = _bn_rows_cache.get(key)
-        if n is None:
-            n = _bn_rows_cache[key] = native.load().ctvae_conv_backward_lazy_slices(*key[:-2], 1, ws.numel() * 4)
-        if n > 1:
+        lazy = _conv_backward_lazy(x, dy, w_param, gw, gb, acc, spec, in_coef, in_act, 0)
+        if lazy is not None:
             # small layer: the data gradient stays n raw split-K slices, summed by the BatchNorm's own backward launch
-            slices = torch.empty(n * B * H * W * spec.ci, dtype=torch.float32, device=dy.device)
-            native.call("ctvae_conv_backward_lazy", spec.kind, x.data_ptr(), dy.data_ptr(), w_param.data_ptr(), gw.data_ptr(),
-                        native.ptr(gb), slices.data_ptr(), B, H, W, spec.ci, spec.co, spec.k, spec.stride, spec.pad, spec.out_pad,
-                        acc, in_coef.data_ptr() if in_coef is not None else None,
-                        in_coef.data_ptr() + 4 * spec.ci if in_coef is not None else None, in_act, 0, ws.data_ptr(), ws.numel() * 4)
-            link.publish_lazy(dx, slices, n, key[:10])
+            link.publish_lazy(dx, *lazy, g)
             return dx
     if grad_slices and link is None and mask is None and wino_filters is None and dy_bn is None and bn_commit is None:
-        key = (spec.kind, B, H, W, spec.ci, spec.co, spec.k, spec.stride, spec.pad, spec.out_pad, ws.numel(), "slices")
-        n = _bn_rows_cache.get(key)
-        if n is None:
-            n = _bn_rows_cache[key] = native.load().ctvae_conv_backward_lazy_slices(*key[:-2], 0, ws.numel() * 4)
-        if n > 1:
+        lazy = _conv_backward_lazy(x, dy, w_param, gw, gb, acc, spec, in_coef, in_act, 1)
+        if lazy is not None:
             # the consumer of this gradient sums split-K slices itself (offer_lazy_grad): no finish launch, dx is a placeholder
-            slices = torch.empty(n * B * H * W * spec.ci, dtype=torch.float32, device=dy.device)
-            native.call("ctvae_conv_backward_lazy", spec.kind, x.data_ptr(), dy.data_ptr(), w_param.data_ptr(), gw.data_ptr(),
-                        native.ptr(gb), slices.data_ptr(), B, H, W, spec.ci, spec.co, spec.k, spec.stride, spec.pad, spec.out_pad,
-                        acc, in_coef.data_ptr() if in_coef is not None else None,
-                        in_coef.data_ptr() + 4 * spec.ci if in_coef is not None else None, in_act, 1, ws.data_ptr(), ws.numel() * 4)
-            offer_lazy_grad(dx, slices, n)
+            offer_lazy_grad(dx, *lazy)
             return dx
+    part, rows = None, 0
     if link is not None and tuple(link.y.shape) == (B, H, W, spec.ci):
-        key = (spec.kind, B, H, W, spec.ci, spec.co, spec.k, spec.stride, spec.pad, spec.out_pad, -ws.numel())
-        rows = _bn_rows_cache.get(key)
-        if rows is None:
-            rows = _bn_rows_cache[key] = native.load().ctvae_conv_backward_bn_rows(*key[:-1], ws.numel() * 4)
+        rows = max(_geom_query("ctvae_conv_backward_bn_rows", g, ws.numel() * 4), 0)    # (halves the workspace itself)
         if rows > 0:
             part = torch.empty(rows * spec.ci * 2, dtype=torch.float32, device=dy.device)
-        else:
-            rows = 0
     bn = link if part is not None else None
     coef = torch.empty(7 * spec.ci, dtype=torch.float32, device=dy.device) if bn is not None else None   # the finalize rides along
-    sc = in_coef.data_ptr() if in_coef is not None else None
-    sh = in_coef.data_ptr() + 4 * spec.ci if in_coef is not None else None
-    by, bc, bact, bgy = (dy_bn[0].data_ptr(), dy_bn[1].data_ptr(), dy_bn[2], dy_bn[3].data_ptr()) if dy_bn is not None else (None, None, 0, None)
-    native.call("ctvae_conv_backward", spec.kind, x.data_ptr(), dy.data_ptr(), w_param.data_ptr(), gw.data_ptr(), native.ptr(gb),
-                dx.data_ptr(), B, H, W, spec.ci, spec.co, spec.k, spec.stride, spec.pad, spec.out_pad, acc,
-                native.ptr(mask), mask_act, native.ptr(wino_filters),
+    cg, cb, cacc = _bn_commit_args(bn_commit)
+    if coef is None:
+        cg = cb = None        # no rider, nothing commits
+    native.call("ctvae_conv_backward", g[0], x.data_ptr(), dy.data_ptr(), w_param.data_ptr(), gw.data_ptr(), native.ptr(gb),
+                dx.data_ptr(), *g[1:], acc, native.ptr(mask), mask_act, native.ptr(wino_filters),
                 native.ptr(bn.y if bn else None), native.ptr(bn.mean if bn else None), native.ptr(bn.invstd if bn else None),
                 native.ptr(bn.gamma if bn else None), native.ptr(bn.beta if bn else None), bn.act if bn else 0,
-                native.ptr(part), rows, native.ptr(coef),
-                native.ptr(bn_commit[0]) if (bn_commit and coef is not None) else None,
-                native.ptr(bn_commit[1]) if (bn_commit and coef is not None) else None, bn_commit[2] if bn_commit else 0,
-                sc, sh, in_act, by, bc, bact, bgy, ws.data_ptr(), ws.numel() * 4)
+                native.ptr(part), rows, native.ptr(coef), cg, cb, cacc,
+                *_coef_ptrs(in_coef, spec.ci), in_act, *_dy_bn_args(dy_bn), ws.data_ptr(), ws.numel() * 4)
     if bn is not None:
         bn.publish(dx, part, rows, coef)
     return dx
@@ -506,11 +516,9 @@ def conv_backward_raw(x, dy, w_param, b_param, spec: ConvSpec, link=None, mask=N
 
 def wgrad_then_dgrad(x, g, w_param, b_param, spec, need_dgrad, link=None, wino_filters=None, in_coef=None, in_act=ACT_NONE,
                      grad_slices=False):
-    """Weight gradient (accumulated straight into ``.grad``) and data gradient of one layer, on the launch stream.
-    Measured on MI355X: putting the wgrad kernels on a second HIP stream (joined right after dgrad, or once at the
-    end of backward) is SLOWER than back-to-back launches (2.43 vs 2.32 ms/step) -- each GEMM launch already covers
-    every CU, and the fork/join edges cost more than the overlap of prologue/epilogue phases returns.  What does pay is
-    ONE launch for both GEMMs (ctvae_conv_backward / conv_bwd_pair_kernel)."""
+    """Weight gradient (accumulated straight into ``.grad``) and data gradient of one layer, on the launch stream.  Each GEMM
+    launch already covers every CU, so nothing is gained by overlapping the two; what does pay is ONE launch for both GEMMs
+    (ctvae_conv_backward / conv_bwd_pair_kernel)."""
     if need_dgrad:
         return conv_backward_raw(x, g, w_param, b_param, spec, link=link, wino_filters=wino_filters, in_coef=in_coef, in_act=in_act,
                                  grad_slices=grad_slices)
@@ -562,16 +570,9 @@ class LinearToNHWC(Function):
     launch behind it.  Backward is what ConvAct + _ToNHWC did: the gradient goes back to the Linear's own feature order (summing
     the consumer's split-K slices on the way when it arrives as slices), then the Linear's paired backward launch."""
 
-    _ok = {}
-
     @staticmethod
     def supported(B, ci, C, P, device):
-        key = (B, ci, C, P)
-        ok = LinearToNHWC._ok.get(key)
-        if ok is None:
-            ws = native.workspace(device)
-            ok = LinearToNHWC._ok[key] = bool(native.load().ctvae_linear_pixmajor_supported(B, ci, C, P, ws.numel() * 4))
-        return ok
+        return bool(_geom_query("ctvae_linear_pixmajor_supported", (B, ci, C, P), native.workspace(device).numel() * 4))
 
     @staticmethod
     def forward(ctx, x, w, b, spec, C, h, wd):
@@ -748,38 +749,28 @@ class ConvAct(Function):
         """aux: companion rows (see above); returns (y, y_aux) then.  lazy_slices (model code: the ONE consumer of y sums split-K
         slices itself, e.g. GaussianLatent): where the launch splits K, y is an unwritten placeholder and the raw slices (no bias)
         wait in kernels.pop_fwd_slices() for the caller to hang on it."""
-        global _last_act_link, _last_fwd_slices
+        global _last_fwd_slices
         _req_cuda(x, w)
         ctx.link_in = link_of(x)
         ctx.x_slices_ok = bool(getattr(x, "_ctvae_grad_slices_ok", False))
+        ctx.wino_u = None
+        ctx.spec, ctx.w, ctx.b, ctx.has_add = spec, w, b, add is not None
         if lazy_slices and aux is None and add is None and spec.act == ACT_NONE and x.is_contiguous():
             B, H, W_, _ = x.shape
             ws = native.workspace(x.device)
-            key = (spec.kind, B, H, W_, spec.ci, spec.co, spec.k, spec.stride, spec.pad, spec.out_pad, ws.numel(), "fwd-slices")
-            n = _bn_rows_cache.get(key)
-            if n is None:
-                n = _bn_rows_cache[key] = native.load().ctvae_conv_forward_lazy_slices(*key[:10], ws.numel() * 4)
+            g = spec.geom(B, H, W_)
+            n = _geom_query("ctvae_conv_forward_lazy_slices", g, ws.numel() * 4)
             if n > 1:
                 ho, wo = spec.out_hw(H, W_)
                 y = torch.empty((B, ho, wo, spec.co), dtype=torch.float32, device=x.device)
                 slices = torch.empty(n * y.numel(), dtype=torch.float32, device=x.device)
-                native.call("ctvae_conv_forward_lazy", spec.kind, x.data_ptr(), w.data_ptr(), slices.data_ptr(), B, H, W_, spec.ci,
-                            spec.co, spec.k, spec.stride, spec.pad, spec.out_pad, ws.data_ptr(), ws.numel() * 4)
-                ctx.act_in = getattr(x, "_ctvae_act_link", None)
-                ctx.act_out = None
-                ctx.wino_u = None
-                ctx.spec, ctx.w, ctx.b, ctx.has_add = spec, w, b, False
+                native.call("ctvae_conv_forward_lazy", g[0], x.data_ptr(), w.data_ptr(), slices.data_ptr(), *g[1:],
+                            ws.data_ptr(), ws.numel() * 4)
                 ctx.save_for_backward(x, None)
                 _last_fwd_slices = (slices, n, b)
                 return y
-        ctx.act_in = getattr(x, "_ctvae_act_link", None) if x.is_contiguous() else None
-        ctx.act_out = _last_act_link = ActLink(spec.act) if spec.act != ACT_NONE else None
         x = _c(x)
         add_c = _c(add) if add is not None else None
-        ctx.wino_u = None
-        ctx.spec = spec
-        ctx.w, ctx.b = w, b
-        ctx.has_add = add is not None
         if aux is not None:
             if add is not None:
                 raise RuntimeError("ConvAct: companion rows and a residual operand together are not supported")
@@ -810,17 +801,9 @@ class ConvAct(Function):
         spec = ctx.spec
         x, y = ctx.saved_tensors
         g_y = _c(g_y)
-        if spec.act == ACT_NONE or (ctx.act_out is not None and ctx.act_out.take(g_y)):
-            g_pre = g_y                                   # no activation, or its derivative is already in g_y
-        else:
-            g_pre = act_backward_raw(g_y, y, spec.act)
-        if ctx.act_in is not None and ctx.needs_input_grad[0] and ctx.link_in is None:
-            # x is the activated output of the producer and this layer is its only consumer: dgrad * act'(x) in one launch
-            g_x = conv_backward_raw(x, g_pre, ctx.w, ctx.b, spec, mask=x, mask_act=ctx.act_in.act)
-            ctx.act_in.publish_done(g_x)
-        else:
-            g_x = wgrad_then_dgrad(x, g_pre, ctx.w, ctx.b, spec, ctx.needs_input_grad[0], ctx.link_in, ctx.wino_u,
-                                   grad_slices=ctx.x_slices_ok)
+        g_pre = g_y if spec.act == ACT_NONE else act_backward_raw(g_y, y, spec.act)
+        g_x = wgrad_then_dgrad(x, g_pre, ctx.w, ctx.b, spec, ctx.needs_input_grad[0], ctx.link_in, ctx.wino_u,
+                               grad_slices=ctx.x_slices_ok)
         g_add = g_pre if (ctx.has_add and ctx.needs_input_grad[3]) else None
         return g_x, None, None, g_add, None, None, None
 
@@ -877,6 +860,45 @@ class ResBlock(Function):
         return g_x, None, None, None, None, None
 
 
+def _conv_bn_act_forward(x, params, running, training, spec, bn_act, lazy_in, want_a, want_coef):
+    """ctvae_conv_bn_act_forward: y = conv(x, w) + b and the BatchNorm2d (+ activation) behind it.  params = (w, b, gamma,
+    beta); running = (running_mean, running_var, num_batches_tracked); lazy_in = (coef, act) of an input that is read through
+    the previous block's BatchNorm, or None.  want_a: the activated tensor is written; want_coef: the [2][C] scale | shift
+    block is, for a consumer that applies it on load.  Returns y, a, coef, save_mean, save_invstd."""
+    w, b, gamma, beta = params
+    running_mean, running_var, num_batches_tracked = running
+    B, H, W, _ = x.shape
+    ho, wo = spec.out_hw(H, W)
+    C = spec.co
+    y = torch.empty((B, ho, wo, C), dtype=torch.float32, device=x.device)
+    a = torch.empty_like(y) if want_a else None
+    coef = torch.empty(2 * C, dtype=torch.float32, device=x.device) if want_coef else None
+    save_mean = torch.empty(C, dtype=torch.float32, device=x.device)
+    save_invstd = torch.empty(C, dtype=torch.float32, device=x.device)
+    ws = native.workspace(x.device)
+    in_coef, in_act = lazy_in if lazy_in is not None else (None, ACT_NONE)
+    g = spec.geom(B, H, W)
+    native.call("ctvae_conv_bn_act_forward", g[0], x.data_ptr(), w.data_ptr(), native.ptr(b), gamma.data_ptr(),
+                beta.data_ptr(), native.ptr(running_mean), native.ptr(running_var), BN_MOMENTUM, BN_EPS,
+                1 if training else 0, bn_act, y.data_ptr(), native.ptr(a), save_mean.data_ptr(), save_invstd.data_ptr(),
+                native.ptr(coef), native.ptr(num_batches_tracked) if training else None, *g[1:],
+                *_coef_ptrs(in_coef, spec.ci), in_act, ws.data_ptr(), ws.numel() * 4)
+    return y, a, coef, save_mean, save_invstd
+
+
+def _bn_backward(g_a, y, bn, bn_act, g_y, grads, part=None, rows=0, coef_out=None, coef_in=None):
+    """ctvae_bn_backward over y [B,H,W,C].  bn = (gamma, beta, save_mean, save_invstd); grads = (dgamma, dbeta, accumulate).
+    g_y None: the apply pass is left to the weight-gradient kernel, which reads coef_out.  part / rows: the sums the consumer's
+    data gradient emitted; coef_in: the [7][C] block of a finalize that already ran (BNLink.take)."""
+    gamma, beta, save_mean, save_invstd = bn
+    gg, gbt, acc = grads
+    B, H, W, C = y.shape
+    ws = native.workspace(y.device)
+    native.call("ctvae_bn_backward", g_a.data_ptr(), beta.data_ptr(), y.data_ptr(), B * H * W, C, gamma.data_ptr(),
+                save_mean.data_ptr(), save_invstd.data_ptr(), bn_act, native.ptr(g_y), gg.data_ptr(), gbt.data_ptr(), acc,
+                native.ptr(part), rows, native.ptr(coef_out), native.ptr(coef_in), ws.data_ptr(), ws.numel() * 4)
+
+
 class ConvBNAct(Function):
     """a = act(BatchNorm2d(conv(x, w) + b)) with train-mode batch statistics (vanilla_vae.py:25-35,47-75)."""
 
@@ -892,23 +914,9 @@ class ConvBNAct(Function):
         ctx.x_slices_ok = bool(getattr(x, "_ctvae_grad_slices_ok", False))
         lazy_in = getattr(x, "_ctvae_lazy_bn", None) if x.is_contiguous() else None
         x = _c(x)
-        B, H, W, _ = x.shape
-        ho, wo = spec.out_hw(H, W)
-        C = spec.co
-        y = torch.empty((B, ho, wo, C), dtype=torch.float32, device=x.device)
-        a = None if lazy_out else torch.empty_like(y)
-        coef = torch.empty(2 * C, dtype=torch.float32, device=x.device) if lazy_out else None
-        ws = native.workspace(x.device)
-        save_mean = torch.empty(C, dtype=torch.float32, device=x.device)
-        save_invstd = torch.empty(C, dtype=torch.float32, device=x.device)
-        isc = lazy_in[0].data_ptr() if lazy_in is not None else None
-        ish = lazy_in[0].data_ptr() + 4 * spec.ci if lazy_in is not None else None
-        native.call("ctvae_conv_bn_act_forward", spec.kind, x.data_ptr(), w.data_ptr(), native.ptr(b), gamma.data_ptr(),
-                    beta.data_ptr(), native.ptr(running_mean), native.ptr(running_var), BN_MOMENTUM, BN_EPS,
-                    1 if training else 0, bn_act, y.data_ptr(), native.ptr(a), save_mean.data_ptr(), save_invstd.data_ptr(),
-                    native.ptr(coef), native.ptr(num_batches_tracked) if training else None, B, H, W, spec.ci, spec.co, spec.k,
-                    spec.stride, spec.pad, spec.out_pad, isc, ish, lazy_in[1] if lazy_in is not None else ACT_NONE,
-                    ws.data_ptr(), ws.numel() * 4)
+        y, a, coef, save_mean, save_invstd = _conv_bn_act_forward(
+            x, (w, b, gamma, beta), (running_mean, running_var, num_batches_tracked), training, spec, bn_act, lazy_in,
+            want_a=not lazy_out, want_coef=lazy_out)
         ctx.spec, ctx.bn_act, ctx.training = spec, bn_act, training
         ctx.params = (w, b, gamma, beta)
         ctx.lazy_in = lazy_in
@@ -928,14 +936,8 @@ class ConvBNAct(Function):
         w, b, gamma, beta = ctx.params
         x, y, save_mean, save_invstd = ctx.saved_tensors
         g_a = _c(g_a)
-        B, H, W, C = y.shape
-        in_coef, in_act = (ctx.lazy_in[0], ctx.lazy_in[1]) if ctx.lazy_in is not None else (None, ACT_NONE)
-        ws = native.workspace(x.device)
-        gg, accg = grad_target(gamma)
-        gbt, accb = grad_target(beta)
-        if accg != accb:
-            (gg if accg == 0 else gbt).zero_()
-            accg = 1
+        in_coef, in_act = ctx.lazy_in if ctx.lazy_in is not None else (None, ACT_NONE)
+        gg, gbt, accg = _grad_targets(gamma, beta)
         lazy = ctx.link_out.take_lazy(g_a) if ctx.link_out is not None else None
         if lazy is not None:
             # g_a was never materialised: the consumer's split-K slices are summed here, with the sums, the finalize and the apply
@@ -943,49 +945,31 @@ class ConvBNAct(Function):
             native.call("ctvae_bn_backward_fused", lazy[0].data_ptr(), lazy[1], *lazy[2], y.data_ptr(), gamma.data_ptr(),
                         beta.data_ptr(), save_mean.data_ptr(), save_invstd.data_ptr(), ctx.bn_act, g_y.data_ptr(), gg.data_ptr(),
                         gbt.data_ptr(), accg)
-            g_x = wgrad_then_dgrad(x, g_y, w, b, spec, ctx.needs_input_grad[0], ctx.link_in, in_coef=in_coef, in_act=in_act,
-                                   grad_slices=ctx.x_slices_ok)
-            return (g_x,) + (None,) * 11
-        part, rows, coef = ctx.link_out.take(g_a) if ctx.link_out is not None else (None, 0, None)
-        if coef is not None:
-            part, rows = None, 0         # finalized by the consumer's finishing launch: apply + commit only
-            if not ctx.needs_input_grad[0] and wgrad_bn_apply_mode(spec, x.shape[0], x.shape[1], x.shape[2]) == 2:
-                # the first layer of the encoder: no data gradient follows, so g_y is only the weight gradient's operand -- formed
-                # on load from (g_a, y, coef); the apply launch and its 33 MB output are not needed
-                conv_wgrad_raw(x, g_a, w, b, spec, dy_bn=(y, coef, ctx.bn_act, None), bn_commit=(gg, gbt, accg))
-                return (None,) * 12
-        g_y = torch.empty_like(y)
-        native.call("ctvae_bn_backward", g_a.data_ptr(), beta.data_ptr(), y.data_ptr(), B * H * W, C, gamma.data_ptr(),
-                    save_mean.data_ptr(), save_invstd.data_ptr(), ctx.bn_act, g_y.data_ptr(), gg.data_ptr(), gbt.data_ptr(),
-                    accg, native.ptr(part), rows, None, native.ptr(coef), ws.data_ptr(), ws.numel() * 4)
+        else:
+            part, rows, coef = ctx.link_out.take(g_a) if ctx.link_out is not None else (None, 0, None)
+            if coef is not None:
+                part, rows = None, 0         # finalized by the consumer's finishing launch: apply + commit only
+                if not ctx.needs_input_grad[0] and wgrad_bn_apply_mode(spec, x.shape[0], x.shape[1], x.shape[2]) == 2:
+                    # the first layer of the encoder: no data gradient follows, so g_y is only the weight gradient's operand --
+                    # formed on load from (g_a, y, coef); the apply launch and its 33 MB output are not needed
+                    conv_wgrad_raw(x, g_a, w, b, spec, dy_bn=(y, coef, ctx.bn_act, None), bn_commit=(gg, gbt, accg))
+                    return (None,) * 12
+            g_y = torch.empty_like(y)
+            _bn_backward(g_a, y, (gamma, beta, save_mean, save_invstd), ctx.bn_act, g_y, (gg, gbt, accg), part, rows, coef_in=coef)
         g_x = wgrad_then_dgrad(x, g_y, w, b, spec, ctx.needs_input_grad[0], ctx.link_in, in_coef=in_coef, in_act=in_act,
                                grad_slices=ctx.x_slices_ok)
         return (g_x,) + (None,) * 11
 
 
-_xform_ok_cache = {}
-
-
 def input_transform_supported(spec: ConvSpec, B, H, W) -> bool:
     """Can this layer apply the previous block's BatchNorm + activation while loading (ctvae_conv_forward in_scale)?"""
-    key = (spec.kind, B, H, W, spec.ci, spec.co, spec.k, spec.stride, spec.pad, spec.out_pad)
-    ok = _xform_ok_cache.get(key)
-    if ok is None:
-        ok = _xform_ok_cache[key] = bool(native.load().ctvae_conv_input_transform_supported(*key))
-    return ok
-
-
-_wgrad_bn_ok_cache = {}
+    return bool(_geom_query("ctvae_conv_input_transform_supported", spec.geom(B, H, W)))
 
 
 def wgrad_bn_apply_mode(spec: ConvSpec, B, H, W) -> int:
     """ctvae_conv_wgrad_bn_apply_supported: 0 no; 1 the weight-gradient kernel applies the BatchNorm backward on load and writes
     g_y for the data gradient (final_layer.0); 2 it applies it on load and nothing is written (encoder.0: no data gradient)."""
-    key = (spec.kind, B, H, W, spec.ci, spec.co, spec.k, spec.stride, spec.pad, spec.out_pad)
-    mode = _wgrad_bn_ok_cache.get(key)
-    if mode is None:
-        mode = _wgrad_bn_ok_cache[key] = int(native.load().ctvae_conv_wgrad_bn_apply_supported(*key))
-    return mode
+    return int(_geom_query("ctvae_conv_wgrad_bn_apply_supported", spec.geom(B, H, W)))
 
 
 def wgrad_bn_apply_supported(spec: ConvSpec, B, H, W) -> bool:
@@ -1007,22 +991,9 @@ class ConvBNActConvAct(Function):
         ctx.link_in = link_of(x)
         lazy_in = ctx.lazy_in = getattr(x, "_ctvae_lazy_bn", None) if x.is_contiguous() else None
         x = _c(x)
-        B, H, W, _ = x.shape
-        ho, wo = spec1.out_hw(H, W)
-        C = spec1.co
-        y1 = torch.empty((B, ho, wo, C), dtype=torch.float32, device=x.device)
-        coef = torch.empty(2 * C, dtype=torch.float32, device=x.device)
-        save_mean = torch.empty(C, dtype=torch.float32, device=x.device)
-        save_invstd = torch.empty(C, dtype=torch.float32, device=x.device)
-        ws = native.workspace(x.device)
-        native.call("ctvae_conv_bn_act_forward", spec1.kind, x.data_ptr(), w1.data_ptr(), native.ptr(b1), gamma.data_ptr(),
-                    beta.data_ptr(), native.ptr(running_mean), native.ptr(running_var), BN_MOMENTUM, BN_EPS,
-                    1 if training else 0, bn_act, y1.data_ptr(), None, save_mean.data_ptr(), save_invstd.data_ptr(),
-                    coef.data_ptr(), native.ptr(num_batches_tracked) if training else None, B, H, W, spec1.ci, spec1.co,
-                    spec1.k, spec1.stride, spec1.pad, spec1.out_pad,
-                    lazy_in[0].data_ptr() if lazy_in is not None else None,
-                    lazy_in[0].data_ptr() + 4 * spec1.ci if lazy_in is not None else None,
-                    lazy_in[1] if lazy_in is not None else ACT_NONE, ws.data_ptr(), ws.numel() * 4)
+        y1, _, coef, save_mean, save_invstd = _conv_bn_act_forward(
+            x, (w1, b1, gamma, beta), (running_mean, running_var, num_batches_tracked), training, spec1, bn_act, lazy_in,
+            want_a=False, want_coef=True)
         r = conv_forward_raw(y1, w2, b2, spec2, in_coef=coef, in_act=bn_act)
         ctx.act_out = offer_out_act_link(r, spec2.act) if (training and spec2.act != ACT_NONE) else None
         ctx.specs, ctx.bn_act, ctx.training = (spec1, spec2), bn_act, training
@@ -1042,35 +1013,27 @@ class ConvBNActConvAct(Function):
             g_pre = g_r                                          # the loss's backward pass already applied act'(r)
         else:
             g_pre = act_backward_raw(g_r, r, spec2.act) if spec2.act != ACT_NONE else g_r
-        B, H, W, C = y1.shape
+        C = y1.shape[3]
+        bn = (gamma, beta, save_mean, save_invstd)
         link = BNLink(y1, save_mean, save_invstd, gamma, beta, ctx.bn_act)
-        ws = native.workspace(x.device)
-        gg, accg = grad_target(gamma)
-        gbt, accb = grad_target(beta)
-        if accg != accb:
-            (gg if accg == 0 else gbt).zero_()
-            accg = 1
+        grads = _grad_targets(gamma, beta)
         lazy = wgrad_bn_apply_supported(spec1, x.shape[0], x.shape[1], x.shape[2])
         g_y = torch.empty_like(y1)
         # conv2's weight gradient, its data gradient (which emits the BatchNorm's backward sums) and the BatchNorm's
         # finalize in one call: the finalize rides in the slab-reduction launch (the link is local to this node, so the
         # rider commits d gamma / d beta itself when no apply launch follows)
         g_a = conv_backward_raw(y1, g_pre, w2, b2, spec2, link=link, in_coef=coef, in_act=ctx.bn_act,
-                                bn_commit=(gg, gbt, accg) if lazy else None)
+                                bn_commit=grads if lazy else None)
         part, rows, c7 = link.take(g_a)
         if c7 is None:
             # the rider declined (no sums from the data gradient): the BatchNorm's own launch finalizes
             bcoef = torch.empty(5 * C, dtype=torch.float32, device=x.device) if lazy else None
-            native.call("ctvae_bn_backward", g_a.data_ptr(), beta.data_ptr(), y1.data_ptr(), B * H * W, C, gamma.data_ptr(),
-                        save_mean.data_ptr(), save_invstd.data_ptr(), ctx.bn_act, None if lazy else g_y.data_ptr(), gg.data_ptr(),
-                        gbt.data_ptr(), accg, native.ptr(part), rows, native.ptr(bcoef), None, ws.data_ptr(), ws.numel() * 4)
+            _bn_backward(g_a, y1, bn, ctx.bn_act, None if lazy else g_y, grads, part, rows, coef_out=bcoef)
         elif lazy:
             bcoef = c7                                           # rows 0-4 are the coefficients the weight-gradient kernel reads
         else:
-            native.call("ctvae_bn_backward", g_a.data_ptr(), beta.data_ptr(), y1.data_ptr(), B * H * W, C, gamma.data_ptr(),
-                        save_mean.data_ptr(), save_invstd.data_ptr(), ctx.bn_act, g_y.data_ptr(), gg.data_ptr(), gbt.data_ptr(),
-                        accg, None, 0, None, c7.data_ptr(), ws.data_ptr(), ws.numel() * 4)
-        in_coef, in_act = (ctx.lazy_in[0], ctx.lazy_in[1]) if ctx.lazy_in is not None else (None, ACT_NONE)
+            _bn_backward(g_a, y1, bn, ctx.bn_act, g_y, grads, coef_in=c7)
+        in_coef, in_act = ctx.lazy_in if ctx.lazy_in is not None else (None, ACT_NONE)
         if lazy:
             # the weight-gradient kernel turns g_a into g_y on load and leaves g_y behind for the data gradient
             if ctx.needs_input_grad[0]:

@@ -31,7 +31,6 @@ SIGNATURES = {
     "ctvae_bn_backward_fused": [_fp, _i] + [_i] * 10 + [_fp, _fp, _fp, _fp, _fp, _i, _fp, _fp, _fp, _i, _vp],
     "ctvae_bn_forward": [_fp, _i, _i, _fp, _fp, _fp, _fp, _f, _f, _i, _i, _fp, _fp, _fp, _fp, _fp, _sz, _vp],
     "ctvae_bn_backward": [_fp, _fp, _fp, _i, _i, _fp, _fp, _fp, _i, _fp, _fp, _fp, _i, _fp, _i, _fp, _fp, _fp, _sz, _vp],
-    "ctvae_conv_dgrad_bn": [_i, _fp, _fp, _fp, _fp, _i, _fp] + [_i] * 9 + [_fp, _fp, _fp, _fp, _fp, _i, _fp, _i, _fp, _sz, _vp],
     "ctvae_permute": [_fp, _fp, _i, _i, _i, _i, _vp],
     "ctvae_crop_resize_u8": [_fp, _fp, _fp, _i, _i, _i, _i, _i, _i, _vp],
     "ctvae_gat_score": [_i, _fp, _fp, _fp, _fp, _fp, _fp, _i, _i, _i, _i, _f, _vp],
@@ -119,7 +118,6 @@ _RESTYPES = {
     "ctvae_prof_enable": None,
     "ctvae_prof_calibrate": None,
     "ctvae_prof_report": _c.c_size_t,
-    "ctvae_conv_dgrad_bn_rows": _c.c_int,
     "ctvae_conv_backward_bn_rows": _c.c_int,
     "ctvae_conv_backward_lazy_slices": _c.c_int,
     "ctvae_conv_forward_lazy_slices": _c.c_int,
@@ -166,7 +164,6 @@ def load():
         fn.argtypes = {"ctvae_error_string": [_c.c_int], "ctvae_prof_enable": [_c.c_int],
                        "ctvae_prof_calibrate": [_c.c_void_p, _c.c_int],
                        "ctvae_prof_report": [_c.c_char_p, _c.c_size_t],
-                       "ctvae_conv_dgrad_bn_rows": [_c.c_int] * 10 + [_c.c_size_t],
                        "ctvae_conv_backward_bn_rows": [_c.c_int] * 10 + [_c.c_size_t],
                        "ctvae_conv_backward_lazy_slices": [_c.c_int] * 11 + [_c.c_size_t],
                        "ctvae_conv_forward_lazy_slices": [_c.c_int] * 10 + [_c.c_size_t],

@@ -105,20 +105,6 @@ int ctvae_conv_dgrad(int kind, const float* dy, const float* w, const float* add
                      float* dx, int B, int H, int W, int Ci, int Co, int k, int stride, int pad, int out_pad,
                      const float* wino_filters, float* ws, size_t ws_bytes, void* stream);
 
-/* ctvae_conv_dgrad whose result dx is the gradient w.r.t. a = act(BN(y)), the output of a train-mode BatchNorm2d
- * (+activation) that fed this layer (autograd of vanilla_vae.py:28-31 chained into the next block).  The epilogue
- * also emits, per output tile, that BatchNorm's backward sums (sum g', sum g'*xhat; g' = dx*act'(gamma*xhat+beta),
- * xhat = (y-mean)*invstd) into bn_part [bn_part_rows][Ci][2], which ctvae_bn_backward takes as part_in: one pass
- * over (g_a, y) less.  bn_part_rows must equal ctvae_conv_dgrad_bn_rows() of the same geometry and workspace; that
- * function returns 0 when the launch configuration cannot fuse (split-K), then use ctvae_conv_dgrad. */
-int ctvae_conv_dgrad_bn_rows(int kind, int B, int H, int W, int Ci, int Co, int k, int stride, int pad, int out_pad,
-                             size_t ws_bytes);
-int ctvae_conv_dgrad_bn(int kind, const float* dy, const float* w, const float* add, const float* mask, int mask_act,
-                        float* dx, int B, int H, int W, int Ci, int Co, int k, int stride, int pad, int out_pad,
-                        const float* bn_y, const float* bn_mean, const float* bn_invstd, const float* bn_gamma,
-                        const float* bn_beta, int bn_act, float* bn_part, int bn_part_rows, float* ws, size_t ws_bytes,
-                        void* stream);
-
 /* dw (+)= wgrad(x, dy);  dbias (+)= sum over pixels of dy (dbias may be NULL).  Deterministic two-pass. */
 /* in_scale/in_shift/in_act: as ctvae_conv_forward (x is then the raw BatchNorm input y of the previous block). */
 int ctvae_conv_wgrad(int kind, const float* x, const float* dy, float* dw, float* dbias, int B, int H, int W, int Ci,
@@ -127,12 +113,16 @@ int ctvae_conv_wgrad(int kind, const float* x, const float* dy, float* dw, float
                      float* gy_out, float* bn_dgamma, float* bn_dbeta, int bn_accumulate, float* ws, size_t ws_bytes,
                      void* stream);
 /* A layer's whole backward pass in one call: weight (+ bias) gradient as ctvae_conv_wgrad(x, dy -> dw, dbias) and data
- * gradient as ctvae_conv_dgrad / ctvae_conv_dgrad_bn(dy, w -> dx; optional mask, Winograd filters, fused BatchNorm-backward
- * sums).  The two GEMMs are independent; when both take their 64x64 tile kernels they are issued as ONE launch
- * (conv_bwd_pair_kernel: one kernel boundary instead of two, the weight-gradient workgroups start while the data
- * gradient's stores drain), otherwise as the separate launches of those entry points.  Each GEMM uses one half of ws:
- * query bn_part_rows with ctvae_conv_backward_bn_rows (0: this layer's data gradient cannot emit the sums).
- * bn_part == NULL: no BatchNorm fusion.
+ * gradient as ctvae_conv_dgrad(dy, w -> dx; optional mask, Winograd filters).  The two GEMMs are independent; when both
+ * take their 64x64 tile kernels they are issued as ONE launch (conv_bwd_pair_kernel: one kernel boundary instead of two,
+ * the weight-gradient workgroups start while the data gradient's stores drain), otherwise as the separate launches of
+ * those entry points.  Each GEMM uses one half of ws.
+ * bn_part [bn_part_rows][Ci][2] (with bn_y / bn_mean / bn_invstd / bn_gamma / bn_beta / bn_act; NULL: no BatchNorm fusion):
+ * dx is the gradient w.r.t. a = act(BN(y)), the output of a train-mode BatchNorm2d (+ activation) that fed this layer (autograd of
+ * vanilla_vae.py:28-31 chained into the next block), and the data gradient's epilogue also emits, per output tile, that
+ * BatchNorm's backward sums (sum g', sum g'*xhat; g' = dx*act'(gamma*xhat+beta), xhat = (y-mean)*invstd), which
+ * ctvae_bn_backward takes as part_in: one pass over (g_a, y) less.  bn_part_rows must equal ctvae_conv_backward_bn_rows() of
+ * the same geometry and workspace; that function returns 0 when this layer's data gradient cannot emit the sums (split-K).
  * bn_coef_out [7][Ci] (may be NULL; needs bn_part): that BatchNorm's backward FINALIZE rides as extra blocks of this call's
  * finishing launch (the slab reduction) -- rows 0-4 = k1,k2,k3,scale,shift as ctvae_bn_backward's coef_out, rows 5,6 = this
  * pass's d gamma, d beta.  ctvae_bn_backward(coef_in = bn_coef_out) then only applies and commits them: one launch less per
@@ -202,7 +192,7 @@ int ctvae_bn_forward(const float* y, int R, int C, const float* gamma, const flo
                      void* stream);
 /* g_y from g_a (grad wrt the activated output); the activation derivative is re-derived from the sign of
  * gamma*invstd*(y-mean)+beta, so the activated tensor is not read; dgamma/dbeta (+)= ...
- * part_in/part_rows: the per-tile sums a ctvae_conv_dgrad_bn launch emitted for this g_a (NULL/0: computed here).
+ * part_in/part_rows: the per-tile sums ctvae_conv_backward left in bn_part for this g_a (NULL/0: computed here).
  * coef_out [5][C] (may be NULL): k1,k2,k3,scale,shift of g_y = k1*g_a*act'(y*scale+shift) + k2*y + k3; with
  * g_y == NULL the apply pass is left to ctvae_conv_wgrad (dy_bn_*).
  * coef_in [7][C] (NULL normally; excludes part_in / coef_out, needs g_y): the finalize already ran as a rider of

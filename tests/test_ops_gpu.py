@@ -397,7 +397,7 @@ def test_adam_matches_torch(K):
 @pytest.mark.parametrize("transposed,B,H", [(False, 32, 32), (True, 128, 16), (False, 4, 16), (True, 3, 8)])
 def test_bn_backward_sums_fused_into_dgrad(K, transposed, B, H):
     """Two chained ConvBNAct blocks: the second block's dgrad emits the first BatchNorm's backward sums
-    (ctvae_conv_dgrad_bn).  All gradients against torch autograd, and the fused path must really have run."""
+    (ctvae_conv_backward bn_part).  All gradients against torch autograd, and the fused path must really have run."""
     from ctvae_amd import native
     from ctvae_amd.models import blocks
     g = torch.Generator().manual_seed(31 + B)
@@ -462,7 +462,7 @@ def test_bn_backward_sums_fused_into_dgrad(K, transposed, B, H):
     ws = native.workspace(dev)
     Hin = H * 2 if transposed else H          # input size of the second block
     # the plan of the call backward really makes: the paired launch (ctvae_conv_backward) splits K later than a lone data gradient
-    rows_of = native.load().ctvae_conv_backward_bn_rows if K._PAIR else native.load().ctvae_conv_dgrad_bn_rows
+    rows_of = native.load().ctvae_conv_backward_bn_rows
     rows = rows_of(kind, B, Hin, Hin, C1, C2, 3, s, 1, op, ws.numel() * 4)
     if B >= 32:
         assert rows > 0, "this shape is expected to take the fused path"
