@@ -152,6 +152,11 @@ size_t dip_state_floats(int B, int D);
 int launch_dip_forward(const float* mu, long mu_rs, const float* lv, long lv_rs, int B, int D, float l_diag, float l_off,
                        float* state, hipStream_t st);
 int launch_dip_backward(const float* state, const float* go, float* g_mu, float* g_lv, int B, int D, hipStream_t st);
+int launch_column_moments(const float* z, int N, int L, float* mean, float* var, float* mn, float* mx, hipStream_t st);
+int launch_mi_matrix(const float* z, const float* lo, const float* hi, const int32_t* factors, const int32_t* sizes, int N, int L,
+                     int F, float* mi, uint8_t* bins, hipStream_t st);
+int launch_group_var_argmin(const float* z, const float* gvar, const uint8_t* active, int G, int B, int L, int32_t* arg, float* val,
+                            hipStream_t st);
 int launch_loss_forward(const float* r, const float* x, long n, const float* mu, long mu_rs, const float* lv, long lv_rs,
                         int B, int L, float M_N, const float* extra, float* out4, float* ws, size_t ws_bytes,
                         hipStream_t st, float logcosh_alpha, float* g_r = nullptr, float* g_mu = nullptr, float* g_lv = nullptr,
@@ -1002,6 +1007,23 @@ int ctvae_dip_forward(const float* mu, long mu_rs, const float* logvar, long lv_
 int ctvae_dip_backward(const float* state, const float* g_dip, float* g_mu, float* g_logvar, int B, int D, void* stream) {
   if (!state || !g_dip || !g_mu || !g_logvar || B <= 0 || D <= 0) return kErrBadArg;
   return launch_dip_backward(state, g_dip, g_mu, g_logvar, B, D, (hipStream_t)stream);
+}
+
+int ctvae_column_moments(const float* z, int N, int L, float* mean, float* var, float* min, float* max, void* stream) {
+  if (!z || !mean || !var || !min || !max) return kErrBadArg;
+  return launch_column_moments(z, N, L, mean, var, min, max, (hipStream_t)stream);
+}
+
+int ctvae_mi_matrix(const float* z, const float* lo, const float* hi, const int32_t* factors, const int32_t* sizes, int N, int L,
+                    int F, float* mi, uint8_t* bins, void* stream) {
+  if (!z || !lo || !hi || !factors || !sizes || !mi) return kErrBadArg;
+  return launch_mi_matrix(z, lo, hi, factors, sizes, N, L, F, mi, bins, (hipStream_t)stream);
+}
+
+int ctvae_group_var_argmin(const float* z, const float* global_var, const uint8_t* active, int G, int B, int L, int32_t* arg,
+                           float* val, void* stream) {
+  if (!z || !global_var || !active || !arg || !val) return kErrBadArg;
+  return launch_group_var_argmin(z, global_var, active, G, B, L, arg, val, (hipStream_t)stream);
 }
 
 size_t ctvae_adam_state_floats(void) { return adam_state_floats(); }

@@ -7,6 +7,11 @@ over ``model.parameters()`` or ``getattr(model, update_parameters).parameters()`
 (``gradient_clip_val`` / ``gradient_clip_algorithm``, see optim.py) in front of the step.  What changes is the
 machinery: one flat fused Adam launch, one bucketed RCCL all-reduce, and scalars fetched with ONE device
 -> host copy every ``log_every`` steps instead of one ``.item()`` sync per key per step (experiment.py:95-96).
+
+``val_metric`` (a ``metrics.MetricSet``): the reference recomputes the disentanglement metrics inside EVERY validation batch
+and lets Lightning average the copies (experiment.py:72-74).  That is a cost, not a semantic -- the metric does not read the
+batch -- so ``fit()`` computes it ONCE per validation epoch, after the validation batches, on rank 0 only and without a
+collective, seeded from ``manual_seed`` and the epoch; the results join the epoch record and the JSONL log under ``val_``.
 """
 import json
 import sys
@@ -104,7 +109,8 @@ class _GraphedTrainStep:
 class VAEXperiment:
 
     def __init__(self, vae_model, params: dict, ddp: GradBucketAllReduce = None, log_every: int = 50, log_file=None,
-                 gradient_clip_val=None, gradient_clip_algorithm=None):
+                 gradient_clip_val=None, gradient_clip_algorithm=None, val_metric=None):
+        self.val_metric = val_metric
         self.gradient_clip_val, self.gradient_clip_algorithm = clip_settings(gradient_clip_val, gradient_clip_algorithm)
         self.model = vae_model
         self.params = params
@@ -148,6 +154,19 @@ class VAEXperiment:
         x = x.to(next(self.model.parameters()).device)
         x = self.model.encode(x)[0]
         return x.reshape(x.size(0), -1)
+
+    def validation_metrics(self, epoch: int) -> dict:
+        """The ``val_metric`` results of one validation epoch under the ``val_`` prefix (also one JSONL line); {} without a
+        metric or off rank 0.  The metric's own generator is seeded per epoch; no torch generator and no model state moves."""
+        rank0 = self.ddp is None or not torch.distributed.is_initialized() or torch.distributed.get_rank() == 0
+        if self.val_metric is None or not rank0:
+            return {}
+        seed = int(self.params.get('manual_seed', 0) or 0) * 1_000_003 + int(epoch)
+        res = {"val_" + k: v for k, v in self.val_metric.compute(self.metric_func, model=self.model, seed=seed).items()}
+        if self.log_file is not None:
+            self.log_file.write(json.dumps({**res, "step": self.global_step}) + "\n")
+            self.log_file.flush()
+        return res
 
     def log_all(self, losses: dict, batch_size, validation: bool = False, force: bool = False):
         """Scalar tensors only (strings / images are dropped like experiment.py:93-106); one fused all-reduce over
@@ -275,6 +294,7 @@ class VAEXperiment:
                             sums[k] = sums.get(k, 0.0) + v
                     cnt += 1
                 rec.update({k: v / max(cnt, 1) for k, v in sums.items()})
+                rec.update(self.validation_metrics(epoch))
             history.append(rec)
             if on_epoch_end is not None:
                 on_epoch_end(epoch, rec)

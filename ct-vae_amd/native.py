@@ -103,6 +103,9 @@ SIGNATURES = {
     "ctvae_mmd_forward": [_fp, _fp, _i, _i, _i, _f, _f, _f, _f, _f, _fp, _fp, _fp, _sz, _vp],
     "ctvae_dip_forward": [_fp, _l, _fp, _l, _i, _i, _f, _f, _fp, _vp],
     "ctvae_dip_backward": [_fp, _fp, _fp, _fp, _i, _i, _vp],
+    "ctvae_column_moments": [_fp, _i, _i, _fp, _fp, _fp, _fp, _vp],
+    "ctvae_mi_matrix": [_fp, _fp, _fp, _fp, _fp, _i, _i, _i, _fp, _fp, _vp],
+    "ctvae_group_var_argmin": [_fp, _fp, _fp, _i, _i, _i, _fp, _fp, _vp],
     "ctvae_adam_step": [_fp, _fp, _fp, _fp, _fp, _l, _f, _vp],
     "ctvae_adam_step_clipped": [_fp, _fp, _fp, _fp, _fp, _l, _f, _i, _f, _fp, _fp, _vp],
     "ctvae_mssim_forward": [_fp, _fp, _fp, _fp, _fp, _fp, _fp, _i, _i, _i, _i, _vp],

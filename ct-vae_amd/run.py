@@ -9,6 +9,8 @@ so they interchange with the reference's (run.py:85-97), plus a ``trainer`` entr
 step, random streams) for ``trainer_params.resume_from_checkpoint`` without ``load_weights_only`` (run.py:85-101: full resume).
 ``trainer_params.gradient_clip_val`` / ``gradient_clip_algorithm`` clip the gradients before every optimizer step as the
 Lightning Trainer does (configs/gammavae.yaml); without them the step is unchanged.
+``exp_params.metrics`` (run.py:64-76; "MIG", "FactorVaeScore") with ``data_params.hbm_factor_sizes`` (the sizes of the
+ground-truth factor grid the ``hbm_images`` rows enumerate row-major) adds the disentanglement metrics to every validation epoch.
 """
 import argparse
 import json
@@ -129,6 +131,26 @@ class HbmData:
         return self._loader("test", self.p["val_batch_size"], False)
 
 
+def build_val_metric(config, data):
+    """``exp_params.metrics`` -> a MetricSet over the whole store (the reference hands it ``_full_data``), sized as run.py:72-76;
+    None without the key.  A metric that cannot run is a SystemExit with the reason."""
+    names = config['exp_params'].get('metrics')
+    if not names:
+        return None
+    from . import metrics as M
+    dp = config['data_params']
+    if not isinstance(data, HbmData):
+        raise SystemExit("exp_params.metrics needs ground-truth factors: synthetic data has none (set data_params.hbm_images)")
+    if not dp.get('hbm_factor_sizes'):
+        raise SystemExit("exp_params.metrics needs data_params.hbm_factor_sizes (the sizes of the factor grid hbm_images enumerates)")
+    try:
+        dataset = M.FactorData(data.store, M.FactorGrid(dp['hbm_factor_sizes']))
+        return M.MetricSet(list(names), dataset, batch_size=dp['val_batch_size'], num_train=dp['train_batch_size'] * 20,
+                           num_test=dp['train_batch_size'] * 10, seed=config['exp_params'].get('manual_seed', 0) or 0)
+    except ValueError as e:
+        raise SystemExit(f"exp_params.metrics: {e}")
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser(description='MI355X runner for the ct-vae models')
     ap.add_argument('--config', '-c', dest="filename", metavar='FILE', default='configs/vae.yaml')
@@ -175,6 +197,8 @@ def main(argv=None):
         data = HbmData(config['data_params'], mp, dev, rank, world, seed)
     else:
         data = SyntheticData(config['data_params'], mp, dev, rank, world, args.steps_per_epoch, seed)
+
+    exp.val_metric = build_val_metric(config, data)
 
     start_epoch = 0
     if ckpt is not None and not weights_only:

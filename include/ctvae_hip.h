@@ -524,6 +524,24 @@ int ctvae_dip_forward(const float* mu, long mu_row_stride, const float* logvar, 
                       float lambda_diag, float lambda_offdiag, float* state, void* stream);
 int ctvae_dip_backward(const float* state, const float* g_dip, float* g_mu, float* g_logvar, int B, int D, void* stream);
 
+/* Disentanglement metrics (metrics.py) over a contiguous row-major f32 code matrix z [N][L]: 2 <= N <= 65535, 1 <= L <= 16384.
+ * Anything out of range is a bad argument (-22) and launches nothing.
+ * ctvae_column_moments: per column the mean, the unbiased variance (ddof = 1; f32: Welford mean merged pairwise, then sum (x - mean)^2), and the exact
+ * minimum and maximum.
+ * ctvae_mi_matrix: mi[l][f] = mutual information in nats between the 20-bin discretisation of column l and factor f, for
+ * factors [N][F] (device, value of factor f in 0 .. sizes[f]-1) and sizes[F] (HOST memory: checked before the launch;
+ * 1 <= F <= 16, 2 <= sizes[f] <= 256).  The bin of x is the number of k in 0..19 with lo + k*((hi - lo)/20) <= x, every
+ * operation rounded to f32 on its own: np.digitize(x, np.histogram(x, 20)[1][:-1]) with lo / hi the column's minimum / maximum
+ * (1..20; x = hi lands in 20; hi == lo is widened to lo - 0.5, hi + 0.5).  bins [N][L] (uint8) receives the bins when non-NULL.
+ * ctvae_group_var_argmin: z [G][B][L] (B >= 2); per group g the active column (active[l] != 0) with the smallest
+ * var_B(z[g][:, l]) / global_var[l] (unbiased variance; ties go to the lowest column): arg[g] its column index, val[g] the ratio
+ * (-1 and +inf when no column is active). */
+int ctvae_column_moments(const float* z, int N, int L, float* mean, float* var, float* min, float* max, void* stream);
+int ctvae_mi_matrix(const float* z, const float* lo, const float* hi, const int32_t* factors, const int32_t* sizes, int N, int L,
+                    int F, float* mi, uint8_t* bins, void* stream);
+int ctvae_group_var_argmin(const float* z, const float* global_var, const uint8_t* active, int G, int B, int L, int32_t* arg,
+                           float* val, void* stream);
+
 /* MSSIMVAE's reconstruction loss (mssim_vae.py:182-279): 1 - prod_{i<4} (mcs_i^w_i * mssim_4^w_4) over five levels of SSIM with the
  * reference's 11-tap window (2x2 average pooling between levels), for NHWC pictures a (the reconstruction) and b [B,64,64,C].
  * window [11] and weights [5]: HOST arrays (the window as the reference builds it: exp(+(x-5)^2 / 4.5), normalised).
