@@ -157,6 +157,9 @@ int launch_mi_matrix(const float* z, const float* lo, const float* hi, const int
                      int F, float* mi, uint8_t* bins, hipStream_t st);
 int launch_group_var_argmin(const float* z, const float* gvar, const uint8_t* active, int G, int B, int L, int32_t* arg, float* val,
                             hipStream_t st);
+int launch_image_grid_u8(const float* x, long sN, long sC, long sH, long sW, int N, int C, int H, int W, int nrow, int pad,
+                         int normalize, int has_range, float lo, float hi, float pad_value, int scanlines, uint8_t* out,
+                         size_t out_bytes, float* ws, size_t ws_bytes, hipStream_t st);
 int launch_loss_forward(const float* r, const float* x, long n, const float* mu, long mu_rs, const float* lv, long lv_rs,
                         int B, int L, float M_N, const float* extra, float* out4, float* ws, size_t ws_bytes,
                         hipStream_t st, float logcosh_alpha, float* g_r = nullptr, float* g_mu = nullptr, float* g_lv = nullptr,
@@ -1024,6 +1027,13 @@ int ctvae_group_var_argmin(const float* z, const float* global_var, const uint8_
                            float* val, void* stream) {
   if (!z || !global_var || !active || !arg || !val) return kErrBadArg;
   return launch_group_var_argmin(z, global_var, active, G, B, L, arg, val, (hipStream_t)stream);
+}
+
+int ctvae_image_grid_u8(const float* x, long stride_n, long stride_c, long stride_h, long stride_w, int N, int C, int H, int W,
+                        int nrow, int padding, int normalize, int has_range, float range_lo, float range_hi, float pad_value,
+                        int scanlines, uint8_t* out, size_t out_bytes, float* workspace, size_t workspace_bytes, void* stream) {
+  return launch_image_grid_u8(x, stride_n, stride_c, stride_h, stride_w, N, C, H, W, nrow, padding, normalize, has_range, range_lo,
+                              range_hi, pad_value, scanlines, out, out_bytes, workspace, workspace_bytes, (hipStream_t)stream);
 }
 
 size_t ctvae_adam_state_floats(void) { return adam_state_floats(); }

@@ -12,15 +12,31 @@ machinery: one flat fused Adam launch, one bucketed RCCL all-reduce, and scalars
 and lets Lightning average the copies (experiment.py:72-74).  That is a cost, not a semantic -- the metric does not read the
 batch -- so ``fit()`` computes it ONCE per validation epoch, after the validation batches, on rank 0 only and without a
 collective, seeded from ``manual_seed`` and the epoch; the results join the epoch record and the JSONL log under ``val_``.
+
+``val_sampling`` with a ``sample_dir`` (the reference's ``sample_images``, experiment.py:114-150, which Lightning calls at the end
+of every validation epoch): ``fit(..., test_batches=...)`` then writes three PNG grids per epoch from the FIRST test batch --
+``Inputs/inputs_<name>_Epoch_<e>.png``, ``Reconstructions/recons_<name>_Epoch_<e>.png`` (``model.generate``) and
+``Samples/sample_<name>_Epoch_<e>.png`` (``model.sample``; skipped when the model raises ``Warning``, as VQVAE does) -- with
+``imagegrid.save_image(normalize=True, nrow=12)``, on rank 0 only and without a collective.  Differences from the reference: it
+samples ``min(32, rows of the test batch)`` images with that many of the batch's labels (``ConditionalVAE.sample(32,
+labels=<whole batch>)`` cannot concatenate unless the batch has 32 rows); a per-row ``mode`` list, which the transition loaders
+hand out, is passed on as its one mode, so that ``CTMCQVAE.generate``'s causal -> action remap sees it.  The call leaves the
+run as it found it: eval mode and ``no_grad`` (no BatchNorm statistics, no in-kernel noise state, no parameter epoch move), its
+``torch.randn`` draws come from generators seeded from ``manual_seed`` and the epoch, and torch's CPU / device generator states
+are put back afterwards.
 """
+import contextlib
 import json
+import os
 import sys
 import time
 
 import torch
 
+from . import imagegrid
 from . import kernels as K
 from .ddp import GradBucketAllReduce
+from .metrics import _eval_mode as eval_mode
 from .optim import ExponentialLR, FlatAdam, clip_settings
 
 
@@ -106,11 +122,34 @@ class _GraphedTrainStep:
         return losses
 
 
+@contextlib.contextmanager
+def seeded_torch_rng(seed: int, device):
+    """torch's CPU generator and ``device``'s generator seeded with ``seed`` inside; both states come back afterwards."""
+    cuda = device is not None and torch.device(device).type == "cuda"
+    cpu_state = torch.get_rng_state()
+    dev_state = torch.cuda.get_rng_state(device) if cuda else None
+    try:
+        torch.default_generator.manual_seed(seed)
+        if cuda:
+            with torch.cuda.device(device):
+                torch.cuda.manual_seed(seed)
+        yield
+    finally:
+        torch.set_rng_state(cpu_state)
+        if cuda:
+            torch.cuda.set_rng_state(dev_state, device)
+
+
 class VAEXperiment:
 
+    SAMPLE_DIRS = ("Inputs", "Reconstructions", "Samples")
+
     def __init__(self, vae_model, params: dict, ddp: GradBucketAllReduce = None, log_every: int = 50, log_file=None,
-                 gradient_clip_val=None, gradient_clip_algorithm=None, val_metric=None):
+                 gradient_clip_val=None, gradient_clip_algorithm=None, val_metric=None, val_sampling: bool = False,
+                 sample_dir=None, run_name=None):
         self.val_metric = val_metric
+        self.val_sampling, self.sample_dir = bool(val_sampling), sample_dir
+        self.run_name = run_name if run_name is not None else type(vae_model).__name__
         self.gradient_clip_val, self.gradient_clip_algorithm = clip_settings(gradient_clip_val, gradient_clip_algorithm)
         self.model = vae_model
         self.params = params
@@ -158,8 +197,7 @@ class VAEXperiment:
     def validation_metrics(self, epoch: int) -> dict:
         """The ``val_metric`` results of one validation epoch under the ``val_`` prefix (also one JSONL line); {} without a
         metric or off rank 0.  The metric's own generator is seeded per epoch; no torch generator and no model state moves."""
-        rank0 = self.ddp is None or not torch.distributed.is_initialized() or torch.distributed.get_rank() == 0
-        if self.val_metric is None or not rank0:
+        if self.val_metric is None or not self._rank0():
             return {}
         seed = int(self.params.get('manual_seed', 0) or 0) * 1_000_003 + int(epoch)
         res = {"val_" + k: v for k, v in self.val_metric.compute(self.metric_func, model=self.model, seed=seed).items()}
@@ -167,6 +205,47 @@ class VAEXperiment:
             self.log_file.write(json.dumps({**res, "step": self.global_step}) + "\n")
             self.log_file.flush()
         return res
+
+    def _rank0(self):
+        return self.ddp is None or not torch.distributed.is_initialized() or torch.distributed.get_rank() == 0
+
+    def sample_seed(self, epoch: int) -> int:
+        """Seed of the epoch's ``sample_images`` draws (the rule of ``validation_metrics``)."""
+        return int(self.params.get('manual_seed', 0) or 0) * 1_000_003 + int(epoch)
+
+    def sample_images(self, test_batch, epoch: int) -> list:
+        """experiment.py:114-150 on one test batch ``(input, labels, *options)``: the input, ``model.generate`` and
+        ``model.sample`` grids of this epoch under ``sample_dir`` (module docstring).  Returns the paths written."""
+        test_input, test_label, kwargs = self._unpack(test_batch)
+        dev = next(self.model.parameters()).device
+        test_input = test_input.to(dev)
+        if torch.is_tensor(test_label):
+            test_label = test_label.to(dev)
+        kwargs = dict(kwargs)
+        if isinstance(kwargs.get("mode"), list):
+            kwargs["mode"] = kwargs["mode"][0]
+        for d in self.SAMPLE_DIRS:
+            os.makedirs(os.path.join(self.sample_dir, d), exist_ok=True)
+
+        def path(d, stem):
+            return os.path.join(self.sample_dir, d, f"{stem}_{self.run_name}_Epoch_{epoch}.png")
+
+        written = []
+
+        def save(img, p):
+            imagegrid.save_image(img, p, normalize=True, nrow=12)
+            written.append(p)
+
+        with eval_mode(self.model), seeded_torch_rng(self.sample_seed(epoch), dev):
+            save(test_input, path("Inputs", "inputs"))
+            save(self.model.generate(test_input, labels=test_label, **kwargs), path("Reconstructions", "recons"))
+            try:
+                n = min(32, test_input.size(0))
+                labels = test_label[:n] if torch.is_tensor(test_label) else test_label
+                save(self.model.sample(n, dev, labels=labels, **kwargs), path("Samples", "sample"))
+            except Warning:
+                pass
+        return written
 
     def log_all(self, losses: dict, batch_size, validation: bool = False, force: bool = False):
         """Scalar tensors only (strings / images are dropped like experiment.py:93-106); one fused all-reduce over
@@ -249,9 +328,11 @@ class VAEXperiment:
         self.optimizer.step(grad_scale=scale)
         self.global_step += 1
 
-    def fit(self, train_batches, val_batches=None, max_epochs=1, on_epoch_end=None, start_epoch=0):
-        """train_batches / val_batches: callables returning an iterable of batches for one epoch.  start_epoch: first epoch
-        to run (a resumed run continues at the checkpoint's epoch + 1; max_epochs counts from 0 as Lightning's does)."""
+    def fit(self, train_batches, val_batches=None, max_epochs=1, on_epoch_end=None, start_epoch=0, test_batches=None):
+        """train_batches / val_batches / test_batches: callables returning an iterable of batches for one epoch.  start_epoch:
+        first epoch to run (a resumed run continues at the checkpoint's epoch + 1; max_epochs counts from 0 as Lightning's
+        does).  test_batches: with ``val_sampling`` and a ``sample_dir``, rank 0 reads its first batch after every validation
+        epoch for ``sample_images``."""
         history = []
         for epoch in range(start_epoch, max_epochs):
             self.model.train()
@@ -295,6 +376,10 @@ class VAEXperiment:
                     cnt += 1
                 rec.update({k: v / max(cnt, 1) for k, v in sums.items()})
                 rec.update(self.validation_metrics(epoch))
+                if self.val_sampling and self.sample_dir is not None and test_batches is not None and self._rank0():
+                    first = next(iter(test_batches()), None)
+                    if first is not None:
+                        self.sample_images(first, epoch)
             history.append(rec)
             if on_epoch_end is not None:
                 on_epoch_end(epoch, rec)

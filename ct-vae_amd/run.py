@@ -11,6 +11,9 @@ step, random streams) for ``trainer_params.resume_from_checkpoint`` without ``lo
 Lightning Trainer does (configs/gammavae.yaml); without them the step is unchanged.
 ``exp_params.metrics`` (run.py:64-76; "MIG", "FactorVaeScore") with ``data_params.hbm_factor_sizes`` (the sizes of the
 ground-truth factor grid the ``hbm_images`` rows enumerate row-major) adds the disentanglement metrics to every validation epoch.
+``exp_params.val_sampling: true`` (the reference's run.py hard-wires it on; here it defaults to false) writes the input,
+reconstruction and sample PNG grids of the first test batch after every validation epoch into ``Inputs/``, ``Reconstructions/``
+and ``Samples/`` of the run's log directory, named after ``logging_params.name`` (experiment.py: ``sample_images``).
 """
 import argparse
 import json
@@ -57,6 +60,10 @@ class SyntheticData:
 
     def val(self):
         return self._batches(self.p["val_batch_size"], self.seed + 1_000_003)
+
+    def test(self):
+        """dataset.py:145-166: batches of the validation kind at val_batch_size (their own draws)."""
+        return self._batches(self.p["val_batch_size"], self.seed + 2_000_003)
 
 
 class HbmData:
@@ -130,6 +137,10 @@ class HbmData:
     def val(self):
         return self._loader("test", self.p["val_batch_size"], False)
 
+    def test(self):
+        """dataset.py:145-166: the validation split again at val_batch_size, shuffled; T-datasets mode-pure with drop_last."""
+        return self._loader("test", self.p["val_batch_size"], True)
+
 
 def build_val_metric(config, data):
     """``exp_params.metrics`` -> a MetricSet over the whole store (the reference hands it ``_full_data``), sized as run.py:72-76;
@@ -191,8 +202,13 @@ def main(argv=None):
     os.makedirs(os.path.join(log_dir, "checkpoints"), exist_ok=True)
     log_file = open(os.path.join(log_dir, f"metrics_rank{rank}.jsonl"), "a") if rank == 0 else None
     tp = config['trainer_params']
+    val_sampling = bool(config['exp_params'].get('val_sampling', False))
+    if val_sampling and rank == 0:
+        for d in VAEXperiment.SAMPLE_DIRS:
+            os.makedirs(os.path.join(log_dir, d), exist_ok=True)
     exp = VAEXperiment(model, config['exp_params'], ddp=ddp, log_file=log_file, gradient_clip_val=tp.get('gradient_clip_val'),
-                       gradient_clip_algorithm=tp.get('gradient_clip_algorithm'))
+                       gradient_clip_algorithm=tp.get('gradient_clip_algorithm'), val_sampling=val_sampling, sample_dir=log_dir,
+                       run_name=config['logging_params'].get('name', mp['name']))
     if config['data_params'].get('hbm_images'):
         data = HbmData(config['data_params'], mp, dev, rank, world, seed)
     else:
@@ -230,7 +246,8 @@ def main(argv=None):
             del best[2:]
 
     epochs = args.max_epochs or config['trainer_params'].get('max_epochs', 1)
-    hist = exp.fit(data.train, data.val, max_epochs=epochs, on_epoch_end=on_epoch_end, start_epoch=start_epoch)
+    hist = exp.fit(data.train, data.val, max_epochs=epochs, on_epoch_end=on_epoch_end, start_epoch=start_epoch,
+                   test_batches=data.test if val_sampling else None)
     if world > 1:
         dist.destroy_process_group()
     return hist

@@ -542,6 +542,23 @@ int ctvae_mi_matrix(const float* z, const float* lo, const float* hi, const int3
 int ctvae_group_var_argmin(const float* z, const float* global_var, const uint8_t* active, int G, int B, int L, int32_t* arg,
                            float* val, void* stream);
 
+/* Image grid as bytes (imagegrid.py): torchvision.utils.make_grid + save_image's byte conversion of an f32 batch x [N][C][H][W],
+ * C = 1 (replicated) or 3, read in place through four element strides (>= 0; contiguous NCHW and channels_last alike).
+ * xmaps = min(nrow, N), ymaps = ceil(N / xmaps), Hg = ymaps*(H+padding)+padding, Wg = xmaps*(W+padding)+padding; image k sits at
+ * row (k / xmaps)*(H+padding)+padding, column (k % xmaps)*(W+padding)+padding; borders and the empty cells of the last grid row
+ * hold pad_value.  out: Hg rows of 3*Wg bytes (R, G, B per pixel), or with scanlines != 0 of 1 + 3*Wg bytes, the first being
+ * PNG filter type 0 -- the stream a PNG IDAT chunk deflates.  out must be 16-byte aligned and out_bytes at least the stream's
+ * length rounded up to a multiple of 4; bytes past the stream's length are not written.
+ * normalize != 0: v = (clamp(x, lo, hi) - lo) / max(hi - lo, 1e-5) with lo / hi = range_lo / range_hi when has_range != 0, else
+ * the minimum / maximum over the whole batch (one more launch; workspace: device, 8-byte aligned, at least 2048 bytes).
+ * normalize == 0: v = x.  byte = (uint8) clamp(v*255 + 0.5, 0, 255); pad_value takes the same conversion un-normalised.
+ * Every operation is rounded to f32 on its own.  NaN does not enter the minimum / maximum and becomes byte 0 (torch would
+ * propagate it); +-inf clamp.  A bad argument (C not 1 or 3, N / H / W / nrow < 1, padding < 0, NULL x / out, a stream of
+ * 2^31 bytes or more, out or the workspace too small or misaligned) returns -22 and launches nothing. */
+int ctvae_image_grid_u8(const float* x, long stride_n, long stride_c, long stride_h, long stride_w, int N, int C, int H, int W,
+                        int nrow, int padding, int normalize, int has_range, float range_lo, float range_hi, float pad_value,
+                        int scanlines, uint8_t* out, size_t out_bytes, float* workspace, size_t workspace_bytes, void* stream);
+
 /* MSSIMVAE's reconstruction loss (mssim_vae.py:182-279): 1 - prod_{i<4} (mcs_i^w_i * mssim_4^w_4) over five levels of SSIM with the
  * reference's 11-tap window (2x2 average pooling between levels), for NHWC pictures a (the reconstruction) and b [B,64,64,C].
  * window [11] and weights [5]: HOST arrays (the window as the reference builds it: exp(+(x-5)^2 / 4.5), normalised).
