@@ -126,6 +126,12 @@ size_t adam_state_floats();
 int launch_adam_clipped(float* p, const float* g, float* m, float* v, float* state, long n, float grad_scale, int algorithm,
                         float clip, float* ws, float* norm_out, hipStream_t st);
 size_t grad_clip_workspace_floats();
+int launch_adam_mark_members(int* hits, int nhits, const int* group, int B, hipStream_t st);
+int launch_adam_block_flags(const int* present, const int* hit_index, int* hits, int nhits, const float* bstate, int* active,
+                            int nb, int until_first, hipStream_t st);
+int launch_adam_blocks(float* p, const float* g, float* m, float* v, float* state, long n, float grad_scale, int algorithm,
+                       float clip, float* ws, float* norm_out, const int* blk_lo, const int* blk_hi, float* bstate,
+                       const int* active, int nb, hipStream_t st);
 int launch_ssim_forward(const float* a, const float* b, const float* window, float* part, float* loss, float* coef, int B, int C, int H,
                         int W, const float* weights, hipStream_t st);
 int launch_ssim_backward(const float* a, const float* b, const float* window, const float* coef, const float* g_loss, float* g_a, int B,
@@ -1063,6 +1069,29 @@ int ctvae_adam_step_clipped(float* params, const float* grads, float* exp_avg, f
   if (algorithm == CTVAE_CLIP_NORM && !workspace) return kErrBadArg;
   return launch_adam_clipped(params, grads, exp_avg, exp_avg_sq, state, n, grad_scale, algorithm, clip_val, workspace, norm_out,
                              (hipStream_t)stream);
+}
+
+int ctvae_adam_mark_members(int* hits, int nhits, const int* group, int B, void* stream) {
+  if (!hits || nhits < 1 || B < 0 || (B > 0 && !group)) return kErrBadArg;
+  return launch_adam_mark_members(hits, nhits, B > 0 ? group : nullptr, B, (hipStream_t)stream);
+}
+
+int ctvae_adam_block_flags(const int* present, const int* hit_index, int* hits, int nhits, const float* block_state, int* active,
+                           int nb, int until_first, void* stream) {
+  if (!present || !hit_index || !block_state || !active || nb < 1 || nhits < 0 || (nhits > 0 && !hits)) return kErrBadArg;
+  return launch_adam_block_flags(present, hit_index, hits, nhits, block_state, active, nb, until_first, (hipStream_t)stream);
+}
+
+int ctvae_adam_step_blocks(float* params, const float* grads, float* exp_avg, float* exp_avg_sq, float* state, long n,
+                           float grad_scale, int algorithm, float clip_val, float* workspace, float* norm_out,
+                           const int* block_lo, const int* block_hi, float* block_state, const int* active, int nb, void* stream) {
+  if (!params || !grads || !exp_avg || !exp_avg_sq || !state || n <= 0) return kErrBadArg;
+  if (!block_lo || !block_hi || !block_state || !active || nb < 1) return kErrBadArg;
+  if (algorithm != CTVAE_CLIP_NORM && algorithm != CTVAE_CLIP_VALUE && algorithm != CTVAE_ADAM_NO_CLIP) return kErrBadArg;
+  if (algorithm != CTVAE_ADAM_NO_CLIP && !(clip_val > 0.f)) return kErrBadArg;
+  if (algorithm == CTVAE_CLIP_NORM && !workspace) return kErrBadArg;
+  return launch_adam_blocks(params, grads, exp_avg, exp_avg_sq, state, n, grad_scale, algorithm, clip_val, workspace, norm_out,
+                            block_lo, block_hi, block_state, active, nb, (hipStream_t)stream);
 }
 
 }  // extern "C"

@@ -427,6 +427,227 @@ __global__ __launch_bounds__(256) void adam_clip_kernel(float* __restrict__ p, c
   }
 }
 
+// ---- block-aware Adam: parameters that got no gradient stand still ---------------------------------------
+// torch.optim.Adam keeps a step counter per parameter and leaves a parameter whose .grad is None alone (no moment decay, no
+// weight decay, no counter advance).  FlatAdam's absent_grad = "skip" / "skip_until_first" gets that from a BLOCK TABLE over the
+// flat buffer: blk_lo / blk_hi are nb sorted, disjoint ranges [lo, hi) of the n floats (floats in no range are alignment gaps:
+// never read, never written), bstate[4b ..] = {step, beta1^step, beta2^step, seen} of block b, and active[b] != 0 means block b
+// steps in this launch, with its OWN bias corrections.
+// A workgroup owns one contiguous range of quads: thread 0 finds the first block that reaches into it by binary search, every
+// thread walks on from there with a cursor that only moves forward (its quads ascend).  A quad inside one block takes the
+// 16-byte path, or is skipped whole; a quad that straddles a boundary or the end of the buffer goes float by float, each
+// float under its own block.  The update's roundings are adam_kernel's / adam_clip_kernel's for the same position of the
+// buffer (16-byte region or tail), so with every block active and equal counters the step is theirs bit for bit.
+constexpr int kClipOff = 2;
+
+template <bool VEC, int MODE>
+__global__ __launch_bounds__(256) void adam_blocks_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
+                                                          float* __restrict__ v, float* state, long n, float grad_scale, float clip,
+                                                          const float* partial, int nparts, float* norm_out,
+                                                          const int* __restrict__ blk_lo, const int* __restrict__ blk_hi,
+                                                          float* bstate, const int* __restrict__ active, int nb) {
+  __shared__ int s_first, s_last;
+  const float lr = state[1], b1 = state[2], b2 = state[3], eps = state[4], wd = state[5];
+  float c = 1.f;
+  if constexpr (MODE == kClipNorm) {
+    __shared__ float lds[4];
+    float s = 0.f;
+    for (int k = threadIdx.x; k < nparts; k += 256) s += partial[k];
+    const float total = sqrtf(block_sum256(s, lds));
+    c = (1.f / (total + 1e-6f)) * clip;
+    c = c > 1.f ? 1.f : c;                     // not fminf: a NaN coefficient must stay NaN
+    if (norm_out != nullptr && blockIdx.x == 0 && threadIdx.x == 0) *norm_out = total;
+  }
+  const long nq = (n + 3) / 4;                 // the last quad may be partial
+  const long qper = (nq + gridDim.x - 1) / gridDim.x;
+  const long q0 = (long)blockIdx.x * qper, q1 = q0 + qper < nq ? q0 + qper : nq;
+  if (threadIdx.x == 0) {                      // first block that ends behind this workgroup's first float
+    const long e = 4 * q0;
+    int lo = 0, hi = nb;
+    while (lo < hi) {
+      const int mid = (lo + hi) >> 1;
+      if ((long)blk_hi[mid] <= e) lo = mid + 1;
+      else hi = mid;
+    }
+    s_first = lo;
+  }
+  __syncthreads();
+  int bi = s_first, cur = -1;
+  float step_size = 0.f, bc2s = 1.f;
+  auto use_block = [&](int b) {                // bias corrections of block b's own step count
+    if (b != cur) {
+      // beta^t rounded before the subtraction, as adam_kernel has it (it stores beta^t); contracted, 1 - x * b would fuse
+#pragma clang fp contract(off)
+      cur = b;
+      const float b1t = bstate[4 * b + 1] * b1, b2t = bstate[4 * b + 2] * b2;
+      const float bc1 = 1.f - b1t, bc2 = 1.f - b2t;
+      step_size = lr / bc1;
+      bc2s = sqrtf(bc2);
+    }
+  };
+  auto upd = [&](float& pi, float gi, float& mi, float& vi, bool quad) {
+    // no contraction in here: every fused operation is written as one
+#pragma clang fp contract(off)
+    if constexpr (MODE == kClipNorm) {
+      gi = quad ? fmaf(gi * grad_scale, c, wd * pi) : fmaf(wd, pi, (gi * grad_scale) * c);
+    } else if constexpr (MODE == kClipValue) {
+      gi = gi * grad_scale;
+      gi = gi < -clip ? -clip : (gi > clip ? clip : gi);   // comparisons, not fminf / fmaxf: NaN stays NaN
+      gi = fmaf(wd, pi, gi);
+    } else {
+      gi = quad ? fmaf(gi, grad_scale, wd * pi) : fmaf(wd, pi, gi * grad_scale);
+    }
+    // the moments with the roundings the compiler gives adam_kernel / adam_clip_kernel (read off the ISA): fused in their
+    // 16-byte loops, two rounded products and an add in their scalar loops -- spelled out, so that this kernel's float-by-float
+    // path inside the 16-byte region still rounds like their 16-byte loop
+    const float gs1 = (1.f - b1) * gi, gs2 = gi * ((1.f - b2) * gi);
+    if (quad) {
+      mi = fmaf(b1, mi, gs1);
+      vi = fmaf(b2, vi, gs2);
+    } else {
+      mi = b1 * mi + gs1;
+      vi = b2 * vi + gs2;
+    }
+    pi = fmaf(-step_size, mi / (sqrtf(vi) / bc2s + eps), pi);
+  };
+  const long nfull = VEC ? (n / 4) * 4 : 0;    // where adam_kernel runs its 16-byte loop
+  // quad q: blk >= 0 -> inside the active block blk (16-byte path); mixed -> some float of it may lie in a block, go float by float
+  auto classify = [&](long q, int& blk, bool& mixed) {
+    blk = -1;
+    mixed = false;
+    const long e0 = 4 * q;
+    while (bi < nb && (long)blk_hi[bi] <= e0) ++bi;
+    if (bi >= nb) return;
+    const long lo = blk_lo[bi], hi = blk_hi[bi];
+    if (lo <= e0 && e0 + 4 <= hi && e0 + 4 <= n) {
+      if (active[bi]) {
+        if (VEC) blk = bi;
+        else mixed = true;
+      }
+    } else if (lo < e0 + 4) {
+      mixed = true;
+    }
+  };
+  auto by_float = [&](long q) {
+    int bj = bi;
+    for (int k = 0; k < 4; ++k) {
+      const long e = 4 * q + k;
+      if (e >= n) break;
+      while (bj < nb && (long)blk_hi[bj] <= e) ++bj;
+      if (bj >= nb) break;
+      if ((long)blk_lo[bj] <= e && active[bj]) {
+        use_block(bj);
+        float pi = p[e], mi = m[e], vi = v[e];
+        upd(pi, g[e], mi, vi, e < nfull);
+        m[e] = mi;
+        v[e] = vi;
+        p[e] = pi;
+      }
+    }
+  };
+  f32x4* p4 = reinterpret_cast<f32x4*>(p);
+  const f32x4* g4 = reinterpret_cast<const f32x4*>(g);
+  f32x4* m4 = reinterpret_cast<f32x4*>(m);
+  f32x4* v4 = reinterpret_cast<f32x4*>(v);
+  for (long qa = q0 + threadIdx.x; qa < q1; qa += 512) {   // two quads per thread in flight
+    const long qb = qa + 256;
+    int ba, bb = -1;
+    bool mixa, mixb = false;
+    classify(qa, ba, mixa);
+    const int bia = bi;                        // cursor at quad a, for its float-by-float walk
+    if (qb < q1) classify(qb, bb, mixb);
+    f32x4 pa, ga, ma, va, pb, gb, mb, vb;
+    if (ba >= 0) { pa = p4[qa]; ga = g4[qa]; ma = m4[qa]; va = v4[qa]; }
+    if (bb >= 0) { pb = p4[qb]; gb = g4[qb]; mb = m4[qb]; vb = v4[qb]; }
+    if (ba >= 0) {
+      use_block(ba);
+#pragma unroll
+      for (int q = 0; q < 4; ++q) {
+        float pq = pa[q], mq = ma[q], vq = va[q];
+        upd(pq, ga[q], mq, vq, true);
+        pa[q] = pq; ma[q] = mq; va[q] = vq;
+      }
+      m4[qa] = ma; v4[qa] = va; p4[qa] = pa;
+    }
+    if (bb >= 0) {
+      use_block(bb);
+#pragma unroll
+      for (int q = 0; q < 4; ++q) {
+        float pq = pb[q], mq = mb[q], vq = vb[q];
+        upd(pq, gb[q], mq, vq, true);
+        pb[q] = pq; mb[q] = mq; vb[q] = vq;
+      }
+      m4[qb] = mb; v4[qb] = vb; p4[qb] = pb;
+    }
+    if (mixa) {
+      const int keep = bi;
+      bi = bia;
+      by_float(qa);
+      bi = keep;
+    }
+    if (mixb) by_float(qb);
+  }
+  __syncthreads();   // every thread of this workgroup has read the block states it needs
+  if (threadIdx.x == 0) {   // adam_kernel's two-level ticket
+    unsigned* tk = reinterpret_cast<unsigned*>(state + kAdamTicketOffset);
+    const unsigned grp = blockIdx.x >> 5, ngrp = (gridDim.x + 31) >> 5;
+    const unsigned gsize = gridDim.x - grp * 32 < 32 ? gridDim.x - grp * 32 : 32;
+    int last = 0;
+    if (atomicAdd(tk + 16 * (1 + grp), 1u) == gsize - 1) {
+      atomicExch(tk + 16 * (1 + grp), 0u);
+      if (atomicAdd(tk, 1u) == ngrp - 1) {
+        atomicExch(tk, 0u);
+        last = 1;
+      }
+    }
+    s_last = last;
+  }
+  __syncthreads();
+  if (s_last) {   // the workgroup that finished last: the counters of the blocks that stepped move on, the others stand
+    for (int b = threadIdx.x; b < nb; b += 256) {
+      if (active[b]) {
+        bstate[4 * b] += 1.f;
+        bstate[4 * b + 1] *= b1;
+        bstate[4 * b + 2] *= b2;
+        bstate[4 * b + 3] = 1.f;
+      }
+    }
+    if (threadIdx.x == 0) {                    // launches so far; the buffer-wide beta^t keep their meaning for the record
+      state[0] += 1.f;
+      state[6] *= b1;
+      state[7] *= b2;
+    }
+  }
+}
+
+// hits[k] = 1 for member 0 of a parameter bank and for every member group[b] a sample of this forward selects (racing
+// threads store the same 1)
+__global__ __launch_bounds__(256) void adam_mark_members_kernel(int* __restrict__ hits, int nhits, const int* __restrict__ group,
+                                                                int B) {
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i == 0) hits[0] = 1;
+  if (group != nullptr && i < B) {
+    const int k = group[i];
+    if (k >= 0 && k < nhits) hits[k] = 1;
+  }
+}
+
+// active[b] = present[b] (what the host knows: a gradient kernel wrote the block / autograd produced a gradient), for a bank
+// member and its hit word too; until_first: a block that has stepped once steps ever after.  Consumes the hit words.
+__global__ __launch_bounds__(256) void adam_block_flags_kernel(const int* __restrict__ present, const int* __restrict__ hit_index,
+                                                               int* hits, int nhits, const float* __restrict__ bstate,
+                                                               int* __restrict__ active, int nb, int until_first) {
+  for (int b = threadIdx.x; b < nb; b += 256) {
+    int a = present[b] != 0;
+    const int h = hit_index[b];
+    if (h >= 0) a = a && (h < nhits && hits[h] != 0);
+    if (until_first && bstate[4 * b + 3] != 0.f) a = 1;
+    active[b] = a;
+  }
+  __syncthreads();
+  for (int k = threadIdx.x; k < nhits; k += 256) hits[k] = 0;
+}
+
 // Straight-through Bernoulli sample through a 2-class Gumbel-softmax (tau = 1, hard) of
 // log(clamp([1-p, p], 1e-4)) (ct_mcq_vae.py:126,177-183).  noise = 2 standard Gumbel draws/element.
 __global__ __launch_bounds__(256) void gumbel_st_fwd_kernel(const float* __restrict__ p, const float* __restrict__ noise,
@@ -557,6 +778,57 @@ int launch_adam_clipped(float* p, const float* g, float* m, float* v, float* sta
     else hipLaunchKernelGGL((adam_clip_kernel<false, kClipValue>), grid, dim3(256), 0, st, p, g, m, v, state, n, grad_scale,
                             clip, nullptr, 0, nullptr);
   }
+  CTVAE_LAUNCH_CHECK();
+  return 0;
+}
+
+int launch_adam_mark_members(int* hits, int nhits, const int* group, int B, hipStream_t st) {
+  hipLaunchKernelGGL(adam_mark_members_kernel, dim3((unsigned)((B > 1 ? B : 1) + 255) / 256), dim3(256), 0, st, hits, nhits, group, B);
+  CTVAE_LAUNCH_CHECK();
+  return 0;
+}
+
+int launch_adam_block_flags(const int* present, const int* hit_index, int* hits, int nhits, const float* bstate, int* active,
+                            int nb, int until_first, hipStream_t st) {
+  hipLaunchKernelGGL(adam_block_flags_kernel, dim3(1), dim3(256), 0, st, present, hit_index, hits, nhits, bstate, active, nb,
+                     until_first);
+  CTVAE_LAUNCH_CHECK();
+  return 0;
+}
+
+int launch_adam_blocks(float* p, const float* g, float* m, float* v, float* state, long n, float grad_scale, int algorithm,
+                       float clip, float* ws, float* norm_out, const int* blk_lo, const int* blk_hi, float* bstate,
+                       const int* active, int nb, hipStream_t st) {
+  constexpr int wgs = 1024;
+  static_assert(wgs <= kAdamMaxWgs, "the Adam state is sized for kAdamMaxWgs workgroups");
+  if (n > 0x7fffffffL) return kErrBadArg;       // the block table holds 32-bit offsets
+  const bool vec = ((reinterpret_cast<uintptr_t>(p) | reinterpret_cast<uintptr_t>(g) | reinterpret_cast<uintptr_t>(m) |
+                     reinterpret_cast<uintptr_t>(v)) % 16) == 0;
+  const dim3 grid(grid_for((n + 3) / 4, wgs));
+  int nparts = 0;
+  if (algorithm == kClipNorm) {                 // blocks that do not step and gaps hold zeros: the norm pass is adam_clip's
+    nparts = (int)grid_for(n / 4, kClipMaxWgs);
+    ProfScope ps("grad_sqnorm_kernel", st, 0.0, 4.0 * (double)n + 4.0 * nparts);
+    if (reinterpret_cast<uintptr_t>(g) % 16 == 0)
+      hipLaunchKernelGGL(grad_sqnorm_kernel<true>, dim3(nparts), dim3(256), 0, st, g, n, grad_scale, ws);
+    else hipLaunchKernelGGL(grad_sqnorm_kernel<false>, dim3(nparts), dim3(256), 0, st, g, n, grad_scale, ws);
+    CTVAE_LAUNCH_CHECK();
+  }
+  ProfScope ps("adam_blocks_kernel", st, 0.0, 28.0 * (double)n + 4.0 * nparts);
+#define CTVAE_ADAM_BLOCKS(V, M)                                                                                              \
+  hipLaunchKernelGGL((adam_blocks_kernel<V, M>), grid, dim3(256), 0, st, p, g, m, v, state, n, grad_scale, clip, ws, nparts, \
+                     norm_out, blk_lo, blk_hi, bstate, active, nb)
+  if (algorithm == kClipNorm) {
+    if (vec) CTVAE_ADAM_BLOCKS(true, kClipNorm);
+    else CTVAE_ADAM_BLOCKS(false, kClipNorm);
+  } else if (algorithm == kClipValue) {
+    if (vec) CTVAE_ADAM_BLOCKS(true, kClipValue);
+    else CTVAE_ADAM_BLOCKS(false, kClipValue);
+  } else {
+    if (vec) CTVAE_ADAM_BLOCKS(true, kClipOff);
+    else CTVAE_ADAM_BLOCKS(false, kClipOff);
+  }
+#undef CTVAE_ADAM_BLOCKS
   CTVAE_LAUNCH_CHECK();
   return 0;
 }

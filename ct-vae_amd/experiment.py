@@ -4,7 +4,9 @@
 ``model(real_img, labels=..., **options)``, ``loss_function(*results, M_N=kld_weight)`` for training and
 ``M_N=1.0`` with a ``val_`` key prefix for validation, Adam(lr=LR, weight_decay) + ExponentialLR(gamma)
 over ``model.parameters()`` or ``getattr(model, update_parameters).parameters()``, with the Trainer's gradient clipping
-(``gradient_clip_val`` / ``gradient_clip_algorithm``, see optim.py) in front of the step.  What changes is the
+(``gradient_clip_val`` / ``gradient_clip_algorithm``, see optim.py) in front of the step; ``exp_params.adam_absent_grad``
+("zero", the default; "skip"; "skip_until_first") chooses what the step does to parameters without a gradient (optim.py; the
+two skip modes are refused together with a DDP gradient exchange).  What changes is the
 machinery: one flat fused Adam launch, one bucketed RCCL all-reduce, and scalars fetched with ONE device
 -> host copy every ``log_every`` steps instead of one ``.item()`` sync per key per step (experiment.py:95-96).
 
@@ -37,7 +39,7 @@ from . import imagegrid
 from . import kernels as K
 from .ddp import GradBucketAllReduce
 from .metrics import _eval_mode as eval_mode
-from .optim import ExponentialLR, FlatAdam, clip_settings
+from .optim import ExponentialLR, FlatAdam, absent_grad_setting, clip_settings
 
 
 def _graph_key(real_img, kwargs):
@@ -74,6 +76,7 @@ class _GraphedTrainStep:
         self.seen = 0
         self.graph = None
         self.losses = None
+        self.pattern = None       # FlatAdam's host-known block activity of this signature's steps (absent_grad skip modes)
 
     def _body(self):
         exp = self.exp
@@ -91,6 +94,12 @@ class _GraphedTrainStep:
         exp.model.gather_torch_grads()
         if exp.ddp is None:
             exp.optimizer.step()
+            pat = exp.optimizer.host_pattern
+            if pat is not None:              # constant per signature: a replay repeats the capture step's launches and flags
+                if self.pattern is not None and pat != self.pattern:
+                    raise RuntimeError("steps of one graph signature got gradients for different parameter blocks: "
+                                       f"{sum(a != b for a, b in zip(pat, self.pattern))} blocks differ")
+                self.pattern = pat
         # detached: a live loss keeps the step's autograd graph -- and with it the AccumulateGrad nodes of the parameters
         # torch accumulates itself (the CT layer's banks), bound to the stream they were made on -- alive into the next
         # signature's capture, where running them on that other stream ends the capture with a fault
@@ -154,6 +163,9 @@ class VAEXperiment:
         self.model = vae_model
         self.params = params
         self.ddp = ddp
+        if absent_grad_setting(params.get("adam_absent_grad")) != "zero" and ddp is not None:
+            raise ValueError(f"adam_absent_grad={params['adam_absent_grad']!r} is not available with a DDP gradient exchange: the "
+                             "per-block activity flags are not reduced across ranks yet, and ranks must not step differently")
         self.curr_device = None
         self.log_every = log_every
         self.log_file = log_file
@@ -272,7 +284,8 @@ class VAEXperiment:
         if "update_parameters" in self.params:
             sl = self.model.flat_range(self.params["update_parameters"])
         opt = FlatAdam(self.model, lr=self.params['LR'], weight_decay=self.params.get('weight_decay', 0.0), params_slice=sl,
-                       clip_val=self.gradient_clip_val, clip_algorithm=self.gradient_clip_algorithm)
+                       clip_val=self.gradient_clip_val, clip_algorithm=self.gradient_clip_algorithm,
+                       absent_grad=absent_grad_setting(self.params.get("adam_absent_grad")))
         sched = None
         if self.params.get('scheduler_gamma') is not None:
             sched = ExponentialLR(opt, self.params['scheduler_gamma'])
@@ -290,6 +303,8 @@ class VAEXperiment:
                             "state": opt["state"][:8].detach().cpu(), "lr": float(self.optimizer.lr),
                             "slice": [int(self.optimizer.slice.start or 0), int(self.optimizer.slice.stop)]},
               "torch_rng": torch.get_rng_state()}
+        if "block_state" in opt:           # adam_absent_grad skip modes: per-block step, beta^step and seen flag
+            sd["optimizer"].update(absent_grad=opt["absent_grad"], block_state=opt["block_state"].detach().cpu())
         if self.scheduler is not None:
             sd["scheduler"] = {"epoch": int(self.scheduler.epoch), "base_lr": float(self.scheduler.base_lr),
                                "gamma": float(self.scheduler.gamma)}
@@ -306,6 +321,9 @@ class VAEXperiment:
         o = sd["optimizer"]
         if [int(self.optimizer.slice.start or 0), int(self.optimizer.slice.stop)] != [int(v) for v in o["slice"]]:
             raise RuntimeError("checkpoint optimizes another parameter range than this run (update_parameters differs)")
+        if o.get("absent_grad", "zero") != self.optimizer.absent_grad:
+            raise RuntimeError(f"checkpoint was written under adam_absent_grad={o.get('absent_grad', 'zero')!r}, this run uses "
+                               f"{self.optimizer.absent_grad!r} (exp_params.adam_absent_grad differs)")
         self.optimizer.load_state_dict(o)
         self.optimizer.lr = float(o["lr"])
         if self.scheduler is not None and "scheduler" in sd:

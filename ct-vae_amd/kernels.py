@@ -60,12 +60,14 @@ def _c(t):
 
 def grad_target(p):
     """(tensor to write the gradient into, accumulate flag).  Allocates p.grad with p's memory layout if absent."""
+    blk = getattr(p, "_grad_block", None)
+    if blk is not None:
+        blk.written = True                 # FlatAdam's block activity: a gradient kernel wrote the block since zero_grad
     if p.grad is None:
         p.grad = torch.empty_strided(p.shape, p.stride(), dtype=p.dtype, device=p.device)
         return p.grad, 0
     if p.grad.stride() != p.stride():
         raise RuntimeError("parameter .grad does not share the packed layout of the parameter")
-    blk = getattr(p, "_grad_block", None)
     if blk is not None and blk.fresh:      # zero_grad(lazy=True) (models/packing.py): first writer of the block overwrites
         blk.fresh = False
         return p.grad, 0
@@ -2490,3 +2492,58 @@ def adam_step_clipped(flat_params, flat_grads, exp_avg, exp_avg_sq, state, grad_
     native.call("ctvae_adam_step_clipped", flat_params.data_ptr(), flat_grads.data_ptr(), exp_avg.data_ptr(),
                 exp_avg_sq.data_ptr(), state.data_ptr(), flat_params.numel(), float(grad_scale), CLIP_ALGORITHMS[algorithm],
                 float(clip_val), native.ptr(workspace), native.ptr(norm_out))
+
+
+CLIP_OFF = 2                                       # CTVAE_ADAM_NO_CLIP
+ABSENT_GRAD_MODES = ("zero", "skip", "skip_until_first")
+
+
+class AdamBlockTable:
+    """Device side of FlatAdam's block table (``absent_grad`` "skip" / "skip_until_first", ctvae_adam_step_blocks): sorted int32
+    ``lo`` / ``hi`` offsets of the blocks inside the optimizer's slice of ``n`` floats, ``hit_index`` (a bank member's word of
+    the hit vector, -1 for every other block), ``state`` [nb, 4] = (step, beta1^step, beta2^step, seen) per block and the
+    ``active`` flags the step fills and reads."""
+
+    def __init__(self, ranges, hit_index, n, nhits, device):
+        prev = 0
+        for lo, hi in ranges:
+            if not prev <= lo < hi <= n:
+                raise ValueError(f"block table: [{lo}, {hi}) is empty, overlaps its predecessor or leaves the {n} floats")
+            prev = hi
+        if not ranges or n >= 2 ** 31 or len(hit_index) != len(ranges) or any(h >= nhits for h in hit_index):
+            raise ValueError("block table: needs at least one block, fewer than 2^31 floats and one hit index per block")
+        dev = torch.device(device)
+        self.nb, self.n, self.nhits = len(ranges), int(n), int(nhits)
+        self.lo = torch.tensor([r[0] for r in ranges], dtype=torch.int32, device=dev)
+        self.hi = torch.tensor([r[1] for r in ranges], dtype=torch.int32, device=dev)
+        self.hit_index = torch.tensor(list(hit_index), dtype=torch.int32, device=dev)
+        self.hits = torch.zeros(max(self.nhits, 1), dtype=torch.int32, device=dev)
+        self.state = torch.tensor([0.0, 1.0, 1.0, 0.0], dtype=torch.float32, device=dev).repeat(self.nb, 1)
+        self.active = torch.zeros(self.nb, dtype=torch.int32, device=dev)
+
+
+def adam_mark_members(hits, group=None):
+    """Forward side of a parameter bank: member 0 and every member ``group`` (int32 [B]) names were used in this step."""
+    _req_cuda(hits, group)
+    native.call("ctvae_adam_mark_members", hits.data_ptr(), hits.numel(), native.ptr(group), 0 if group is None else group.numel())
+
+
+def adam_step_blocks(flat_params, flat_grads, exp_avg, exp_avg_sq, state, table, present, mode, grad_scale=1.0, algorithm=None,
+                     clip_val=None, workspace=None, norm_out=None):
+    """adam_step / adam_step_clipped (algorithm None / "norm" / "value") on the blocks of ``table`` that have a gradient in this
+    step, every block under its own step counter; the others keep parameter, moments and counter.  present: int32 [nb] device
+    tensor, what the host knows of the blocks' gradients; a bank member also needs its hit word (adam_mark_members).
+    mode: "skip" or "skip_until_first"."""
+    if not flat_params.is_cuda:
+        raise RuntimeError(f"FlatAdam absent_grad={mode!r} needs device tensors: the block-aware step (ctvae_adam_step_blocks) "
+                           "is a HIP kernel, there is no CPU fallback and no CPU test double of it")
+    _req_cuda(flat_grads, present)
+    if mode not in ABSENT_GRAD_MODES[1:] or flat_params.numel() != table.n or present.numel() != table.nb:
+        raise ValueError("adam_step_blocks: mode is 'skip' or 'skip_until_first'; table and present flags must fit the buffers")
+    bump_param_epoch()
+    native.call("ctvae_adam_block_flags", present.data_ptr(), table.hit_index.data_ptr(), table.hits.data_ptr(), table.nhits,
+                table.state.data_ptr(), table.active.data_ptr(), table.nb, 1 if mode == "skip_until_first" else 0)
+    native.call("ctvae_adam_step_blocks", flat_params.data_ptr(), flat_grads.data_ptr(), exp_avg.data_ptr(), exp_avg_sq.data_ptr(),
+                state.data_ptr(), flat_params.numel(), float(grad_scale), CLIP_OFF if algorithm is None else CLIP_ALGORITHMS[algorithm],
+                0.0 if clip_val is None else float(clip_val), native.ptr(workspace), native.ptr(norm_out), table.lo.data_ptr(),
+                table.hi.data_ptr(), table.state.data_ptr(), table.active.data_ptr(), table.nb)

@@ -203,6 +203,10 @@ class _DiscoverBank(nn.ModuleList):
     out (storage_blocks); a stand-alone module that is not under a flat root falls back to torch.stack."""
 
     autograd_grads = True        # placed by storage_blocks(), but the gradients arrive through autograd (kernels.BankView)
+    # int32 device vector, one word per scorer, or None.  BankView's backward hands every scorer a dense slice of the bank's
+    # gradient, so WHICH scorers a step used is not visible in .grad: an optimizer that wants to know (FlatAdam's absent_grad
+    # "skip" modes) installs this vector and the forward marks the scorers it reads -- one tiny launch, no host sync.
+    member_hits = None
 
     def __init__(self, n, in_dim, hidden):
         super().__init__([nn.Sequential(nn.Linear(in_dim, hidden), nn.LeakyReLU(), nn.Linear(hidden, 1), nn.Sigmoid())
@@ -219,6 +223,11 @@ class _DiscoverBank(nn.ModuleList):
             views = [(p, k * n, tuple(p.shape), tuple(p.detach().contiguous().stride())) for k, p in enumerate(plist)]
             blocks.append((-(-len(plist) * n // 4) * 4, views))       # every bank starts 16-byte aligned
         return blocks
+
+    def mark_members(self, group=None):
+        """Scorer 0 and the scorers ``group`` (int32 [B], 1 + action) names take part in this training step."""
+        if self.member_hits is not None and torch.is_grad_enabled():
+            K.adam_mark_members(self.member_hits, group)
 
     def tensors(self):
         """(W1 [G,H,2D], b1 [G,H], w2 [G,H], b2 [G])"""
@@ -319,6 +328,8 @@ class CausalTransition(nn.Module):
         discoverer 0 and of every sample's own discoverer are ONE grouped GEMM (kernels.GroupLinear), the all-pairs scorer
         reads them and the scorer bank in place (kernels.PairScores).  mask None: no intervention (base mode)."""
         D, Hd = latent.size(-1), self.latent_dims[0]
+        if self.graph_discovers.member_hits is not None:
+            self.graph_discovers.mark_members(None if mask is None else self._action_group(action))
         if latent.is_cuda and latent.size(1) == 64 and K.glinear_ok(D, Hd, 2 * D):
             W1, b1, w2, b2 = self.graph_discovers.tensors()
             if mask is None:

@@ -127,11 +127,12 @@ class PackedEmbedding(nn.Module):
 class _GradBlock:
     """One storage block of the flat gradient buffer, [lo, hi) floats.  ``fresh``: zero_grad(lazy=True) declared the block zero
     without writing it -- the first kernel that writes the block's gradient overwrites instead of accumulating
-    (kernels.grad_target), and whatever is still fresh when the buffer is read gets its zeros then (settle_grads)."""
-    __slots__ = ("lo", "hi", "fresh")
+    (kernels.grad_target), and whatever is still fresh when the buffer is read gets its zeros then (settle_grads).
+    ``written``: a gradient kernel asked for the block since the last zero_grad, lazy or not (FlatAdam's block activity)."""
+    __slots__ = ("lo", "hi", "fresh", "written")
 
     def __init__(self, lo, hi):
-        self.lo, self.hi, self.fresh = lo, hi, False
+        self.lo, self.hi, self.fresh, self.written = lo, hi, False, True
 
 
 class FlatParamMixin:
@@ -232,6 +233,45 @@ class FlatParamMixin:
                         g.copy_(p.grad)
                 p.grad = g
 
+    def adam_blocks(self):
+        """The ranges of the flat buffers that get or miss their gradient as a whole, in buffer order, for FlatAdam's block
+        table: [(lo, hi, kind, ref, member)] with kind "kernel" (a storage block the HIP gradient kernels write in one call --
+        a PackedLinearGroup's heads are one; ref = its _GradBlock), "torch" (an autograd-managed parameter; ref = it) or "bank"
+        (one member's sub-range of a module bank such as _DiscoverBank's; ref = (the bank module, the parameter), member = its
+        index: autograd hands the whole bank one dense gradient, so which members were used is known on the device only).
+        Alignment gaps and a bank's padding belong to no block."""
+        self.flat_params                                   # (flattens on first use)
+        bank_of = {}
+        for m in self.modules():
+            if getattr(m, "autograd_grads", False) and hasattr(m, "storage_blocks") and m is not self:
+                for _, views in m.storage_blocks():
+                    for k, (p, *_) in enumerate(views):
+                        bank_of[id(p)] = (m, k)
+        out, off = [], 0
+        for n, views in self._collect_blocks():
+            if n < 0:
+                off = -(-off // -n) * -n
+                continue
+            if views and id(views[0][0]) in bank_of:
+                for p, o, *_ in views:
+                    mod, k = bank_of[id(p)]
+                    out.append((off + o, off + o + p.numel(), "bank", (mod, p), k))
+            elif views and any(id(p) in self._torch_param_ids for p, *_ in views):
+                for p, o, *_ in views:
+                    out.append((off + o, off + o + p.numel(), "torch", p, None))
+            elif views:
+                out.append((off, off + n, "kernel", views[0][0]._grad_block, None))
+            off += n
+        return out
+
+    def torch_grad_present(self, p) -> bool:
+        """Whether autograd produced a gradient for the torch-level parameter p in this step: p.grad was not None when
+        gather_torch_grads() first ran after zero_grad (before any zero_grad: yes)."""
+        present = getattr(self, "_torch_present", False)
+        if present is None:
+            raise RuntimeError("torch_grad_present: call gather_torch_grads() first (nothing was gathered since zero_grad)")
+        return True if present is False else id(p) in present
+
     def flat_range(self, prefix: str) -> slice:
         """Contiguous slice of the flat buffers that holds every parameter under sub-module `prefix`
         (experiment.py:157 optimises only ``getattr(model, update_parameters).parameters()``)."""
@@ -299,6 +339,9 @@ class FlatParamMixin:
                 self._lazy_zero = False
                 prezeroed = True
             self._torch_prezeroed = prezeroed
+            for blk in self._grad_blocks:
+                blk.written = False
+            self._torch_present = None     # gather_torch_grads() records which torch-level parameters autograd gave a gradient
             for p, _ in getattr(self, "_torch_grad_views", ()):
                 p.grad = None
             _K.note_zero_grad(prezeroed)
@@ -352,6 +395,8 @@ class FlatParamMixin:
         """Move autograd-produced gradients of torch-level parameters into their views of the flat gradient buffer and
         re-attach the views (call before the optimizer step / gradient exchange).  Completes a lazy zero_grad first."""
         self.settle_grads()
+        if getattr(self, "_torch_present", False) is None:      # first gather since zero_grad: later ones find every view attached
+            self._torch_present = {id(p) for p, _ in getattr(self, "_torch_grad_views", ()) if p.grad is not None}
         # (a gradient that a kernel wrote straight into the flat buffer -- kernels.flat_grad_alias -- is already in place)
         pairs = [(p, g) for p, g in getattr(self, "_torch_grad_views", ())
                  if p.grad is not None and p.grad is not g and p.grad.data_ptr() != g.data_ptr()]

@@ -109,6 +109,9 @@ SIGNATURES = {
     "ctvae_image_grid_u8": [_fp, _l, _l, _l, _l, _i, _i, _i, _i, _i, _i, _i, _i, _f, _f, _f, _i, _fp, _sz, _fp, _sz, _vp],
     "ctvae_adam_step": [_fp, _fp, _fp, _fp, _fp, _l, _f, _vp],
     "ctvae_adam_step_clipped": [_fp, _fp, _fp, _fp, _fp, _l, _f, _i, _f, _fp, _fp, _vp],
+    "ctvae_adam_mark_members": [_fp, _i, _fp, _i, _vp],
+    "ctvae_adam_block_flags": [_fp, _fp, _fp, _i, _fp, _fp, _i, _i, _vp],
+    "ctvae_adam_step_blocks": [_fp, _fp, _fp, _fp, _fp, _l, _f, _i, _f, _fp, _fp, _fp, _fp, _fp, _fp, _i, _vp],
     "ctvae_mssim_forward": [_fp, _fp, _fp, _fp, _fp, _fp, _fp, _i, _i, _i, _i, _vp],
     "ctvae_mssim_backward": [_fp, _fp, _fp, _fp, _fp, _fp, _i, _i, _i, _i, _vp],
     "ctvae_defer_begin": [_fp, _sz],

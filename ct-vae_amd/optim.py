@@ -5,15 +5,33 @@ reference's harness builds (experiment.py:158-160); the schedule is ``Exponentia
 per epoch (experiment.py:173-175).  One kernel launch per step for the whole model, hyper-parameters and the
 step counter live in a small device tensor so the launch is hipGraph-capturable.
 
-Deviations from ``torch.optim.Adam`` (documented, not pinned by a fixture):
-* ONE step counter for the whole buffer, and every element is updated every step.  torch keeps a step per parameter and
-  skips parameters whose ``.grad`` is None.  The two differ only for parameters that receive NO gradient in some steps --
-  in this repository CT-MCQ-VAE's per-action ``graph_discovers`` whose action is absent from a batch, ``ct_layer.mask`` in
-  base-mode steps, the decoder in causal-mode steps: here they see a zero gradient (first moment decays, the parameter keeps
-  drifting by its momentum, bias correction follows the global count), in torch they are frozen for that step.  VanillaVAE /
-  MCQ-VAE (every parameter gets a gradient every step) are unaffected: tests/test_ct_gpu.py pins their 3-step trajectory.
-* beta1^t / beta2^t are accumulated in fp32 on the device (state[6..7]); torch computes them in double on the host.  After
-  10^4 steps the relative difference of the bias corrections is < 1e-4 (beta2^t has decayed to 4.5e-5 by then).
+Parameters without a gradient (``absent_grad``, ``exp_params.adam_absent_grad``).  torch keeps a step counter per parameter
+and does not touch a parameter whose ``.grad`` is None.  That matters only where a parameter receives NO gradient in some steps
+-- in this repository CT-MCQ-VAE's per-action ``graph_discovers`` whose action is absent from a batch, ``ct_layer.mask`` in
+base-mode steps, the decoder in causal-mode steps; VanillaVAE / MCQ-VAE, where every parameter gets a gradient every step,
+step identically under all three values (tests/test_ct_gpu.py pins their 3-step trajectory):
+* ``"zero"`` (the default): ONE step counter for the whole buffer, and every element is updated every step.  A parameter
+  without a gradient sees a zero gradient: its first moment decays, it keeps drifting by its momentum, its bias correction
+  follows the global count.  The plain ``ctvae_adam_step`` / ``ctvae_adam_step_clipped`` launches, no block table.
+* ``"skip"``: a block without a gradient is not touched in that step -- parameter, both moments and its own step counter stay,
+  no weight decay.  ``torch.optim.Adam`` with ``zero_grad(set_to_none=True)``, current torch's default and what the CPU oracle
+  runs.
+* ``"skip_until_first"``: a block is frozen until its first gradient, where its counter starts; from then on it steps every
+  step, with a zero gradient when none arrived.  torch 1.12.1 under Lightning 1.6.5 (the reference's pinned stack), whose
+  ``zero_grad()`` keeps zero tensors.
+The two skip modes run ``ctvae_adam_step_blocks`` over a block table built once from the model's layout
+(``FlatParamMixin.adam_blocks``, clipped to the slice): one block per kernel-managed storage block (active when a gradient
+kernel wrote it since ``zero_grad``), per torch-level parameter (active when autograd produced its ``.grad``) and per member
+of a module bank (active when the bank was used AND the forward marked the member on the device: scorer 0, and scorer 1 + i
+iff some sample has action i); alignment gaps belong to no block and are never written.  What the host knows travels as a
+device word per block, constant per captured step signature (checked at capture), the rest is decided on the device, so a
+replayed hipGraph steps correctly.  Not available together with the DDP gradient exchange (VAEXperiment refuses it): the
+activity flags would have to be reduced across ranks with the gradient.  ``ct_layer.a_dense`` never has a non-zero gradient
+(its node has no outgoing edge) and never steps here; torch hands it an all-zero gradient and would apply weight decay to it.
+
+Deviation from ``torch.optim.Adam`` in every mode (documented, not pinned by a fixture):
+* beta1^t / beta2^t are accumulated in fp32 on the device (state[6..7], or per block); torch computes them in double on the
+  host.  After 10^4 steps the relative difference of the bias corrections is < 1e-4 (beta2^t has decayed to 4.5e-5 by then).
 
 Gradient clipping (Lightning's ``gradient_clip_val`` / ``gradient_clip_algorithm``, which the reference's YAMLs hand to the
 Trainer): ``clip_val`` None or <= 0 is off, and the step is the plain Adam launch.  Otherwise the step clips the optimizer's
@@ -42,9 +60,17 @@ def clip_settings(clip_val, algorithm=None):
     return (float(clip_val) if clip_val > 0 else None), algo.lower()
 
 
+def absent_grad_setting(value):
+    """Validated ``absent_grad`` (module docstring); None means the default, "zero"."""
+    v = "zero" if value is None else value
+    if not isinstance(v, str) or v not in K.ABSENT_GRAD_MODES:
+        raise ValueError(f"adam_absent_grad {value!r} is invalid: allowed are 'zero', 'skip' and 'skip_until_first'")
+    return v
+
+
 class FlatAdam:
     def __init__(self, model, lr, weight_decay=0.0, betas=(0.9, 0.999), eps=1e-8, params_slice=None, clip_val=None,
-                 clip_algorithm="norm"):
+                 clip_algorithm="norm", absent_grad="zero"):
         self.model = model
         flat = model.flat_params
         self.slice = params_slice if params_slice is not None else slice(0, flat.numel())
@@ -58,6 +84,56 @@ class FlatAdam:
         if self.clip_val is not None and self.clip_algorithm == "norm":
             self.clip_ws = K.grad_clip_workspace(flat.device)
             self.grad_norm = torch.zeros((), dtype=torch.float32, device=flat.device)
+        self.absent_grad = absent_grad_setting(absent_grad)
+        self.blocks = self.table = self.host_pattern = None
+        if self.absent_grad != "zero":
+            self._build_block_table(n, flat.device)
+
+    # -- block table (absent_grad "skip" / "skip_until_first") ---------------------------------------------
+    def _build_block_table(self, n, device):
+        """self.blocks: [(lo, hi, kind, ref, member)] of model.adam_blocks() clipped to the slice, offsets relative to it;
+        self.table: its device side.  Every bank module gets its words of the hit vector (``member_hits``)."""
+        start = int(self.slice.start or 0)
+        blocks = []
+        for lo, hi, kind, ref, member in self.model.adam_blocks():
+            lo, hi = max(lo - start, 0), min(hi - start, n)
+            if lo < hi:
+                blocks.append((lo, hi, kind, ref, member))
+        blocks.sort(key=lambda b: b[0])
+        banks, base, hit_index = {}, 0, []
+        for _, _, kind, ref, member in blocks:
+            if kind == "bank":
+                banks.setdefault(id(ref[0]), [ref[0], 0])
+                banks[id(ref[0])][1] = max(banks[id(ref[0])][1], member + 1)
+        for ent in banks.values():
+            ent.append(base)
+            base += ent[1]
+        for _, _, kind, ref, member in blocks:
+            hit_index.append(banks[id(ref[0])][2] + member if kind == "bank" else -1)
+        self.blocks = blocks
+        self.table = K.AdamBlockTable([(b[0], b[1]) for b in blocks], hit_index, n, base, device)
+        self._patterns = {}
+        if self.table.hits.is_cuda:          # (on the CPU the table can be built and inspected; the step itself is a HIP kernel)
+            for mod, count, off in banks.values():
+                mod.member_hits = self.table.hits[off:off + count]
+
+    def _host_pattern(self):
+        """What the host knows of this step's gradients, one 0 / 1 per block (a bank member: whether its bank was used)."""
+        out = []
+        for _, _, kind, ref, _ in self.blocks:
+            if kind == "kernel":
+                out.append(int(ref.written))
+            elif kind == "torch":
+                out.append(int(self.model.torch_grad_present(ref)))
+            elif kind == "bank":
+                out.append(int(self.model.torch_grad_present(ref[1])))
+            else:                            # a caller's own record: ref() -> bool
+                out.append(int(bool(ref())))
+        return tuple(out)
+
+    def block_steps(self):
+        """Per-block step counts (device, float), in the order of ``blocks``."""
+        return self.table.state[:, 0]
 
     def set_lr(self, lr):
         self.lr = lr
@@ -65,21 +141,43 @@ class FlatAdam:
 
     def step(self, grad_scale=1.0):
         self.model.gather_torch_grads()
-        if self.clip_val is None:
-            K.adam_step(self.model.flat_params[self.slice], self.model.flat_grads[self.slice], self.exp_avg, self.exp_avg_sq,
-                        self.state, grad_scale)
+        p, g = self.model.flat_params[self.slice], self.model.flat_grads[self.slice]
+        if self.absent_grad != "zero":
+            pat = self._host_pattern()
+            present = self._patterns.get(pat)
+            if present is None:
+                if p.is_cuda and torch.cuda.is_current_stream_capturing():
+                    raise RuntimeError("FlatAdam: the step being captured has gradients for other blocks than every eager step "
+                                       "before it; a captured step's host-known activity must be constant")
+                present = self._patterns[pat] = torch.tensor(pat, dtype=torch.int32, device=p.device)
+            self.host_pattern = pat
+            K.adam_step_blocks(p, g, self.exp_avg, self.exp_avg_sq, self.state, self.table, present, self.absent_grad, grad_scale,
+                               None if self.clip_val is None else self.clip_algorithm, self.clip_val, self.clip_ws, self.grad_norm)
+        elif self.clip_val is None:
+            K.adam_step(p, g, self.exp_avg, self.exp_avg_sq, self.state, grad_scale)
         else:
-            K.adam_step_clipped(self.model.flat_params[self.slice], self.model.flat_grads[self.slice], self.exp_avg,
-                                self.exp_avg_sq, self.state, grad_scale, self.clip_algorithm, self.clip_val, self.clip_ws,
-                                self.grad_norm)
+            K.adam_step_clipped(p, g, self.exp_avg, self.exp_avg_sq, self.state, grad_scale, self.clip_algorithm, self.clip_val,
+                                self.clip_ws, self.grad_norm)
 
     def zero_grad(self, set_to_none=False):
         self.model.zero_grad()
 
     def state_dict(self):
-        return {"exp_avg": self.exp_avg, "exp_avg_sq": self.exp_avg_sq, "state": self.state}
+        sd = {"exp_avg": self.exp_avg, "exp_avg_sq": self.exp_avg_sq, "state": self.state}
+        if self.absent_grad != "zero":       # (the default's state layout is what it was)
+            sd["absent_grad"] = self.absent_grad
+            sd["block_state"] = self.table.state      # [nb, 4]: step, beta1^step, beta2^step, seen
+        return sd
 
     def load_state_dict(self, sd):
+        theirs = sd.get("absent_grad", "zero")
+        if theirs != self.absent_grad:
+            raise RuntimeError(f"optimizer state was written under adam_absent_grad={theirs!r}, this run uses "
+                               f"{self.absent_grad!r}: the step counters of the two do not translate")
+        if self.absent_grad != "zero":
+            if tuple(sd["block_state"].shape) != tuple(self.table.state.shape):
+                raise RuntimeError("optimizer state has another block table than this model")
+            self.table.state.copy_(sd["block_state"])
         self.exp_avg.copy_(sd["exp_avg"])
         self.exp_avg_sq.copy_(sd["exp_avg_sq"])
         self.state[:8].copy_(sd["state"][:8])      # (states saved before the ticket word existed have 8 entries)

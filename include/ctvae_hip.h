@@ -608,6 +608,30 @@ size_t ctvae_grad_clip_workspace_floats(void);
 int ctvae_adam_step_clipped(float* params, const float* grads, float* exp_avg, float* exp_avg_sq, float* state, long n,
                             float grad_scale, int algorithm, float clip_val, float* workspace, float* norm_out, void* stream);
 
+/* Block-aware Adam: torch.optim.Adam's treatment of parameters WITHOUT a gradient (FlatAdam absent_grad "skip" /
+ * "skip_until_first").  A block table lies over the n floats: block_lo / block_hi (device, nb sorted disjoint ranges [lo, hi),
+ * 32-bit, hi <= n; floats in no range are alignment gaps and are neither read nor written), block_state (device, 4 floats
+ * per block: step, beta1^step, beta2^step, seen; created as {0, 1, 1, 0}) and active (device, nb words).
+ *   ctvae_adam_step_blocks  ctvae_adam_step / ctvae_adam_step_clipped (algorithm CTVAE_ADAM_NO_CLIP, CTVAE_CLIP_NORM or _VALUE; same `state`,
+ *                           same arithmetic) on the blocks whose active word is non-zero, each with the bias corrections of its
+ *                           own step count; every other float keeps parameter and moments bit for bit.  A 16-byte quad that
+ *                           straddles a block boundary is handled float by float.  The workgroup that finishes last advances
+ *                           step / beta^step of the active blocks and sets their seen word, and counts the launch in state[0].
+ *                           The norm of CTVAE_CLIP_NORM runs over all n gradients: inactive blocks and gaps must hold zeros.
+ *   ctvae_adam_block_flags  fills `active` in front of it (one small launch): active[b] = present[b], for a block with
+ *                           hit_index[b] >= 0 (a member of a parameter bank, whose presence only the device knows) only if
+ *                           hits[hit_index[b]] != 0 as well; until_first != 0: a block whose seen word is set is active
+ *                           whatever else.  Clears the nhits hit words.
+ *   ctvae_adam_mark_members the forward pass's side: hits[0] = 1 and hits[group[b]] = 1 for the B samples' groups (int32,
+ *                           values outside [0, nhits) are ignored; B = 0: member 0 only). */
+#define CTVAE_ADAM_NO_CLIP 2
+int ctvae_adam_mark_members(int* hits, int nhits, const int* group, int B, void* stream);
+int ctvae_adam_block_flags(const int* present, const int* hit_index, int* hits, int nhits, const float* block_state, int* active,
+                           int nb, int until_first, void* stream);
+int ctvae_adam_step_blocks(float* params, const float* grads, float* exp_avg, float* exp_avg_sq, float* state, long n,
+                           float grad_scale, int algorithm, float clip_val, float* workspace, float* norm_out,
+                           const int* block_lo, const int* block_hi, float* block_state, const int* active, int nb, void* stream);
+
 /* Input side: the reference's per-sample pipeline ToTensor -> CenterCrop(crop) -> Resize(size)
  * (dataset.py:72-80; bilinear, align_corners=False, no antialias -- what transforms.Resize does to a tensor; images smaller
  * than the crop are zero-padded as torchvision's center_crop does) for a batch of rows of a uint8 dataset
