@@ -166,6 +166,10 @@ int launch_group_var_argmin(const float* z, const float* gvar, const uint8_t* ac
 int launch_image_grid_u8(const float* x, long sN, long sC, long sH, long sW, int N, int C, int H, int W, int nrow, int pad,
                          int normalize, int has_range, float lo, float hi, float pad_value, int scanlines, uint8_t* out,
                          size_t out_bytes, float* ws, size_t ws_bytes, hipStream_t st);
+int launch_image_grid_each_u8(const float* x, long sN, long sC, long sH, long sW, int N, int C, int H, int W, int nrow, int pad,
+                              int normalize, int has_range, float lo, float hi, float pad_value, int scanlines, uint8_t* out,
+                              size_t out_bytes, float* ws, size_t ws_bytes, hipStream_t st);
+int launch_action_hits(const float* probas, const float* action, int N, int A, int* counts, hipStream_t st);
 int launch_loss_forward(const float* r, const float* x, long n, const float* mu, long mu_rs, const float* lv, long lv_rs,
                         int B, int L, float M_N, const float* extra, float* out4, float* ws, size_t ws_bytes,
                         hipStream_t st, float logcosh_alpha, float* g_r = nullptr, float* g_mu = nullptr, float* g_lv = nullptr,
@@ -1040,6 +1044,18 @@ int ctvae_image_grid_u8(const float* x, long stride_n, long stride_c, long strid
                         int scanlines, uint8_t* out, size_t out_bytes, float* workspace, size_t workspace_bytes, void* stream) {
   return launch_image_grid_u8(x, stride_n, stride_c, stride_h, stride_w, N, C, H, W, nrow, padding, normalize, has_range, range_lo,
                               range_hi, pad_value, scanlines, out, out_bytes, workspace, workspace_bytes, (hipStream_t)stream);
+}
+
+int ctvae_image_grid_each_u8(const float* x, long stride_n, long stride_c, long stride_h, long stride_w, int N, int C, int H, int W,
+                             int nrow, int padding, int normalize, int has_range, float range_lo, float range_hi, float pad_value,
+                             int scanlines, uint8_t* out, size_t out_bytes, float* workspace, size_t workspace_bytes, void* stream) {
+  return launch_image_grid_each_u8(x, stride_n, stride_c, stride_h, stride_w, N, C, H, W, nrow, padding, normalize, has_range,
+                                   range_lo, range_hi, pad_value, scanlines, out, out_bytes, workspace, workspace_bytes,
+                                   (hipStream_t)stream);
+}
+
+int ctvae_action_hits(const float* probas, const float* action, int N, int A, int* counts, void* stream) {
+  return launch_action_hits(probas, action, N, A, counts, (hipStream_t)stream);
 }
 
 size_t ctvae_adam_state_floats(void) { return adam_state_floats(); }

@@ -10,7 +10,9 @@ as the scanlines of a PNG; the host side is one device -> host copy, ``zlib.comp
 The arithmetic is restated from torchvision's published source, not compared against it (the package is absent).  Known
 differences: a batch of ONE image is framed by the padding like any other (``make_grid`` returns it bare); NaN does not enter the
 batch's minimum / maximum and is written as byte 0 (torch propagates it and blanks the picture); only float32 batches of 1 or 3
-channels.  There is no CPU path: a tensor that is not on the GPU is an error.
+channels.  ``scale_each=True`` (every image scaled by its own minimum / maximum, what a rollout sheet needs: rollout.py) is a
+second entry point with the same two passes, segmented by image, and is unpinned against torchvision in the same way.
+There is no CPU path: a tensor that is not on the GPU is an error.
 """
 import struct
 import zlib
@@ -40,10 +42,12 @@ def _as_batch(x: torch.Tensor) -> torch.Tensor:
 
 
 def make_grid_u8(x: torch.Tensor, nrow: int = 8, padding: int = 2, normalize: bool = False, value_range=None,
-                 pad_value: float = 0.0, scanlines: bool = False, *, out: torch.Tensor = None) -> torch.Tensor:
+                 pad_value: float = 0.0, scanlines: bool = False, *, scale_each: bool = False,
+                 out: torch.Tensor = None) -> torch.Tensor:
     """The grid of batch x as bytes on x's device: [Hg, Wg, 3], or with ``scanlines`` [Hg, 1 + 3*Wg] (a zero in front of every
-    row: PNG filter type 0).  Defaults are torchvision's.  ``out``: a flat uint8 buffer to write into (16-byte aligned, the
-    stream's length rounded up to a multiple of 4 at least); the result is a view of it."""
+    row: PNG filter type 0).  Defaults are torchvision's.  ``scale_each``: with ``normalize`` and no ``value_range`` every image
+    is scaled by its own minimum and maximum instead of the batch's (otherwise it changes nothing).  ``out``: a flat uint8 buffer
+    to write into (16-byte aligned, the stream's length rounded up to a multiple of 4 at least); the result is a view of it."""
     with torch.no_grad():
         x = _as_batch(x)
         N, C, H, W = x.shape
@@ -56,9 +60,10 @@ def make_grid_u8(x: torch.Tensor, nrow: int = 8, padding: int = 2, normalize: bo
             raise ValueError("out must be a flat contiguous uint8 tensor on the batch's device")
         has_range = value_range is not None
         lo, hi = (float(value_range[0]), float(value_range[1])) if has_range else (0.0, 1.0)
+        entry = "ctvae_image_grid_each_u8" if (scale_each and normalize and not has_range) else "ctvae_image_grid_u8"
         with torch.cuda.device(x.device):
             ws = native.workspace(x.device)
-            native.call("ctvae_image_grid_u8", x.data_ptr(), x.stride(0), x.stride(1), x.stride(2), x.stride(3), N, C, H, W,
+            native.call(entry, x.data_ptr(), x.stride(0), x.stride(1), x.stride(2), x.stride(3), N, C, H, W,
                         int(nrow), int(padding), int(bool(normalize)), int(has_range), lo, hi, float(pad_value), int(bool(scanlines)),
                         out.data_ptr(), out.numel(), ws.data_ptr(), ws.numel() * 4)
         return out[:total].view(Hg, pitch) if scanlines else out[:total].view(Hg, Wg, 3)
@@ -77,10 +82,10 @@ def png_bytes(scanline_stream: bytes, width: int, height: int) -> bytes:
 
 
 def save_image(x: torch.Tensor, path, nrow: int = 8, padding: int = 2, normalize: bool = False, value_range=None,
-               pad_value: float = 0.0) -> None:
+               pad_value: float = 0.0, scale_each: bool = False) -> None:
     """``torchvision.utils.save_image`` for PNG files: the grid's scanlines come from the GPU in one copy."""
     grid = make_grid_u8(x, nrow=nrow, padding=padding, normalize=normalize, value_range=value_range, pad_value=pad_value,
-                        scanlines=True)
+                        scanlines=True, scale_each=scale_each)
     height, pitch = grid.shape
     data = png_bytes(grid.cpu().numpy().tobytes(), (pitch - 1) // 3, height)
     with open(path, "wb") as f:

@@ -559,6 +559,24 @@ int ctvae_image_grid_u8(const float* x, long stride_n, long stride_c, long strid
                         int nrow, int padding, int normalize, int has_range, float range_lo, float range_hi, float pad_value,
                         int scanlines, uint8_t* out, size_t out_bytes, float* workspace, size_t workspace_bytes, void* stream);
 
+/* The same grid with every image scaled by its OWN range: torchvision's make_grid(normalize=True, scale_each=True), i.e. what
+ * saving each picture on its own with normalize=True shows (the reference's apply_action notebook, cell 6).  Same parameters,
+ * layout, byte conversion and NaN rule; image k uses lo_k / hi_k = its own minimum / maximum (an all-NaN image is all byte 0).
+ * Two launches: a segmented range pass (P = min(16, ceil(C*H*W / 4096)) workgroups per image, N <= 65535; workspace: device,
+ * 8-byte aligned, at least N*P*8 bytes) and the compose pass.  With has_range != 0 or normalize == 0 every image has the same
+ * range and the call is ctvae_image_grid_u8 itself. */
+int ctvae_image_grid_each_u8(const float* x, long stride_n, long stride_c, long stride_h, long stride_w, int N, int C, int H, int W,
+                             int nrow, int padding, int normalize, int has_range, float range_lo, float range_hi, float pad_value,
+                             int scanlines, uint8_t* out, size_t out_bytes, float* workspace, size_t workspace_bytes, void* stream);
+
+/* Per-action hit counts of CT-MCQ-VAE's causal mode (rollout.py; the reference's apply_action notebook, cells 7 and 9):
+ * probas [N][A] = forward_causal's action probabilities, action [N][A] = the one-hot action, counts [A][3] int32.  With V = A / 2,
+ * a = argmax(action row), p = argmax(probas row), every row ADDS 1 to counts[a][0], (p == a) to counts[a][1] and
+ * (p % V == a % V) to counts[a][2] -- rows, directed hits, direction-agnostic hits; successive launches accumulate, and integer
+ * adds make the result independent of their order.  argmax is torch.argmax: the first maximal value wins, NaN counts as maximal
+ * and the first NaN wins.  A even, 2 <= A <= 256; N == 0 is a successful no-op; N < 0, another A or a NULL pointer returns -22. */
+int ctvae_action_hits(const float* probas, const float* action, int N, int A, int* counts, void* stream);
+
 /* MSSIMVAE's reconstruction loss (mssim_vae.py:182-279): 1 - prod_{i<4} (mcs_i^w_i * mssim_4^w_4) over five levels of SSIM with the
  * reference's 11-tap window (2x2 average pooling between levels), for NHWC pictures a (the reconstruction) and b [B,64,64,C].
  * window [11] and weights [5]: HOST arrays (the window as the reference builds it: exp(+(x-5)^2 / 4.5), normalised).
