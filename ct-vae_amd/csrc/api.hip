@@ -129,6 +129,9 @@ size_t grad_clip_workspace_floats();
 int launch_adam_mark_members(int* hits, int nhits, const int* group, int B, hipStream_t st);
 int launch_adam_block_flags(const int* present, const int* hit_index, int* hits, int nhits, const float* bstate, int* active,
                             int nb, int until_first, hipStream_t st);
+int launch_adam_block_flags_local(const int* present, const int* hit_index, int* hits, int nhits, int* active, int nb,
+                                  hipStream_t st);
+int launch_adam_block_flags_finish(const float* bstate, int* active, int nb, int until_first, hipStream_t st);
 int launch_adam_blocks(float* p, const float* g, float* m, float* v, float* state, long n, float grad_scale, int algorithm,
                        float clip, float* ws, float* norm_out, const int* blk_lo, const int* blk_hi, float* bstate,
                        const int* active, int nb, hipStream_t st);
@@ -1096,6 +1099,16 @@ int ctvae_adam_block_flags(const int* present, const int* hit_index, int* hits, 
                            int nb, int until_first, void* stream) {
   if (!present || !hit_index || !block_state || !active || nb < 1 || nhits < 0 || (nhits > 0 && !hits)) return kErrBadArg;
   return launch_adam_block_flags(present, hit_index, hits, nhits, block_state, active, nb, until_first, (hipStream_t)stream);
+}
+
+int ctvae_adam_block_flags_local(const int* present, const int* hit_index, int* hits, int nhits, int* active, int nb, void* stream) {
+  if (!present || !hit_index || !active || nb < 1 || nhits < 0 || (nhits > 0 && !hits)) return kErrBadArg;
+  return launch_adam_block_flags_local(present, hit_index, hits, nhits, active, nb, (hipStream_t)stream);
+}
+
+int ctvae_adam_block_flags_finish(const float* block_state, int* active, int nb, int until_first, void* stream) {
+  if (!block_state || !active || nb < 1) return kErrBadArg;
+  return launch_adam_block_flags_finish(block_state, active, nb, until_first, (hipStream_t)stream);
 }
 
 int ctvae_adam_step_blocks(float* params, const float* grads, float* exp_avg, float* exp_avg_sq, float* state, long n,

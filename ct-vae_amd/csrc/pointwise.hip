@@ -648,6 +648,32 @@ __global__ __launch_bounds__(256) void adam_block_flags_kernel(const int* __rest
   for (int k = threadIdx.x; k < nhits; k += 256) hits[k] = 0;
 }
 
+// The two halves of adam_block_flags_kernel for a step whose flags are reduced across ranks in between (MAX: a block steps
+// everywhere iff it got a gradient somewhere).  Local half: raw[b] = present[b] && hit(b), whatever the block's history; consumes
+// the hit words.
+__global__ __launch_bounds__(256) void adam_block_flags_local_kernel(const int* __restrict__ present,
+                                                                     const int* __restrict__ hit_index, int* hits, int nhits,
+                                                                     int* __restrict__ active, int nb) {
+  for (int b = threadIdx.x; b < nb; b += 256) {
+    int a = present[b] != 0;
+    const int h = hit_index[b];
+    if (h >= 0) a = a && (h < nhits && hits[h] != 0);
+    active[b] = a;
+  }
+  __syncthreads();
+  for (int k = threadIdx.x; k < nhits; k += 256) hits[k] = 0;
+}
+
+// Finish half, on the reduced words in place: 0 / 1 again, and until_first's "has stepped once steps ever after".
+__global__ __launch_bounds__(256) void adam_block_flags_finish_kernel(const float* __restrict__ bstate, int* __restrict__ active,
+                                                                      int nb, int until_first) {
+  for (int b = threadIdx.x; b < nb; b += 256) {
+    int a = active[b] != 0;
+    if (until_first && bstate[4 * b + 3] != 0.f) a = 1;
+    active[b] = a;
+  }
+}
+
 // Straight-through Bernoulli sample through a 2-class Gumbel-softmax (tau = 1, hard) of
 // log(clamp([1-p, p], 1e-4)) (ct_mcq_vae.py:126,177-183).  noise = 2 standard Gumbel draws/element.
 __global__ __launch_bounds__(256) void gumbel_st_fwd_kernel(const float* __restrict__ p, const float* __restrict__ noise,
@@ -792,6 +818,19 @@ int launch_adam_block_flags(const int* present, const int* hit_index, int* hits,
                             int nb, int until_first, hipStream_t st) {
   hipLaunchKernelGGL(adam_block_flags_kernel, dim3(1), dim3(256), 0, st, present, hit_index, hits, nhits, bstate, active, nb,
                      until_first);
+  CTVAE_LAUNCH_CHECK();
+  return 0;
+}
+
+int launch_adam_block_flags_local(const int* present, const int* hit_index, int* hits, int nhits, int* active, int nb,
+                                  hipStream_t st) {
+  hipLaunchKernelGGL(adam_block_flags_local_kernel, dim3(1), dim3(256), 0, st, present, hit_index, hits, nhits, active, nb);
+  CTVAE_LAUNCH_CHECK();
+  return 0;
+}
+
+int launch_adam_block_flags_finish(const float* bstate, int* active, int nb, int until_first, hipStream_t st) {
+  hipLaunchKernelGGL(adam_block_flags_finish_kernel, dim3(1), dim3(256), 0, st, bstate, active, nb, until_first);
   CTVAE_LAUNCH_CHECK();
   return 0;
 }

@@ -86,6 +86,13 @@ class GradBucketAllReduce:
             return []
         return [dist.all_reduce(b, op=dist.ReduceOp.SUM, group=self.pg, async_op=True) for b in parts]
 
+    def all_reduce_flags(self, flags):
+        """MAX all-reduce, in place, of FlatAdam's int32 [nb] block-activity flags (``FlatAdam.step(reduce_flags=...)``): a
+        block counts as active everywhere when some rank has a gradient for it.  One small collective, stream-ordered like the
+        gradient buckets; the optimizer issues it before them, so that it travels while they are being queued."""
+        if self.active:
+            dist.all_reduce(flags, op=dist.ReduceOp.MAX, group=self.pg)
+
     def wait(self, works):
         for w in works:
             w.wait()

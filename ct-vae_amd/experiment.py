@@ -5,8 +5,8 @@
 ``M_N=1.0`` with a ``val_`` key prefix for validation, Adam(lr=LR, weight_decay) + ExponentialLR(gamma)
 over ``model.parameters()`` or ``getattr(model, update_parameters).parameters()``, with the Trainer's gradient clipping
 (``gradient_clip_val`` / ``gradient_clip_algorithm``, see optim.py) in front of the step; ``exp_params.adam_absent_grad``
-("zero", the default; "skip"; "skip_until_first") chooses what the step does to parameters without a gradient (optim.py; the
-two skip modes are refused together with a DDP gradient exchange).  What changes is the
+("zero", the default; "skip"; "skip_until_first") chooses what the step does to parameters without a gradient (optim.py; under
+a DDP gradient exchange the two skip modes MAX-reduce their per-block activity flags across ranks, ``ddp_step``).  What changes is the
 machinery: one flat fused Adam launch, one bucketed RCCL all-reduce, and scalars fetched with ONE device
 -> host copy every ``log_every`` steps instead of one ``.item()`` sync per key per step (experiment.py:95-96).
 
@@ -100,6 +100,11 @@ class _GraphedTrainStep:
                     raise RuntimeError("steps of one graph signature got gradients for different parameter blocks: "
                                        f"{sum(a != b for a, b in zip(pat, self.pattern))} blocks differ")
                 self.pattern = pat
+        elif exp.optimizer.absent_grad != "zero":
+            # the step itself is eager (run()), so eager steps of one signature may differ; what a REPLAY's step needs is the
+            # activity of the launches it repeats, the capture step's -- the host's own record is by then the last Python-run
+            # step's, maybe another signature's
+            self.pattern = exp.optimizer.current_pattern()
         # detached: a live loss keeps the step's autograd graph -- and with it the AccumulateGrad nodes of the parameters
         # torch accumulates itself (the CT layer's banks), bound to the stream they were made on -- alive into the next
         # signature's capture, where running them on that other stream ends the capture with a fault
@@ -125,8 +130,7 @@ class _GraphedTrainStep:
             losses = self._body()
         self.seen += 1
         if exp.ddp is not None:
-            exp.ddp.all_reduce()
-            exp.optimizer.step(grad_scale=exp.ddp.grad_scale)
+            exp.ddp_step(self.pattern)
         exp.global_step += 1
         return losses
 
@@ -163,9 +167,10 @@ class VAEXperiment:
         self.model = vae_model
         self.params = params
         self.ddp = ddp
-        if absent_grad_setting(params.get("adam_absent_grad")) != "zero" and ddp is not None:
-            raise ValueError(f"adam_absent_grad={params['adam_absent_grad']!r} is not available with a DDP gradient exchange: the "
-                             "per-block activity flags are not reduced across ranks yet, and ranks must not step differently")
+        if absent_grad_setting(params.get("adam_absent_grad")) != "zero" and ddp is not None and not hasattr(ddp, "all_reduce_flags"):
+            raise ValueError(f"adam_absent_grad={params['adam_absent_grad']!r} is not available with this DDP gradient exchange: "
+                             "it cannot reduce the per-block activity flags across ranks (no all_reduce_flags), and ranks must "
+                             "not step differently")
         self.curr_device = None
         self.log_every = log_every
         self.log_file = log_file
@@ -338,12 +343,28 @@ class VAEXperiment:
             self.model._rng_state = sd["model_rng"].to(dev)
         K.bump_param_epoch()
 
+    def ddp_step(self, pattern=None):
+        """Gradient exchange + optimizer step of a data-parallel run (1 / world folded into the step).  In the skip modes the
+        step first forms this rank's block flags; their MAX all-reduce goes out from inside the step (``reduce_flags``) with
+        the gradient buckets right behind it, so the small collective is under way before the large ones are queued.
+        pattern: see FlatAdam.step (a replayed captured step hands over its capture step's)."""
+        ddp, opt = self.ddp, self.optimizer
+        if opt.absent_grad == "zero":
+            ddp.all_reduce()
+            opt.step(grad_scale=ddp.grad_scale)
+            return
+
+        def flags_then_grads(flags):
+            ddp.all_reduce_flags(flags)
+            ddp.all_reduce()
+
+        opt.step(grad_scale=ddp.grad_scale, reduce_flags=flags_then_grads, pattern=pattern)
+
     def optimizer_step(self):
-        scale = 1.0
         if self.ddp is not None:
-            self.ddp.all_reduce()
-            scale = self.ddp.grad_scale
-        self.optimizer.step(grad_scale=scale)
+            self.ddp_step()
+        else:
+            self.optimizer.step()
         self.global_step += 1
 
     def fit(self, train_batches, val_batches=None, max_epochs=1, on_epoch_end=None, start_epoch=0, test_batches=None):

@@ -2528,21 +2528,43 @@ def adam_mark_members(hits, group=None):
     native.call("ctvae_adam_mark_members", hits.data_ptr(), hits.numel(), native.ptr(group), 0 if group is None else group.numel())
 
 
+def adam_block_flags_local(table, present):
+    """First half of adam_step_blocks' flags for a step whose flags are reduced across ranks: table.active[b] = present[b],
+    for a bank member and its hit word -- this rank's gradients alone, whatever the blocks' history.  Consumes the hit words."""
+    _req_cuda(table.active, present)
+    if present.numel() != table.nb or present.dtype != torch.int32:
+        raise ValueError("adam_block_flags_local: present is one int32 word per block of the table")
+    native.call("ctvae_adam_block_flags_local", present.data_ptr(), table.hit_index.data_ptr(), table.hits.data_ptr(), table.nhits,
+                table.active.data_ptr(), table.nb)
+
+
+def adam_block_flags_finish(table, mode):
+    """Second half, on the reduced table.active in place: "skip_until_first" adds the blocks that have stepped before.  After
+    it adam_step_blocks runs with ``flags_final=True``."""
+    if mode not in ABSENT_GRAD_MODES[1:]:
+        raise ValueError("adam_block_flags_finish: mode is 'skip' or 'skip_until_first'")
+    _req_cuda(table.active)
+    native.call("ctvae_adam_block_flags_finish", table.state.data_ptr(), table.active.data_ptr(), table.nb,
+                1 if mode == "skip_until_first" else 0)
+
+
 def adam_step_blocks(flat_params, flat_grads, exp_avg, exp_avg_sq, state, table, present, mode, grad_scale=1.0, algorithm=None,
-                     clip_val=None, workspace=None, norm_out=None):
+                     clip_val=None, workspace=None, norm_out=None, flags_final=False):
     """adam_step / adam_step_clipped (algorithm None / "norm" / "value") on the blocks of ``table`` that have a gradient in this
     step, every block under its own step counter; the others keep parameter, moments and counter.  present: int32 [nb] device
     tensor, what the host knows of the blocks' gradients; a bank member also needs its hit word (adam_mark_members).
-    mode: "skip" or "skip_until_first"."""
+    mode: "skip" or "skip_until_first".  flags_final: table.active already holds the step's flags (adam_block_flags_local, the
+    caller's reduction, adam_block_flags_finish); the flags launch is left out and ``present`` is not read (may be None)."""
     if not flat_params.is_cuda:
         raise RuntimeError(f"FlatAdam absent_grad={mode!r} needs device tensors: the block-aware step (ctvae_adam_step_blocks) "
                            "is a HIP kernel, there is no CPU fallback and no CPU test double of it")
-    _req_cuda(flat_grads, present)
-    if mode not in ABSENT_GRAD_MODES[1:] or flat_params.numel() != table.n or present.numel() != table.nb:
+    _req_cuda(flat_grads, table.active if flags_final else present)
+    if mode not in ABSENT_GRAD_MODES[1:] or flat_params.numel() != table.n or (not flags_final and present.numel() != table.nb):
         raise ValueError("adam_step_blocks: mode is 'skip' or 'skip_until_first'; table and present flags must fit the buffers")
     bump_param_epoch()
-    native.call("ctvae_adam_block_flags", present.data_ptr(), table.hit_index.data_ptr(), table.hits.data_ptr(), table.nhits,
-                table.state.data_ptr(), table.active.data_ptr(), table.nb, 1 if mode == "skip_until_first" else 0)
+    if not flags_final:
+        native.call("ctvae_adam_block_flags", present.data_ptr(), table.hit_index.data_ptr(), table.hits.data_ptr(), table.nhits,
+                    table.state.data_ptr(), table.active.data_ptr(), table.nb, 1 if mode == "skip_until_first" else 0)
     native.call("ctvae_adam_step_blocks", flat_params.data_ptr(), flat_grads.data_ptr(), exp_avg.data_ptr(), exp_avg_sq.data_ptr(),
                 state.data_ptr(), flat_params.numel(), float(grad_scale), CLIP_OFF if algorithm is None else CLIP_ALGORITHMS[algorithm],
                 0.0 if clip_val is None else float(clip_val), native.ptr(workspace), native.ptr(norm_out), table.lo.data_ptr(),

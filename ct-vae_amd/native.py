@@ -113,6 +113,8 @@ SIGNATURES = {
     "ctvae_adam_step_clipped": [_fp, _fp, _fp, _fp, _fp, _l, _f, _i, _f, _fp, _fp, _vp],
     "ctvae_adam_mark_members": [_fp, _i, _fp, _i, _vp],
     "ctvae_adam_block_flags": [_fp, _fp, _fp, _i, _fp, _fp, _i, _i, _vp],
+    "ctvae_adam_block_flags_local": [_fp, _fp, _fp, _i, _fp, _i, _vp],
+    "ctvae_adam_block_flags_finish": [_fp, _fp, _i, _i, _vp],
     "ctvae_adam_step_blocks": [_fp, _fp, _fp, _fp, _fp, _l, _f, _i, _f, _fp, _fp, _fp, _fp, _fp, _fp, _i, _vp],
     "ctvae_mssim_forward": [_fp, _fp, _fp, _fp, _fp, _fp, _fp, _i, _i, _i, _i, _vp],
     "ctvae_mssim_backward": [_fp, _fp, _fp, _fp, _fp, _fp, _i, _i, _i, _i, _vp],

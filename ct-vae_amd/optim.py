@@ -25,8 +25,11 @@ kernel wrote it since ``zero_grad``), per torch-level parameter (active when aut
 of a module bank (active when the bank was used AND the forward marked the member on the device: scorer 0, and scorer 1 + i
 iff some sample has action i); alignment gaps belong to no block and are never written.  What the host knows travels as a
 device word per block, constant per captured step signature (checked at capture), the rest is decided on the device, so a
-replayed hipGraph steps correctly.  Not available together with the DDP gradient exchange (VAEXperiment refuses it): the
-activity flags would have to be reduced across ranks with the gradient.  ``ct_layer.a_dense`` never has a non-zero gradient
+replayed hipGraph steps correctly.  Data-parallel training (``step(reduce_flags=...)``) follows torch DDP with
+``find_unused_parameters=True``: the flags are formed from this rank's gradients alone, MAX-reduced across ranks, and only then
+does "skip_until_first" add the blocks that have stepped before -- a block steps on EVERY rank, with the gradient's mean, iff
+it got a gradient on at least one (a rank where it got none contributes its zeros), so the per-block state stays the same on
+all ranks while they run different modes in one step.  ``ct_layer.a_dense`` never has a non-zero gradient
 (its node has no outgoing edge) and never steps here; torch hands it an all-zero gradient and would apply weight decay to it.
 
 Deviation from ``torch.optim.Adam`` in every mode (documented, not pinned by a fixture):
@@ -131,6 +134,11 @@ class FlatAdam:
                 out.append(int(bool(ref())))
         return tuple(out)
 
+    def current_pattern(self):
+        """The host-known activity ``step()`` would use now (skip modes), for a caller that hands it back later as ``pattern``."""
+        self.model.gather_torch_grads()
+        return self._host_pattern()
+
     def block_steps(self):
         """Per-block step counts (device, float), in the order of ``blocks``."""
         return self.table.state[:, 0]
@@ -139,11 +147,16 @@ class FlatAdam:
         self.lr = lr
         self.state[1:2].fill_(lr)
 
-    def step(self, grad_scale=1.0):
+    def step(self, grad_scale=1.0, reduce_flags=None, pattern=None):
+        """reduce_flags (skip modes only; data-parallel training): a callable that MAX-reduces the int32 [nb] flags tensor it
+        is handed across ranks, in place and ordered on the current stream.  The step then runs local flags -> reduce_flags ->
+        finish -> update, so that a block steps on every rank iff it got a gradient on at least one.  pattern: the host-known
+        activity to use instead of the model's current one (a replayed captured step: the host still holds whatever the last
+        step that ran Python left)."""
         self.model.gather_torch_grads()
         p, g = self.model.flat_params[self.slice], self.model.flat_grads[self.slice]
         if self.absent_grad != "zero":
-            pat = self._host_pattern()
+            pat = self._host_pattern() if pattern is None else tuple(pattern)
             present = self._patterns.get(pat)
             if present is None:
                 if p.is_cuda and torch.cuda.is_current_stream_capturing():
@@ -151,8 +164,13 @@ class FlatAdam:
                                        "before it; a captured step's host-known activity must be constant")
                 present = self._patterns[pat] = torch.tensor(pat, dtype=torch.int32, device=p.device)
             self.host_pattern = pat
+            if reduce_flags is not None:
+                K.adam_block_flags_local(self.table, present)
+                reduce_flags(self.table.active)
+                K.adam_block_flags_finish(self.table, self.absent_grad)
             K.adam_step_blocks(p, g, self.exp_avg, self.exp_avg_sq, self.state, self.table, present, self.absent_grad, grad_scale,
-                               None if self.clip_val is None else self.clip_algorithm, self.clip_val, self.clip_ws, self.grad_norm)
+                               None if self.clip_val is None else self.clip_algorithm, self.clip_val, self.clip_ws, self.grad_norm,
+                               flags_final=reduce_flags is not None)
         elif self.clip_val is None:
             K.adam_step(p, g, self.exp_avg, self.exp_avg_sq, self.state, grad_scale)
         else:

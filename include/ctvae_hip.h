@@ -640,12 +640,20 @@ int ctvae_adam_step_clipped(float* params, const float* grads, float* exp_avg, f
  *                           hit_index[b] >= 0 (a member of a parameter bank, whose presence only the device knows) only if
  *                           hits[hit_index[b]] != 0 as well; until_first != 0: a block whose seen word is set is active
  *                           whatever else.  Clears the nhits hit words.
+ *   ctvae_adam_block_flags_local / _finish  the same flags in two launches, for data-parallel training, where the caller
+ *                           MAX-reduces `active` across ranks in between (a block steps on every rank iff it got a gradient
+ *                           on at least one).  _local: active[b] = present[b] (and the hit word, as above), whatever the seen
+ *                           word says; clears the nhits hit words.  _finish, on the reduced words in place: non-zero becomes
+ *                           1, and with until_first != 0 a block whose seen word is set becomes 1.  With nothing in between
+ *                           the two leave what ctvae_adam_block_flags leaves.
  *   ctvae_adam_mark_members the forward pass's side: hits[0] = 1 and hits[group[b]] = 1 for the B samples' groups (int32,
  *                           values outside [0, nhits) are ignored; B = 0: member 0 only). */
 #define CTVAE_ADAM_NO_CLIP 2
 int ctvae_adam_mark_members(int* hits, int nhits, const int* group, int B, void* stream);
 int ctvae_adam_block_flags(const int* present, const int* hit_index, int* hits, int nhits, const float* block_state, int* active,
                            int nb, int until_first, void* stream);
+int ctvae_adam_block_flags_local(const int* present, const int* hit_index, int* hits, int nhits, int* active, int nb, void* stream);
+int ctvae_adam_block_flags_finish(const float* block_state, int* active, int nb, int until_first, void* stream);
 int ctvae_adam_step_blocks(float* params, const float* grads, float* exp_avg, float* exp_avg_sq, float* state, long n,
                            float grad_scale, int algorithm, float clip_val, float* workspace, float* norm_out,
                            const int* block_lo, const int* block_hi, float* block_state, const int* active, int nb, void* stream);
