@@ -757,7 +757,10 @@ int ctvae_glinear_dgrad(const float* dy, int ldy, int nseg, int N, const float* 
   return launch_glinear_dgrad(a, dx, (hipStream_t)stream);
 }
 
-size_t ctvae_glinear_wgrad_ws_bytes(int G, int N, int K) { return glinear_wgrad_ws_floats(G, N, K, 1) * sizeof(float); }
+size_t ctvae_glinear_wgrad_ws_bytes(int G, int N, int K, int B, int grouped) {
+  if (G <= 0 || N <= 0 || K <= 0 || B <= 0) return 0;
+  return glinear_wgrad_ws_floats(G, N, K, glinear_wgrad_slices(B, G, grouped != 0)) * sizeof(float);
+}
 
 int ctvae_glinear_wgrad(const float* x, int ldx, int K, const float* dy, int ldy, int col0, int N, const int32_t* group, int G,
                         int B, float* dW, int ldo, float* dbias, int accumulate, float* ws, size_t ws_bytes, void* stream) {

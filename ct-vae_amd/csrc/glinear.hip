@@ -263,19 +263,24 @@ int launch_glinear_dgrad(const GLinArgs& a, float* dx, hipStream_t st) {
   return 0;
 }
 
+// slices of the batch: no group ids -> one group holds every sample and its 64x64 tiles are few (13-42): many slices fill
+// the chip; group ids -> a group holds B/G samples on average and there are G times the tiles: few slices (a slab is
+// written per (slice, group) whether or not the slice holds a sample of the group)
+int glinear_wgrad_slices(int B, int G, bool grouped) {
+  int S = grouped ? B / (4 * G) : B / 8;
+  S = S < 1 ? 1 : (S > 16 ? 16 : S);
+  while ((B + S - 1) / S > 64) ++S;      // a slice's list of samples has 64 entries
+  return S;
+}
+
 size_t glinear_wgrad_ws_floats(int G, int N, int K, int S) { return (size_t)S * G * N * ((size_t)K + 1); }
 
 int launch_glinear_wgrad(const float* x, int ldx, int K, const float* dy, int ldy, int col0, int N, const int* group, int G,
                          int B, float* dW, int ldo, float* dbias, int accumulate, float* ws, size_t ws_floats, hipStream_t st) {
-  if (!x || !dy || !dW || !ws || B <= 0 || K <= 0 || K % 4 || N <= 0 || N % 4 || G <= 0 || ldx % 4 || ldy % 4 || col0 % 4 ||
-      ldo < K || ldo % 4)
+  if (!x || !dy || !dW || !ws || B <= 0 || K <= 0 || K % 4 || N <= 0 || N % 4 || G <= 0 || ldx < K || ldx % 4 || col0 < 0 ||
+      col0 % 4 || ldy < col0 + N || ldy % 4 || ldo < K || ldo % 4)
     return kErrBadArg;
-  // slices of the batch: no group ids -> one group holds every sample and its 64x64 tiles are few (13-42): many slices fill
-  // the chip; group ids -> a group holds B/G samples on average and there are G times the tiles: few slices (a slab is
-  // written per (slice, group) whether or not the slice holds a sample of the group)
-  int S = group == nullptr ? B / 8 : B / (4 * G);
-  S = S < 1 ? 1 : (S > 16 ? 16 : S);
-  while ((B + S - 1) / S > 64) ++S;      // a slice's list of samples has 64 entries
+  const int S = glinear_wgrad_slices(B, G, group != nullptr);
   if (glinear_wgrad_ws_floats(G, N, K, S) > ws_floats) return kErrWorkspace;
   GLinWgArgs a{x, ldx, K, dy, ldy, col0, N, group, G, B, S, ws};
   {

@@ -24,6 +24,7 @@ struct GLinArgs {
 
 int launch_glinear_forward(const GLinArgs& a, hipStream_t st);
 int launch_glinear_dgrad(const GLinArgs& a, float* dx, hipStream_t st);
+int glinear_wgrad_slices(int B, int G, bool grouped);        // batch slices launch_glinear_wgrad uses
 size_t glinear_wgrad_ws_floats(int G, int N, int K, int S);
 int launch_glinear_wgrad(const float* x, int ldx, int K, const float* dy, int ldy, int col0, int N, const int* group, int G,
                          int B, float* dW, int ldo, float* dbias, int accumulate, float* ws, size_t ws_floats, hipStream_t st);

@@ -181,7 +181,7 @@ def load():
                        "ctvae_conv_bn_act_apply_is_separate": [_c.c_int] * 10 + [_c.c_size_t],
                        "ctvae_winograd_enable": [_c.c_int],
                        "ctvae_dip_state_floats": [_c.c_int, _c.c_int],
-                       "ctvae_glinear_wgrad_ws_bytes": [_c.c_int, _c.c_int, _c.c_int],
+                       "ctvae_glinear_wgrad_ws_bytes": [_c.c_int] * 5,
                        "ctvae_conv_wino_filter_floats": [_c.c_int] * 10 + [_c.c_size_t],
                        "ctvae_conv_input_transform_supported": [_c.c_int] * 10,
                        "ctvae_conv_wgrad_bn_apply_supported": [_c.c_int] * 10}.get(name, [])

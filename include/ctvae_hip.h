@@ -265,13 +265,15 @@ int ctvae_gat_layer_backward(const float* xl, const float* xr, int ld, const flo
  * wgrad (one segment, columns col0..col0+N-1 of dy): dW[(g*N + n)*ldo + k] (+)= sum_{b: group[b]==g} sum_m dy[b,m,col0+n] *
  * x[b,m,k] (ldo >= K: the destination may be a column block of a wider bank), dbias[g*N + n] (+)= column sums (may be NULL);
  * batch slices meet in a fixed-order slab
- * reduction inside ws (>= ctvae_glinear_wgrad_ws_bytes): deterministic, no atomics. */
+ * reduction inside ws: deterministic, no atomics.  ctvae_glinear_wgrad_ws_bytes(G, N, K, B, grouped) is the exact size the
+ * call needs for that batch (one slab [G][N][K+1] per batch slice; grouped = group != NULL); a smaller ws is refused with the
+ * workspace error and nothing is written. */
 int ctvae_glinear_forward(const float* x, int ldx, int K, int nseg, int N, const float* const* W, const int* ldw,
                           const int64_t* w_gstride, const float* const* bias, const int* b_gstride,
                           const int32_t* const* group, float* y, int ldy, int B, void* stream);
 int ctvae_glinear_dgrad(const float* dy, int ldy, int nseg, int N, const float* const* W, const int* ldw,
                         const int64_t* w_gstride, const int32_t* const* group, float* dx, int ldx, int K, int B, void* stream);
-size_t ctvae_glinear_wgrad_ws_bytes(int G, int N, int K);
+size_t ctvae_glinear_wgrad_ws_bytes(int G, int N, int K, int B, int grouped);
 int ctvae_glinear_wgrad(const float* x, int ldx, int K, const float* dy, int ldy, int col0, int N, const int32_t* group, int G,
                         int B, float* dW, int ldo, float* dbias, int accumulate, float* ws, size_t ws_bytes, void* stream);
 

@@ -1,0 +1,369 @@
+"""CPU: the float64 references of tests/ct_ops_checks.py pinned to the project's own torch paths in float64 (and to the golden
+fixtures where they hold the same quantity), the input conditions of every case of tests/test_ct_ops_gpu.py evaluated on the
+reference alone, and a sensitivity check: subtly wrong kernels, modelled by perturbing the reference, violate the very bounds
+the GPU test applies by a wide margin."""
+import numpy as np
+import pytest
+import torch
+import torch.nn.functional as F
+
+from ctvae_amd.models import causal
+from tests import ct_ops_checks as V
+from tests import helpers as H
+
+PIN = 1e-12
+
+
+def assert_pinned(got, want, what):
+    got, want = got.detach().double(), want.detach().double()
+    err = float((got - want).abs().max())
+    scale = max(float(want.abs().max()), 1e-300)
+    assert err <= PIN * scale, f"{what}: {err:.3e} against scale {scale:.3e}"
+
+
+class Replay:
+    """Noise source that hands out one prepared tensor per tag."""
+
+    def __init__(self, **draws):
+        self.draws = draws
+
+    def draw(self, tag, shape, p=0.0):
+        t = self.draws[tag]
+        assert tuple(t.shape) == tuple(shape), (tag, t.shape, shape)
+        return t
+
+
+@pytest.fixture
+def ct64():
+    prev = torch.get_default_dtype()
+    torch.set_default_dtype(torch.float64)
+    try:
+        torch.manual_seed(5)
+        yield lambda A: causal.CausalTransition(64, A, [16, 8]).double()
+    finally:
+        torch.set_default_dtype(prev)
+        causal.set_noise_source(None)
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# references against the project's torch paths
+# ---------------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("cid", ["K36-N12-s2", "K68-N96-s4", "G5-B10-S1"])
+def test_glinear_ref_is_per_group_linear(cid):
+    case = V.case_of(V.GL_CASES, cid)
+    inp = V.gl_inputs(case, "gauss")
+    ref = V.glinear_ref(case, inp)
+    x = V.d(inp["x"]).requires_grad_(True)
+    leaves, ys = [], []
+    for s, (W, b, grp) in zip(case.segs, inp["banks"]):
+        Wd = V.d(W).requires_grad_(True)
+        bd = V.d(b).requires_grad_(True) if b is not None else None
+        leaves.append((Wd, bd))
+        y = torch.zeros(case.B, 64, case.N, dtype=torch.float64)
+        ids = grp.long() if grp is not None else torch.zeros(case.B, dtype=torch.long)
+        for gi in set(ids.tolist()):                                  # one nn.Linear per group on the samples that chose it
+            sel = torch.where(ids == gi)[0]
+            y = y.index_put((sel,), F.linear(x[sel], Wd[gi, :, s.koff:s.koff + case.K], None if bd is None else bd[gi]))
+        ys.append(y)
+    y = torch.cat(ys, -1)
+    y.backward(V.d(inp["dy"]))
+    assert_pinned(ref["y"], y, "y")
+    assert_pinned(ref["dx"], x.grad, "dx")
+    for si, (s, (Wd, bd)) in enumerate(zip(case.segs, leaves)):
+        assert_pinned(ref["dW"][si], Wd.grad[:, :, s.koff:s.koff + case.K], f"dW[{si}]")
+        assert float(Wd.grad[:, :, :s.koff].abs().sum()) == 0.0 and float(Wd.grad[:, :, s.koff + case.K:].abs().sum()) == 0.0
+        if bd is not None:
+            assert_pinned(ref["db"][si], bd.grad, f"db[{si}]")
+        if s.spare:
+            assert float(ref["dW"][si][-1].abs().sum()) == 0.0 and float(ref["rows"][si][-1]) == 0.0
+
+
+@pytest.mark.parametrize("graphs", [("rand", "diag", "isolated"), ("dense", "empty", "neg")])
+def test_gat_layer_ref_is_dense_gatv2_forward(graphs):
+    prev = torch.get_default_dtype()
+    torch.set_default_dtype(torch.float64)
+    try:
+        torch.manual_seed(3)
+        Hh, C, Cin, B = 3, 20, 12, 3
+        gat = causal.DenseGATv2(Cin, C, Hh).double()
+        gat.bias.data.normal_()
+        g = V.gen_of("gat-pin" + graphs[0])
+        adj = torch.stack([V.gat_graph(k, g) for k in graphs]).double().requires_grad_(True)
+        x = torch.randn(B, 64, Cin, generator=g, dtype=torch.float64).requires_grad_(True)
+        g_out = torch.randn(B, 64, Hh, C, generator=g, dtype=torch.float64)
+        out = gat(x, adj)
+        out.backward(g_out.reshape(B, 64, Hh * C))
+        xl, xr = gat.lin_l(x).view(B, 64, Hh, C).detach(), gat.lin_r(x).view(B, 64, Hh, C).detach()
+        ref = V.gat_layer_ref(xl, xr, adj.detach(), gat.lin_edge.weight.view(Hh, C), gat.att[0], gat.bias.view(Hh, C), None,
+                              gat.negative_slope, 0, g_out)
+        assert_pinned(ref["out"].reshape(B, 64, Hh * C), out, "out")
+        assert_pinned(ref["d_adj"], adj.grad, "d_adj")
+        assert_pinned(ref["d_bias"].sum(0), gat.bias.grad.view(Hh, C), "d_bias")
+        assert_pinned(ref["d_att"].sum(0), gat.att.grad[0], "d_att")
+        assert_pinned(ref["d_we"].sum(0), gat.lin_edge.weight.grad.view(Hh, C), "d_we")
+        # d_xl + d_xr reach x through the two Linear layers
+        gx = ref["d_xl"].reshape(B, 64, -1) @ gat.lin_l.weight + ref["d_xr"].reshape(B, 64, -1) @ gat.lin_r.weight
+        assert_pinned(gx, x.grad, "d_x")
+        # head slots: a map that repeats a head equals the plain layer on the repeated parameters
+        hm = torch.tensor([[2, 2], [0, 1], [1, 2]], dtype=torch.int32)
+        par = [t.detach() for t in (gat.lin_edge.weight.view(Hh, C), gat.att[0], gat.bias.view(Hh, C))]
+        got = V.gat_layer_ref(xl[:, :, :2], xr[:, :, :2], adj.detach(), *par, hm, 0.2, 1, g_out[:, :, :2])
+        for b in range(B):
+            sel = [t[hm[b].long()] for t in par]
+            one = V.gat_layer_ref(xl[b:b + 1, :, :2], xr[b:b + 1, :, :2], adj.detach()[b:b + 1], *sel, None, 0.2, 1, g_out[b:b + 1, :, :2])
+            for k in ("out", "alpha", "d_xl", "d_adj", "d_bias", "d_att", "d_we"):
+                assert_pinned(got[k][b:b + 1], one[k], k)
+    finally:
+        torch.set_default_dtype(prev)
+
+
+def test_gat_ref_graph_properties():
+    for case in V.GAT_CASES:
+        inp = V.gat_inputs(case)
+        ref = V.gat_layer_ref(inp["xl"], inp["xr"], inp["adj"], inp["we"], inp["att"], inp["bias"], inp["head_map"], V.SLOPE_GAT, case.act,
+                              inp["g_out"])
+        assert float((ref["alpha"].sum(2) - 1).abs().max()) < 1e-12
+        assert float(ref["alpha"][~ref["keep"][:, None].expand_as(ref["alpha"])].abs().sum()) == 0.0
+        idx = torch.arange(64)
+        assert float(ref["d_adj"][:, idx, idx].abs().max()) == 0.0, "the diagonal of adj never reaches the result"
+        for b, kind in enumerate(case.graphs):
+            if kind == "empty":
+                assert torch.equal(ref["alpha"][b], torch.eye(64, dtype=torch.float64).expand(case.Hs, 64, 64))
+            if kind == "diag":                                         # zeroing the diagonal changes nothing
+                a2 = inp["adj"].clone()
+                a2[b, idx, idx] = 0.0
+                assert float(inp["adj"][b, idx, idx].abs().min()) > 0.0
+                ref2 = V.gat_layer_ref(inp["xl"], inp["xr"], a2, inp["we"], inp["att"], inp["bias"], inp["head_map"], V.SLOPE_GAT, case.act)
+                assert torch.equal(ref2["out"], ref["out"])
+        if case.head_map is not None:
+            used = {h for row in case.head_map for h in row}
+            assert len(used) < case.H and any(len(set(row)) < len(row) for row in case.head_map), "needs an unused and a repeated head"
+    assert {c.C for c in V.GAT_CASES} >= {16, 20, 64, 68, 128} and {c.Hs for c in V.GAT_CASES} == {1, 2, 3}
+
+
+def test_reg_ref_is_the_three_torch_losses(ct64, golden):
+    ct = ct64(4)
+    for case in V.REG_CASES:
+        inp = V.reg_inputs(case)
+        adj = V.d(inp["adj"]).requires_grad_(True)
+        graph = V.d(inp["graph"]).requires_grad_(True)
+        causal.set_noise_source(Replay(kl_target=V.d(inp["uni"])))
+        B = case.B
+        kl, gs, pt = ct.adjacency_KL_loss(adj), ct.graph_size_loss(graph), ct.positive_trial_loss(adj)
+        ckl, cgs, cpt = case.coef
+        (case.g_loss * B * (ckl * kl + cgs * gs + cpt * pt)).backward()
+        ref = V.reg_ref(inp["adj"], inp["graph"], inp["uni"], ckl, cgs, cpt, case.g_loss)
+        assert_pinned(ref["part4"][:, 0].mean(), kl, "KL")
+        assert_pinned(ref["part4"][:, 1].mean(), gs, "graph size")
+        assert_pinned(ref["part4"][:, 2].mean(), pt, "positive trial")
+        assert_pinned(ref["part4"][:, 3].sum(), B * (ckl * kl + cgs * gs + cpt * pt), "total")
+        assert_pinned(ref["d_adj"], adj.grad, "d_adj")
+        assert torch.isfinite(graph.grad).all() or "zerograph" in case.special      # torch's own norm backward at 0 is not relied on
+        ok = torch.tensor([sp != "zerograph" for sp in case.special])
+        assert_pinned(ref["d_graph"][ok], graph.grad[ok], "d_graph")
+        assert float(ref["d_graph"][~ok].abs().sum()) == 0.0 and torch.isfinite(ref["d_adj"]).all()
+        for b, sp in enumerate(case.special):
+            if sp == "ones":
+                o = ref["others"][b]
+                assert float(ref["P"][b, 3]) == 0.0 and float(o[3, 17]) > 0.0 and float(o[3].abs().sum() - o[3, 17]) == 0.0
+                want = float((1 - V.d(inp["adj"])[b, 3, torch.arange(64) != 17]).prod())
+                assert abs(float(o[3, 17]) - want) <= 1e-12 * want                   # the product of the others
+                assert float(o[11].abs().sum()) == 0.0                               # two exact ones: the whole row
+            if sp == "allrows":
+                assert float(ref["part4"][b, 2]) == 0.0
+                kl_only = V.reg_ref(inp["adj"], inp["graph"], inp["uni"], ckl, cgs, 0.0, case.g_loss)
+                assert torch.equal(ref["d_adj"][b], kl_only["d_adj"][b])              # pt = 0: its term is 0
+    # golden: positive_trial with exact zero factors, graph size, positive trial and the cross-entropy of the reference itself
+    for A in (12, 20):
+        g = golden(f"ct_parts_a{A}")
+        seed, B = int(g["seed"]), int(g["B"])
+        adj_z = torch.rand(B, 64, 64, generator=torch.Generator().manual_seed(seed + 9), dtype=torch.float32) * 0.08
+        adj_z[:, ::7, 3] = 1.0
+        zeros = torch.zeros(B, 64, 64)
+        ref = V.reg_ref(adj_z, zeros, torch.zeros(B, 4096), 0.0, 0.0, 1.0 / B)
+        assert abs(float(ref["part4"][:, 2].mean()) - float(g["ptrial_z"])) <= 1e-4 * float(g["ptrial_z"])
+        assert float((ref["d_adj"] - torch.from_numpy(g["ptrial_z.g_adj"])).abs().max()) <= 2e-3 * float(np.abs(g["ptrial_z.g_adj"]).max())
+        ref = V.reg_ref(torch.from_numpy(g["adj"]), torch.from_numpy(g["graph"]).float(), torch.zeros(B, 4096), 0.0, 1.0 / B, 1.0 / B)
+        assert abs(float(ref["part4"][:, 1].mean()) - float(g["gsize"])) <= 1e-4 * float(g["gsize"])
+        assert abs(float(ref["part4"][:, 2].mean()) - float(g["ptrial"])) <= 1e-3 * float(g["ptrial"])
+        assert float((ref["d_graph"] - torch.from_numpy(g["gsize.g_graph"])).abs().max()) <= 1e-3 * float(np.abs(g["gsize.g_graph"]).max())
+        probs = torch.from_numpy(g["y"]).reshape(B * 64, 64)
+        _, tgt_oh = H.ct_codes(seed + 1, B, 64, 64)
+        ce = V.latent_ce_ref(probs, tgt_oh.reshape(B * 64, 64).argmax(-1))
+        assert abs(float(ce["row_loss"].mean()) - float(g["latent_loss"])) <= 1e-4
+        want = torch.from_numpy(g["latent_loss.g"]).permute(0, 2, 3, 1).reshape(B * 64, 64)
+        assert float((ce["d_probs"] - want).abs().max()) <= 1e-4 * max(1.0, float(want.abs().max())) + 1e-3 * float(want.abs().max())
+
+
+def test_blend_softmax_and_ce_refs_are_the_torch_expressions():
+    for case in V.BS_CASES:
+        inp = V.bs_inputs(case)
+        ref = V.blend_softmax_ref(inp["y"], inp["mask"], inp["g"])
+        y = V.d(inp["y"]).view(1, case.R, case.Hs, case.D)
+        m = V.d(inp["mask"]).view(1, case.R, 1) if case.Hs == 2 else None
+        want = (y[:, :, 0] if m is None else y[:, :, 0] * (1 - m) + y[:, :, 1] * m).softmax(dim=-1)        # _compute_y's last line
+        assert_pinned(ref["probs"], want[0], case.id)
+        assert torch.isfinite(ref["probs"]).all() and torch.isfinite(ref["dy"]).all()
+        if case.Hs == 2:
+            assert {0.0, 1.0} <= set(inp["mask"].tolist()) or case.R < 2
+    for case in V.CE_CASES:
+        inp = V.ce_inputs(case)
+        p = V.d(inp["probs"]).requires_grad_(True)
+        strict = p.detach() != V.BOUND               # torch's clamp passes the gradient AT the bound; the header's convention does not
+        loss = F.cross_entropy(p.clamp(min=V.BOUND).log(), inp["target"])
+        (case.g_loss * loss).backward()
+        ref = V.latent_ce_ref(inp["probs"], inp["target"], case.g_loss)
+        assert_pinned(ref["row_loss"].mean(), loss, case.id)
+        assert_pinned(ref["d_probs"][strict], p.grad[strict], case.id + " gradient")
+        assert float(ref["d_probs"][~strict].abs().sum()) == 0.0
+        if case.D >= 10 and case.R >= 3:
+            pt = inp["probs"].gather(1, inp["target"].view(-1, 1)).squeeze(1)
+            assert bool((pt == 0).any()) and bool(((pt > 0) & (pt < V.BOUND)).any())
+            assert bool((inp["probs"] == 0).any()) and float(ref["d_probs"][inp["probs"] <= V.BOUND].abs().sum()) == 0.0
+        assert int(inp["target"][-1]) == case.D - 1 and (case.R == 1 or int(inp["target"][0]) == 0)
+
+
+def test_mask_and_sample_refs_are_the_torch_branch(ct64):
+    for case in V.MASK_CASES:
+        ct = ct64(case.A)
+        ct.train(case.keep)
+        inp = V.mask_inputs(case)
+        with torch.no_grad():
+            ct.mask[0].weight.copy_(V.d(inp["W"]))
+            ct.mask[0].bias.copy_(V.d(inp["bias"]))
+        ct.pos_encoding.p = 1.0 - 1.0 / inp["scale"] if case.keep else ct.pos_encoding.p
+        assert torch.equal(V._f32(lambda: causal.PositionalEncoding(64).pe[:64, 0])(), inp["pe"])      # the float32 table the product holds
+        ct.pos_encoding.pe[:64, 0] = V.d(inp["pe"])
+        src = Replay(mask_dropout=V.d(inp["keep"])) if case.keep else Replay()
+        causal.set_noise_source(src)
+        x, act = V.d(inp["x"]), V.d(inp["action"])
+        pos = ct.pos_encoding(torch.zeros_like(x), "mask_dropout")                  # the torch branch of _compute_mask, line by line
+        inter = ct.mask(torch.cat([act.unsqueeze(1).expand(case.B, 64, case.A), pos], dim=-1))
+        p = (x * inter).sum(dim=-1)
+        ref = V.mask_ref(**{k: inp[k] for k in ("x", "action", "pe", "keep", "scale", "W", "bias", "expo", "g")})
+        assert_pinned(ref["inter"], inter, "inter")
+        assert_pinned(ref["p"], p, "p")
+        # the sampler: F.gumbel_softmax's expression with the Gumbel noise given
+        pr = ref["p"].clone().requires_grad_(True)
+        logits = torch.stack([1 - pr, pr], -1).clamp(min=V.BOUND).log()
+        ysoft = ((logits - V.d(inp["expo"]).log()) / 1.0).softmax(-1)
+        hard = F.one_hot(ysoft.argmax(-1), 2).double()
+        st = (hard - ysoft.detach() + ysoft)[..., 1]
+        (st * V.d(inp["g"])).sum().backward()
+        assert_pinned(ref["soft"], ysoft[..., 1], "soft")
+        assert torch.equal(ref["sample"], hard[..., 1])
+        # dWp / dbp against autograd through the module
+        Wl, bl = V.d(inp["W"]).requires_grad_(True), V.d(inp["bias"]).requires_grad_(True)
+        keep = V.d(inp["keep"]) * inp["scale"] if case.keep else 1.0
+        inn = torch.cat([act.unsqueeze(1).expand(case.B, 64, case.A), V.d(inp["pe"]).expand(case.B, 64, 64) * keep], -1)
+        p2 = (x * torch.sigmoid(F.linear(inn, Wl, bl))).sum(-1)
+        p2.backward(pr.grad)
+        assert_pinned(ref["dWp"].sum(0).t(), Wl.grad, "dW")
+        assert_pinned(ref["dbp"].sum(0), bl.grad, "dbias")
+    for n in V.SAMPLE_N:
+        inp = V.sample_inputs(n)
+        p = V.d(inp["p"]).requires_grad_(True)
+        logits = torch.stack([1 - p, p], -1).clamp(min=V.BOUND).log()
+        ysoft = (logits - V.d(inp["expo"]).log()).softmax(-1)
+        hard = F.one_hot(ysoft.argmax(-1), 2).double()
+        sample = (hard - ysoft.detach() + ysoft)[..., 1]
+        strict = (p.detach() != V.BOUND) & ((1 - p.detach()) != V.BOUND)
+        ((sample * V.d(inp["g_s"])).sum() + (p * sample * V.d(inp["g_w"])).sum()).backward()
+        ref = V.sample_ref(inp["p"], inp["expo"], inp["g_s"], inp["g_w"])
+        assert_pinned(ref["soft"], ysoft[..., 1], "soft")
+        assert torch.equal(ref["sample"], hard[..., 1])
+        assert_pinned(ref["g_p"][strict], p.grad[strict], "g_p")
+        if n >= 6:
+            assert {0.0, 1.0} <= set(inp["p"].tolist()) and bool(((inp["p"] > 0) & (inp["p"] < V.BOUND)).any()) \
+                and bool(((inp["p"] < 1) & (inp["p"] > 1 - V.BOUND)).any())
+
+
+def test_pair_mlp_ref_is_pair_coeffs(ct64):
+    ct = ct64(4)
+    for case in V.PAIR_CASES:
+        inp = V.pair_inputs(case)
+        ref = V.pair_mlp_ref(inp["u"], inp["v"], inp["w2"], inp["b2"], inp["row_of"], V.SLOPE_PAIR, inp["g"])
+        rows = inp["row_of"].long() if inp["row_of"] is not None else torch.zeros(case.B, dtype=torch.long)
+        u, v = V.d(inp["u"]), V.d(inp["v"])
+        for b in range(case.B):                                                   # _pair_coeffs' torch branch per sample
+            h = F.leaky_relu(u[b:b + 1].unsqueeze(2) + v[b:b + 1].unsqueeze(1))
+            want = torch.sigmoid(F.linear(h, V.d(inp["w2"])[rows[b]].view(1, -1), V.d(inp["b2"])[rows[b]].view(1))).squeeze(-1)
+            assert_pinned(ref["out"][b:b + 1], want, case.id)
+        assert float(ref["t"].abs().min()) > 0.0, "a float32 add has the sign of the exact sum: only an exact 0 could differ"
+        if case.row_of is not None:
+            assert len(set(case.row_of)) < len(case.row_of) and len(set(case.row_of)) < case.G
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# input conditions of the GPU cases
+# ---------------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("case", V.GL_CASES, ids=lambda c: c.id)
+def test_glinear_integer_cases_are_exact_in_float32(case):
+    inp = V.gl_inputs(case, "int")
+    ref = V.glinear_ref(case, inp)
+    worst = max(float(ref["y_abs"].max()), float(ref["dx_abs"].max()), max(float(a.max()) for a in ref["dW_abs"]),
+                max(float(a.max()) for a in ref["db_abs"]))
+    assert worst + 1 < 2 ** 24, "every partial sum (in any order) must be an exactly representable integer"
+    for t in (ref["y"], ref["dx"], *ref["dW"]):
+        assert torch.equal(t, t.round()) and torch.equal(t.float().double(), t)
+    for si, s in enumerate(case.segs):
+        S = V.gl_slices(case.B, s.G if s.grouped else 1, s.grouped)
+        assert -(-case.B // S) <= 64
+        if len(case.segs) == 1 and case.id in V.GL_EXPECT_S:
+            assert S == V.GL_EXPECT_S[case.id]
+
+
+def test_glinear_cases_cover_the_issue():
+    assert {c.K for c in V.GL_CASES} >= {4, 36, 64, 68, 100} and {c.N for c in V.GL_CASES} >= {4, 12, 64, 96, 132}
+    assert {c.nseg for c in V.GL_CASES} == {1, 2, 3, 4}
+    segs = [s for c in V.GL_CASES for s in c.segs]
+    assert any(s.koff for s in segs) and any(s.tail for s in segs) and any(not s.bias for s in segs) and any(s.spare for s in segs)
+    assert any(c.xpad for c in V.GL_CASES) and any(c.ypad for c in V.GL_CASES)
+    assert sorted(set(V.GL_EXPECT_S.values())) == [1, 2, 16]
+    assert V.gl_slices(65, 20, True) == 2 and 65 // (4 * 20) == 0            # the > 64 samples per slice branch, at its smallest
+
+
+def test_decision_margins_stay_within_the_cap():
+    for case in V.GAT_CASES:
+        inp = V.gat_inputs(case)
+        ref = V.gat_layer_ref(inp["xl"], inp["xr"], inp["adj"], inp["we"], inp["att"], inp["bias"], inp["head_map"], V.SLOPE_GAT, case.act)
+        inside, total = V.gat_margin_count(case, inp, ref)
+        print(f"gat {case.id}: {inside} of {total} leaky-ReLU arguments inside the float32 margin")
+        assert inside == 0, f"{case.id}: pick another salt ({inside} arguments could take either slope)"
+    for case in V.MASK_CASES:
+        inp = V.mask_inputs(case)
+        ref = V.mask_ref(**{k: inp[k] for k in ("x", "action", "pe", "keep", "scale", "W", "bias", "expo")})
+        _, _, d_a = V.mask_error_bounds(case, inp, ref)
+        share = float(((ref["a1"] - ref["a0"]).abs() <= d_a).double().mean())
+        print(f"mask {case.id}: {share:.4%} of the samples inside the margin")
+        assert share <= V.EXCLUDE_CAP
+    for n in V.SAMPLE_N:
+        inp = V.sample_inputs(n)
+        ref = V.sample_ref(inp["p"], inp["expo"])
+        inside = int(((ref["a1"] - ref["a0"]).abs() <= V.sample_margin(inp["p"], inp["expo"])).sum())
+        assert inside <= V.EXCLUDE_CAP * n, (n, inside)
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# the bounds of the GPU test notice subtly wrong kernels
+# ---------------------------------------------------------------------------------------------------------------------
+def test_bounds_catch_a_dropped_k_tail_a_skipped_slab_and_a_shifted_exclusive_product():
+    case = V.case_of(V.GL_CASES, "K68-N96-s4")                       # K = 68: the last 32-chunk holds 4 columns
+    inp = V.gl_inputs(case, "gauss")
+    ref, bad = V.glinear_ref(case, inp), V.glinear_ref(case, inp, drop_k_tail=True)
+    ratio = ((bad["y"] - ref["y"]).abs() / V.dot_bound(case.K, ref["y_abs"])).max()
+    assert float(ratio) > 1e2, float(ratio)
+    inti = V.gl_inputs(case, "int")
+    assert not torch.equal(V.glinear_ref(case, inti)["y"], V.glinear_ref(case, inti, drop_k_tail=True)["y"])
+    case = V.case_of(V.GL_CASES, "B19-S2")
+    inp = V.gl_inputs(case, "gauss")
+    ref, bad = V.glinear_ref(case, inp), V.glinear_ref(case, inp, skip_slab=1)
+    L = ref["rows"][0][:, None, None] + 2
+    ratio = ((bad["dW"][0] - ref["dW"][0]).abs() / V.dot_bound(L, ref["dW_abs"][0])).max()
+    assert float(ratio) > 1e2, float(ratio)
+    rc = V.case_of(V.REG_CASES, "B3-ones-allrows-zerograph")
+    inp = V.reg_inputs(rc)
+    ref, bad = V.reg_ref(**inp, ckl=rc.coef[0], cgs=rc.coef[1], cpt=rc.coef[2], g_loss=rc.g_loss), \
+        V.reg_ref(**inp, ckl=rc.coef[0], cgs=rc.coef[1], cpt=rc.coef[2], g_loss=rc.g_loss, shift=1)
+    err = float((bad["d_adj"] - ref["d_adj"]).abs().max())
+    assert err > 1e2 * 2e-3 * float(ref["d_adj"].abs().max()), err              # the GPU test allows 2e-3 of the largest magnitude
