@@ -312,7 +312,8 @@ class ActLink:
 # out (final_layer's Tanh output r), and the one consumer that knows how to fold act'(r) into its own backward pass -- the
 # reconstruction loss, which reads r anyway -- claims the link in its forward.  If nobody claims it, or the loss is not
 # asked for that gradient, the producer runs its activation backward as usual; if the loss folded it but a different
-# gradient tensor arrives (r had a second consumer), ActLink.take raises.
+# gradient tensor arrives (r had a second consumer), ActLink.take raises.  Keyed by address, not hung on the tensor as a tag: r
+# crosses the public NCHW boundary as a permuted view between final_layer and the loss -- another tensor object, the same memory.
 _out_act_links = {}
 
 
@@ -338,52 +339,83 @@ def claim_out_act_link(t):
 
 
 # Gradients handed on as raw split-K slices (pixel-major) to an element-wise consumer that sums them while it reads: the producer
-# (conv_backward_raw, asked by a layer whose input tensor carries ``_ctvae_grad_slices_ok``) registers the placeholder it returns,
-# the consumer's backward (GaussianLatent, _ToNHWC) claims it.  The tag is a promise of model code that the tensor's gradient goes
-# to that consumer and nowhere else: the placeholder is never written.
+# (conv_backward_raw, asked by a layer whose input tensor is tagged grad_slices_ok) offers the placeholder it returns, the consumer's
+# backward (GaussianLatent, _ToNHWC, LinearToNHWC) claims it.  The tag is a promise of model code that the tensor's gradient goes to
+# that consumer and nowhere else: the placeholder is never written.  A broken promise raises -- a tensor at an offered address that
+# is not the untouched placeholder (claim_lazy_grad), more offers than a pass can have open (offer_lazy_grad), an offer nobody
+# claimed because autograd summed the placeholder into another tensor for a second consumer (kernels.backward, after the pass).
 _lazy_grads = {}
 
 
 def offer_lazy_grad(g, slices, n):
-    if len(_lazy_grads) > 16:
-        _lazy_grads.clear()
-    # the entry keeps the placeholder alive: its address cannot be handed to another tensor while the entry exists, so a match
-    # on (address, version, size) below IS the placeholder (or a view of it), never a newcomer at a recycled address.  Size, not
-    # shape as in _stamp: the placeholder reaches its consumer through a reshape's backward, i.e. as a view of another shape
+    if len(_lazy_grads) >= 16:
+        raise RuntimeError("offer_lazy_grad: 16 gradient placeholders are on offer unclaimed (backward passes outside kernels.backward?)")
+    # the entry keeps the placeholder alive: its address is not recycled.  Size, not shape as in _stamp: it arrives as a reshape's view
     _lazy_grads[g.data_ptr()] = (slices, n, g._version, g.numel(), g)
 
 
 def claim_lazy_grad(g):
-    """(slices, n) if ``g`` is a registered, untouched placeholder, else None."""
+    """(slices, n) if ``g`` is a placeholder on offer; None if nothing is on offer at its address (an ordinary gradient).  A tensor
+    at an offered address that is not the untouched placeholder (written since, another size, not contiguous) is misuse: raises."""
     e = _lazy_grads.pop(g.data_ptr(), None)
-    if e is None or e[2] != g._version or e[3] != g.numel():
-        return None
-    return e[0], e[1]
+    if e is not None and (e[2] != g._version or e[3] != g.numel() or not g.is_contiguous()):
+        raise RuntimeError("claim_lazy_grad: a gradient left as split-K slices arrived as something else than its untouched placeholder")
+    return e and (e[0], e[1])
+
+
+class _Tag:
+    """What a tensor's producer or model code hands to the ONE layer that consumes it.  Hangs on the tensor object (tag / tag_of);
+    a view is another object and carries nothing unless model code says so (carry_tag)."""
+    __slots__ = ("bn_link", "lazy_bn", "fwd_slices", "grad_slices_ok")
+
+    def __init__(self):
+        self.bn_link = None            # BNLink: the tensor is the output of a train-mode ConvBNAct
+        self.lazy_bn = None            # (coef [2][C], act): the tensor holds the raw conv output, its consumer applies BatchNorm + act on load
+        self.fwd_slices = None         # (slices, n, bias, _stamp): the tensor is an unwritten placeholder for bias + the sum of the slices
+        self.grad_slices_ok = False    # model code: the tensor's gradient goes to ONE backward that can sum split-K slices (_lazy_grads)
+
+
+_NO_TAG = _Tag()
+
+
+def tag(t):
+    """The tag of ``t``, created if absent: for writing."""
+    if not hasattr(t, "_ctvae_tag"):
+        t._ctvae_tag = _Tag()
+    return t._ctvae_tag
+
+
+def tag_of(t):
+    """The tag of ``t`` for reading (a shared empty one if it has none)."""
+    return getattr(t, "_ctvae_tag", _NO_TAG)
+
+
+def carry_tag(src, view):
+    """Model code hands ``view`` (a reshape of src) on in src's place, so src's one consumer is the view's.  Slices are stamped anew."""
+    tg = tag_of(src)
+    if view is not src and (tg.fwd_slices is not None or tg.grad_slices_ok):
+        tag(view).grad_slices_ok = tg.grad_slices_ok
+        tag(view).fwd_slices = tg.fwd_slices and tg.fwd_slices[:3] + (_stamp(view),)
+    return view
+
+
+def _handovers_in(x):
+    """(bn_link, lazy_bn, grad_slices_ok) of a layer's input: the first two describe memory, so only a contiguous x (_c keeps it) has them."""
+    tg, c = tag_of(x), x.is_contiguous()
+    return tg.bn_link if c else None, tg.lazy_bn if c else None, tg.grad_slices_ok
+
+
+def check_fwd_slices(t, fs):
+    """fs = (slices, n, bias, stamp) handed over next to the placeholder t, or None.  Slices made for another tensor raise."""
+    if fs is not None and not (t.is_contiguous() and _same(t, fs[3])):
+        raise RuntimeError("forward split-K slices came with a tensor that is not the untouched placeholder they were made for")
+    return fs
 
 
 def grad_slices_ok(t):
     """Model code: the gradient w.r.t. ``t`` is consumed by ONE backward that can sum split-K slices (see _lazy_grads)."""
-    t._ctvae_grad_slices_ok = True
+    tag(t).grad_slices_ok = True
     return t
-
-
-_last_link = None     # set by ConvBNAct.forward, picked up by the caller of .apply (models/blocks.py) right after
-_last_fwd_slices = None   # set by ConvAct.forward(lazy_slices=True): (slices, n, bias) of the placeholder it returned
-
-
-def pop_fwd_slices():
-    global _last_fwd_slices
-    fs, _last_fwd_slices = _last_fwd_slices, None
-    return fs
-
-
-_last_lazy = None     # set by ConvBNAct.forward(lazy_out=True): (scale | shift [2][C], activation) of the tensor it returned
-
-
-def pop_lazy_bn():
-    global _last_lazy
-    lz, _last_lazy = _last_lazy, None
-    return lz
 
 
 def bn_apply_is_separate(spec, B, H, W) -> bool:
@@ -400,27 +432,15 @@ def lazy_bn_input_supported(spec, B, H, W) -> bool:
     return input_transform_supported(spec, B, H, W)      # (the tile kernels form max(t, slope*t): LeakyReLU / ReLU / none)
 
 
-def pop_bn_link():
-    global _last_link
-    link, _last_link = _last_link, None
-    return link
-
-
 def mark_sole_consumer(x):
     """Model code promises that x -- the output of a train-mode ConvBNAct block -- is read by exactly ONE consumer (the next
     block of a chain: blocks.Chain, or the one layer the model hands it to).  That consumer may then leave its data gradient as
     split-K slices for the BatchNorm's backward launch to sum (BNLink.publish_lazy): the gradient tensor in between is never
     written, so a second consumer would add garbage -- BNLink.take_lazy raises if anything but the placeholder arrives."""
-    link = getattr(x, "_ctvae_bn_link", None)
+    link = tag_of(x).bn_link
     if link is not None:
         link.sole = True
     return x
-
-
-def link_of(x):
-    """BNLink of a tensor that is the untouched, contiguous output of a train-mode ConvBNAct (else None)."""
-    link = getattr(x, "_ctvae_bn_link", None)
-    return link if (link is not None and x.is_contiguous()) else None
 
 
 def _dy_bn_args(dy_bn):
@@ -557,7 +577,7 @@ class _ToNHWC(Function):
     @staticmethod
     def backward(ctx, g):
         B, C, H, W = ctx.dims
-        lazy = claim_lazy_grad(g) if g.is_contiguous() else None
+        lazy = claim_lazy_grad(g)
         if lazy is not None:
             # the gradient arrives as split-K slices of the consumer's data gradient: summed while the layout changes
             out = torch.empty((B, C, H, W), dtype=torch.float32, device=g.device)
@@ -581,8 +601,7 @@ class LinearToNHWC(Function):
         _req_cuda(x, w)
         x = _c(x)
         B = x.shape[0]
-        ctx.link_in = link_of(x)
-        ctx.x_slices_ok = bool(getattr(x, "_ctvae_grad_slices_ok", False))
+        ctx.link_in, _, ctx.x_slices_ok = _handovers_in(x)
         ctx.spec, ctx.w, ctx.b, ctx.dims = spec, w, b, (B, C, h, wd)
         ws = native.workspace(x.device)
         y = torch.empty((B, h, wd, C), dtype=torch.float32, device=x.device)
@@ -600,7 +619,7 @@ class LinearToNHWC(Function):
         spec = ctx.spec
         if spec.act != ACT_NONE:
             raise RuntimeError("LinearToNHWC: a fused activation is not differentiated here (decoder_input has none)")
-        lazy = claim_lazy_grad(g) if g.is_contiguous() else None
+        lazy = claim_lazy_grad(g)
         if lazy is not None:       # split-K slices of the consumer's data gradient: summed while the layout changes
             g_flat = torch.empty((B, 1, 1, C * h * wd), dtype=torch.float32, device=g.device)
             native.call("ctvae_splitk_permute", lazy[0].data_ptr(), lazy[1], g_flat.data_ptr(), B, C, h * wd)
@@ -719,7 +738,7 @@ def flatten_linear(h, w, b, out_features, lazy_slices=False):
     (vanilla_vae.py:87-91 and every model built on that encoder).  k = 2 with 32-aligned widths: a 2x2 stride-2 convolution
     straight on the NHWC tensor over the Linear layer's own [in][out] block (CONV_FLAT) -- no layout copies, and the data
     gradient comes back NHWC with the BatchNorm-backward sums of the layer below in its epilogue.  Anything else: the NCHW copy
-    and a 1x1 GEMM."""
+    and a 1x1 GEMM.  lazy_slices: returns (out, fwd_slices) for GaussianLatent only, which sums the GEMM's split-K slices itself."""
     B, k, k2, C = h.shape
     key = (k, k2, C, out_features)
     spec = _flat_specs.get(key)
@@ -730,17 +749,11 @@ def flatten_linear(h, w, b, out_features, lazy_slices=False):
             spec = ConvSpec(CONV, C * k * k2, out_features, 1)
         _flat_specs[key] = spec
     if spec.kind == CONV_FLAT:
-        if lazy_slices:
-            # the caller hands the result to GaussianLatent only, which sums the GEMM's split-K slices itself
-            y = ConvAct.apply(h, w, b, None, spec, None, True)
-            fs = pop_fwd_slices()
-            out = y.view(B, -1)
-            if fs is not None:
-                out._ctvae_fwd_slices = fs
-            return out
-        return ConvAct.apply(h, w, b, None, spec).view(B, -1)
-    flat = _ToNCHW.apply(h).view(B, 1, 1, -1)
-    return ConvAct.apply(flat, w, b, None, spec).view(B, -1)
+        y = ConvAct.apply(h, w, b, None, spec, None, lazy_slices)
+        out = carry_tag(y, y.view(B, -1))
+    else:
+        out = ConvAct.apply(_ToNCHW.apply(h).view(B, 1, 1, -1), w, b, None, spec).view(B, -1)
+    return (out, tag_of(out).fwd_slices) if lazy_slices else out
 
 
 class ConvAct(Function):
@@ -750,11 +763,9 @@ class ConvAct(Function):
     def forward(ctx, x, w, b, add, spec, aux=None, lazy_slices=False):
         """aux: companion rows (see above); returns (y, y_aux) then.  lazy_slices (model code: the ONE consumer of y sums split-K
         slices itself, e.g. GaussianLatent): where the launch splits K, y is an unwritten placeholder and the raw slices (no bias)
-        wait in kernels.pop_fwd_slices() for the caller to hang on it."""
-        global _last_fwd_slices
+        hang on its tag (fwd_slices) for the caller of .apply to pass on."""
         _req_cuda(x, w)
-        ctx.link_in = link_of(x)
-        ctx.x_slices_ok = bool(getattr(x, "_ctvae_grad_slices_ok", False))
+        ctx.link_in, _, ctx.x_slices_ok = _handovers_in(x)
         ctx.wino_u = None
         ctx.spec, ctx.w, ctx.b, ctx.has_add = spec, w, b, add is not None
         if lazy_slices and aux is None and add is None and spec.act == ACT_NONE and x.is_contiguous():
@@ -769,7 +780,7 @@ class ConvAct(Function):
                 native.call("ctvae_conv_forward_lazy", g[0], x.data_ptr(), w.data_ptr(), slices.data_ptr(), *g[1:],
                             ws.data_ptr(), ws.numel() * 4)
                 ctx.save_for_backward(x, None)
-                _last_fwd_slices = (slices, n, b)
+                tag(y).fwd_slices = (slices, n, b, _stamp(y))
                 return y
         x = _c(x)
         add_c = _c(add) if add is not None else None
@@ -908,13 +919,10 @@ class ConvBNAct(Function):
     def forward(ctx, x, w, b, gamma, beta, running_mean, running_var, training, spec, bn_act, num_batches_tracked=None,
                 lazy_out=False):
         """lazy_out (model code, blocks.Chain: the ONE consumer of the output applies BatchNorm + activation while it loads):
-        the returned tensor holds the raw conv output y and carries ``_ctvae_lazy_bn = (coef [2][C], act)``; the stand-alone
-        apply launch and the activated tensor do not exist.  An input tagged that way is read through its own coefficients."""
-        global _last_link
+        the returned tensor holds the raw conv output y and is tagged lazy_bn = (coef [2][C], act); the stand-alone apply launch and
+        the activated tensor do not exist.  An input tagged that way is read through its own coefficients.  Training tags bn_link."""
         _req_cuda(x, w, gamma)
-        ctx.link_in = link_of(x)
-        ctx.x_slices_ok = bool(getattr(x, "_ctvae_grad_slices_ok", False))
-        lazy_in = getattr(x, "_ctvae_lazy_bn", None) if x.is_contiguous() else None
+        ctx.link_in, lazy_in, ctx.x_slices_ok = _handovers_in(x)
         x = _c(x)
         y, a, coef, save_mean, save_invstd = _conv_bn_act_forward(
             x, (w, b, gamma, beta), (running_mean, running_var, num_batches_tracked), training, spec, bn_act, lazy_in,
@@ -923,12 +931,10 @@ class ConvBNAct(Function):
         ctx.params = (w, b, gamma, beta)
         ctx.lazy_in = lazy_in
         ctx.save_for_backward(x, y, save_mean, save_invstd)
-        ctx.link_out = _last_link = BNLink(y, save_mean, save_invstd, gamma, beta, bn_act) if training else None
-        if lazy_out:
-            global _last_lazy
-            _last_lazy = (coef, bn_act)        # picked up by the caller of .apply (pop_lazy_bn), which tags the returned tensor
-            return y                           # the output IS the raw conv output (also saved above for backward)
-        return a
+        out = y if lazy_out else a             # lazy_out: the output IS the raw conv output (also saved above for backward)
+        ctx.link_out = tag(out).bn_link = BNLink(y, save_mean, save_invstd, gamma, beta, bn_act) if training else None
+        tag(out).lazy_bn = (coef, bn_act) if lazy_out else None
+        return out
 
     @staticmethod
     def backward(ctx, g_a):
@@ -990,11 +996,10 @@ class ConvBNActConvAct(Function):
     @staticmethod
     def forward(ctx, x, w1, b1, gamma, beta, running_mean, running_var, num_batches_tracked, w2, b2, training, spec1, spec2, bn_act):
         _req_cuda(x, w1, w2, gamma)
-        ctx.link_in = link_of(x)
-        lazy_in = ctx.lazy_in = getattr(x, "_ctvae_lazy_bn", None) if x.is_contiguous() else None
+        ctx.link_in, ctx.lazy_in, _ = _handovers_in(x)
         x = _c(x)
         y1, _, coef, save_mean, save_invstd = _conv_bn_act_forward(
-            x, (w1, b1, gamma, beta), (running_mean, running_var, num_batches_tracked), training, spec1, bn_act, lazy_in,
+            x, (w1, b1, gamma, beta), (running_mean, running_var, num_batches_tracked), training, spec1, bn_act, ctx.lazy_in,
             want_a=False, want_coef=True)
         r = conv_forward_raw(y1, w2, b2, spec2, in_coef=coef, in_act=bn_act)
         ctx.act_out = offer_out_act_link(r, spec2.act) if (training and spec2.act != ACT_NONE) else None
@@ -1144,9 +1149,9 @@ class GaussianLatent(Function):
     log_var with a launch each and concatenates with a third."""
 
     @staticmethod
-    def forward(ctx, heads, eps, rng):
+    def forward(ctx, heads, eps, rng, fwd_slices=None):
         _req_cuda(heads)
-        fs = getattr(heads, "_ctvae_fwd_slices", None) if heads.is_contiguous() else None   # (slices, n, bias): heads not written yet
+        fs = check_fwd_slices(heads, fwd_slices)    # what flatten_linear(lazy_slices=True) returned next to heads: heads not written yet
         heads = _c(heads)
         B, L2 = heads.shape
         L = L2 // 2
@@ -1169,12 +1174,12 @@ class GaussianLatent(Function):
         B, L2 = heads.shape
         g_mu = _c(g_mu) if g_mu is not None else None
         g_lv = _c(g_lv) if g_lv is not None else None
-        lazy = claim_lazy_grad(g_z) if (g_z is not None and g_z.is_contiguous()) else None
+        lazy = claim_lazy_grad(g_z) if g_z is not None else None
         g_z = _c(g_z) if g_z is not None else None
         g_heads = torch.empty_like(heads)
         native.call("ctvae_gauss_latent_backward", native.ptr(g_mu), native.ptr(g_lv), lazy[0].data_ptr() if lazy else native.ptr(g_z),
                     heads.data_ptr(), eps.data_ptr(), g_heads.data_ptr(), native.ptr(ctx.rng), B, L2 // 2, lazy[1] if lazy else 0)
-        return g_heads, None, None
+        return g_heads, None, None, None
 
 
 def _scalar_outputs(ctx, out):
@@ -1725,22 +1730,26 @@ def backward(loss):
     ``ones_like(loss)`` on every call (one launch per step; the harness and bench.py call this).
 
     The slab reductions behind the weight-gradient kernels are deferred to the end of the pass (ctvae_defer_begin / _flush:
-    their slabs go into a 2 GB arena, one launch reduces all of them) -- a parameter gradient is complete when this returns."""
+    their slabs go into a 2 GB arena, one launch reduces all of them) -- a parameter gradient is complete when this returns.
+    Raises after the pass if a gradient placeholder on offer (_lazy_grads) was not claimed: the gradients of this pass are garbage."""
     key = (loss.device, loss.dtype, tuple(loss.shape))
     one = _ones.get(key)
     if one is None:
         one = _ones[key] = torch.ones_like(loss)
+    _lazy_grads.clear()            # placeholders of an earlier pass that nobody claimed (a pass cut short) are not valid in this one
     if not (_DEFER_REDUCE and loss.is_cuda):
         loss.backward(gradient=one)
-        return
-    _lazy_grads.clear()            # placeholders of an earlier pass that nobody claimed (a pass cut short) are not valid in this one
-    arena = _defer_arena_for(loss.device)
-    lib = native.load()
-    native.check(lib.ctvae_defer_begin(arena.data_ptr(), arena.numel() * 4), "ctvae_defer_begin")
-    try:
-        loss.backward(gradient=one)
-    finally:
-        native.check(lib.ctvae_defer_flush(native.stream_ptr()), "ctvae_defer_flush")
+    else:
+        arena = _defer_arena_for(loss.device)
+        lib = native.load()
+        native.check(lib.ctvae_defer_begin(arena.data_ptr(), arena.numel() * 4), "ctvae_defer_begin")
+        try:
+            loss.backward(gradient=one)
+        finally:
+            native.check(lib.ctvae_defer_flush(native.stream_ptr()), "ctvae_defer_flush")
+    if _lazy_grads:
+        _lazy_grads.clear()
+        raise RuntimeError("kernels.backward: a gradient left as split-K slices was never claimed (its tensor had a second consumer)")
 
 
 class PairMLP(Function):

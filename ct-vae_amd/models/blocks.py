@@ -12,15 +12,8 @@ def conv_bn_leaky(x, conv, bn, spec, training, lazy_out=False):
     """Conv (+bias) -> train/eval BatchNorm2d -> LeakyReLU on the holders `conv` / `bn`.  lazy_out: see kernels.ConvBNAct --
     only for a tensor whose one consumer is a ConvBNLeaky block that reads it through the coefficients (blocks.Chain)."""
     # num_batches_tracked is advanced by the finalize kernel (no separate launch)
-    a = K.ConvBNAct.apply(x, conv.weight, conv.bias, bn.weight, bn.bias, bn.running_mean, bn.running_var,
-                          training, spec, K.ACT_LRELU, bn.num_batches_tracked, lazy_out)
-    link = K.pop_bn_link()
-    if link is not None:
-        a._ctvae_bn_link = link     # lets the consumer's dgrad emit this BatchNorm's backward sums (kernels.BNLink)
-    lazy = K.pop_lazy_bn()
-    if lazy is not None:
-        a._ctvae_lazy_bn = lazy     # the tensor holds the raw conv output: the consumer applies BatchNorm + LeakyReLU on load
-    return a
+    return K.ConvBNAct.apply(x, conv.weight, conv.bias, bn.weight, bn.bias, bn.running_mean, bn.running_var,
+                             training, spec, K.ACT_LRELU, bn.num_batches_tracked, lazy_out)
 
 
 class ConvBNLeaky(nn.Module):

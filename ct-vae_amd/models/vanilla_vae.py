@@ -100,9 +100,9 @@ class VanillaVAE(BaseVAE):
         return K.to_nhwc(input)
 
     # -- reference API ----------------------------------------------------------------------------
-    def _encode_heads(self, input: Tensor, for_latent_node: bool = False) -> Tensor:
+    def _encode_heads(self, input: Tensor, for_latent_node: bool = False):
         """[B,C,64,64] -> [B, 2L]: fc_mu | fc_var of the flattened encoder output as one GEMM.  for_latent_node: the result goes to
-        kernels.GaussianLatent and nowhere else, which may then receive the GEMM's split-K slices instead of the summed tensor."""
+        kernels.GaussianLatent and nowhere else -- returns (heads, fwd_slices): the GEMM's split-K slices instead of the summed tensor."""
         self.attach_grads()
         h = K.mark_sole_consumer(self.encoder(self._input_nhwc(input)))   # [B,2,2,512] NHWC, read by the heads only
         if tuple(h.shape[1:3]) != (2, 2):
@@ -119,9 +119,7 @@ class VanillaVAE(BaseVAE):
         """[B,L] -> [B,3,64,64] (vanilla_vae.py:94-105)."""
         self.attach_grads()
         B = z.shape[0]
-        zr = z.reshape(B, 1, 1, -1)
-        if getattr(z, "_ctvae_grad_slices_ok", False):
-            K.grad_slices_ok(zr)
+        zr = K.carry_tag(z, z.reshape(B, 1, 1, -1))      # forward() below promised z's gradient to one consumer: that is zr's now
         if K.LinearToNHWC.supported(B, self._dec_in_spec.ci, 512, 4, z.device):
             # the Linear's own epilogue leaves .view(-1,512,2,2) as the NHWC tensor decoder.0 gathers (one launch less)
             h = K.grad_slices_ok(K.LinearToNHWC.apply(zr, self.decoder_input.weight, self.decoder_input.bias, self._dec_in_spec, 512, 2, 2))
@@ -149,15 +147,15 @@ class VanillaVAE(BaseVAE):
         """encode -> reparameterize -> decode (vanilla_vae.py:119-122).  The latent section runs as one node
         (kernels.GaussianLatent): with eps None and gradients on, the N(0,1) noise is drawn inside its kernel."""
         one_node = self.latent_dim % 4 == 0 and type(self).reparameterize is VanillaVAE.reparameterize
-        heads = self._encode_heads(input, for_latent_node=one_node)
         if one_node:
+            heads, fwd_slices = self._encode_heads(input, for_latent_node=True)
             if eps is None and not (torch.is_grad_enabled() and heads.requires_grad):
                 eps = torch.randn((heads.shape[0], self.latent_dim), dtype=heads.dtype, device=heads.device)   # no backward: no state bump
             rng = self._latent_rng(heads.device) if eps is None else None
-            mu, log_var, z = K.GaussianLatent.apply(heads, eps.to(heads.device) if eps is not None else None, rng)
+            mu, log_var, z = K.GaussianLatent.apply(heads, eps.to(heads.device) if eps is not None else None, rng, fwd_slices)
             K.grad_slices_ok(z)          # z's gradient comes back to that node only (decode below is its one consumer)
         else:
-            mu, log_var = K.SplitHeads.apply(heads, self.latent_dim)
+            mu, log_var = K.SplitHeads.apply(self._encode_heads(input), self.latent_dim)
             z = self.reparameterize(mu, log_var, eps)
         return [self.decode(z), input, mu, log_var]
 

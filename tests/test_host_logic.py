@@ -216,7 +216,8 @@ def test_placeholder_gradient_protocols():
     link = K.BNLink(y, torch.zeros(8), torch.ones(8), torch.ones(8), torch.zeros(8), K.ACT_LRELU)
     assert link.sole is False
     a = torch.zeros(2, 4, 4, 8)
-    a._ctvae_bn_link = link
+    K.tag(a).bn_link = link
+    assert K.tag_of(a).bn_link is link and K.tag_of(a.view(2, 16, 8)).bn_link is None     # tags do not follow views
     assert K.mark_sole_consumer(a) is a and link.sole is True
     assert K.mark_sole_consumer(torch.zeros(3)) is not None            # a tensor without a link: nothing to mark, no error
     g, slices = torch.empty(2, 4, 4, 8), torch.empty(3 * 256)
@@ -241,9 +242,109 @@ def test_placeholder_gradient_protocols():
     assert K.claim_lazy_grad(h) is None                                 # handed out once
     K.offer_lazy_grad(h, slices, 4)
     h.mul_(1.0)
-    assert K.claim_lazy_grad(h) is None                                 # modified since: not the placeholder any more
+    with pytest.raises(RuntimeError):
+        K.claim_lazy_grad(h)                                            # modified since: not the placeholder any more
+    assert K.claim_lazy_grad(h) is None                                 # (the misuse took the entry with it)
+    K.offer_lazy_grad(h, slices, 4)
+    with pytest.raises(RuntimeError):
+        K.claim_lazy_grad(h.view(2, 2, 64)[:, 0])                       # same address, another size
+    K.offer_lazy_grad(h, slices, 4)
+    with pytest.raises(RuntimeError):
+        K.claim_lazy_grad(h.t())                                        # same address and size, not contiguous
+    assert not K._lazy_grads
     t = K.grad_slices_ok(torch.zeros(2, 3))
-    assert t._ctvae_grad_slices_ok is True
+    assert K.tag_of(t).grad_slices_ok is True and K.tag_of(torch.zeros(2, 3)).grad_slices_ok is False
+    tr = K.carry_tag(t, t.reshape(2, 1, 1, 3))                          # model code hands a reshaped view on in t's place
+    assert K.tag_of(tr).grad_slices_ok is True and K.tag_of(tr).bn_link is None and K.tag_of(tr).fwd_slices is None
+
+
+def test_offer_table_cap_raises():
+    """The 17th offer while 16 are unclaimed raises: nothing is dropped silently."""
+    from ctvae_amd import kernels as K
+    K._lazy_grads.clear()
+    gs = [torch.empty(4) for _ in range(17)]
+    try:
+        for g in gs[:16]:
+            K.offer_lazy_grad(g, torch.empty(8), 2)
+        with pytest.raises(RuntimeError):
+            K.offer_lazy_grad(gs[16], torch.empty(8), 2)
+        assert len(K._lazy_grads) == 16 and K.claim_lazy_grad(gs[0])[1] == 2     # the 16 stay valid
+    finally:
+        K._lazy_grads.clear()
+
+
+def test_forward_slices_are_for_one_tensor():
+    """GaussianLatent's check of the forward slices handed over next to ``heads``: honoured for the untouched placeholder they were
+    stamped for (through carry_tag: for the view model code hands on), anything else raises."""
+    from ctvae_amd import kernels as K
+    y = torch.empty(4, 1, 1, 256)
+    K.tag(y).fwd_slices = (torch.empty(3 * 1024), 3, None, K._stamp(y))
+    heads = K.carry_tag(y, y.view(4, -1))
+    fs = K.tag_of(heads).fwd_slices
+    assert fs[:3] == K.tag_of(y).fwd_slices[:3] and fs[3] == K._stamp(heads)
+    assert K.check_fwd_slices(heads, fs) is fs
+    assert K.check_fwd_slices(heads, None) is None                      # no slices: an ordinary tensor
+    with pytest.raises(RuntimeError):
+        K.check_fwd_slices(torch.empty(4, 256), fs)                     # made for another tensor
+    with pytest.raises(RuntimeError):
+        K.check_fwd_slices(y, fs)                                       # the same memory under another shape: not what was handed on
+    with pytest.raises(RuntimeError):
+        K.check_fwd_slices(heads.t(), fs)
+    heads.add_(0.0)
+    with pytest.raises(RuntimeError):
+        K.check_fwd_slices(heads, fs)                                   # written since
+
+
+def test_unclaimed_gradient_placeholder_raises_after_the_pass():
+    """An offered placeholder whose tensor has a second consumer reaches the claiming node inside a sum, at another address: nobody
+    claims it, and kernels.backward raises once loss.backward has returned.  The table is empty afterwards: a correct pass runs."""
+    from ctvae_amd import kernels as K
+
+    class Offers(torch.autograd.Function):          # a layer whose data gradient stays slices behind an unwritten placeholder
+        @staticmethod
+        def forward(ctx, t):
+            return t * 2.0
+
+        @staticmethod
+        def backward(ctx, g):
+            ph = torch.zeros_like(g)                # (zeros, not empty: the sum below must not meet a signalling pattern)
+            K.offer_lazy_grad(ph, g * 2.0, 1)
+            return ph
+
+    class Claims(torch.autograd.Function):          # the one consumer that knows how to sum slices
+        @staticmethod
+        def forward(ctx, t):
+            return t.clone()
+
+        @staticmethod
+        def backward(ctx, g):
+            lazy = K.claim_lazy_grad(g)
+            return lazy[0] if lazy is not None else g
+
+    a = torch.ones(3, requires_grad=True)
+    t = Claims.apply(a)
+    with pytest.raises(RuntimeError, match="never claimed"):
+        K.backward(Offers.apply(t).sum() + t.sum())                     # t has two consumers: autograd hands Claims a sum
+    assert not K._lazy_grads
+    a.grad = None
+    K.backward(Offers.apply(Claims.apply(a)).sum())
+    assert torch.equal(a.grad, torch.full((3,), 2.0)) and not K._lazy_grads
+
+    class Fails(torch.autograd.Function):
+        @staticmethod
+        def forward(ctx, t):
+            return t.clone()
+
+        @staticmethod
+        def backward(ctx, g):
+            raise ValueError("from inside the pass")
+
+    with pytest.raises(ValueError, match="from inside the pass"):      # an exception of the pass itself propagates unchanged
+        K.backward(Offers.apply(Fails.apply(a)).sum())
+    assert len(K._lazy_grads) == 1                                      # the pass was cut short after the offer ...
+    a.grad = None
+    K.backward(Offers.apply(Claims.apply(a)).sum())                     # ... which the next pass drops before it starts
+    assert torch.equal(a.grad, torch.full((3,), 2.0)) and not K._lazy_grads
 
 
 def test_chain_marks_intermediates_and_keeps_reference_keys():

@@ -65,6 +65,79 @@ def test_vanilla_vs_golden(dev, golden, B):
         np.testing.assert_allclose(b.cpu().numpy(), g["buf1." + k], atol=1e-5, rtol=1e-4)
 
 
+def _placeholder_paths_are_live(m, B, dev):
+    """The library's own plan for VanillaVAE(3, 128) at batch B: all three never-written placeholders are in play (B = 4 is the
+    smallest such batch) -- heads (forward slices for GaussianLatent), the data gradients of decoder.0 and decoder_input
+    (pixel-major slices for LinearToNHWC / GaussianLatent), the data gradient of the heads (channel-major, for encoder.4's BatchNorm)."""
+    from ctvae_amd import kernels as K
+    from ctvae_amd import native
+    lib, ws = native.load(), native.workspace(dev).numel() * 4
+    heads = K.ConvSpec(K.CONV_FLAT, 512, 2 * m.latent_dim, 2, 2, 0).geom(B, 2, 2)
+    assert lib.ctvae_conv_forward_lazy_slices(*heads, ws) == 16
+    assert lib.ctvae_conv_backward_lazy_slices(*m.decoder[0].spec.geom(B, 2, 2), 0, ws) == 16
+    assert lib.ctvae_conv_backward_lazy_slices(*m._dec_in_spec.geom(B, 1, 1), 0, ws) == 16
+    assert lib.ctvae_conv_backward_lazy_slices(*heads, 1, ws) == 2
+
+
+def _vanilla_step_by_hand(m, xd, eps, second_consumer=False):
+    """VanillaVAE.forward + loss + kernels.backward spelled out; second_consumer: z is also read by the loss directly."""
+    from ctvae_amd import kernels as K
+    m.zero_grad()
+    heads, fwd_slices = m._encode_heads(xd, for_latent_node=True)
+    mu, log_var, z = K.GaussianLatent.apply(heads, eps, None, fwd_slices)
+    K.grad_slices_ok(z)
+    recons = m.decode(z)
+    loss = m.loss_function(recons, xd, mu, log_var, M_N=0.00025)["loss"]
+    K.backward(loss + z.sum() if second_consumer else loss)
+    torch.cuda.synchronize()
+    return loss.detach().clone(), recons.detach().clone()
+
+
+def test_vanilla_second_consumer_of_z_raises_and_leaves_nothing_behind(dev):
+    """z is promised to decode alone (grad_slices_ok): decoder_input leaves its data gradient as slices behind a placeholder that is
+    never written.  With a second consumer autograd hands GaussianLatent placeholder + the other gradient -- at another address, so
+    nobody claims the slices: kernels.backward raises after the pass (every launch has completed; the kernels only read allocated
+    memory).  The next ordinary step of the same model equals a fresh model's, bit for bit."""
+    from ctvae_amd import kernels as K
+    B, seed = 4, 41
+    x, eps = filler.synthetic_batch(seed, B)
+    xd, eps = x.to(dev), eps.to(dev)
+    m, fresh = build_vanilla(dev, seed), build_vanilla(dev, seed)
+    _placeholder_paths_are_live(m, B, dev)
+    with pytest.raises(RuntimeError, match="never claimed"):
+        _vanilla_step_by_hand(m, xd, eps, second_consumer=True)
+    assert not K._lazy_grads
+    _vanilla_step_by_hand(fresh, xd, eps)                   # the same forward passes on both sides: BatchNorm's running statistics
+    got, want = _vanilla_step_by_hand(m, xd, eps), _vanilla_step_by_hand(fresh, xd, eps)
+    assert torch.isfinite(want[0]) and torch.equal(got[0], want[0]) and torch.equal(got[1], want[1])
+    assert torch.isfinite(fresh.flat_grads).all() and fresh.flat_grads.abs().max() > 0
+    assert torch.equal(m.flat_grads, fresh.flat_grads)
+    for (k, a), (_, b) in zip(m.named_buffers(), fresh.named_buffers()):
+        assert torch.equal(a, b), k
+
+
+def test_vanilla_b4_step_runs_the_placeholder_kernels(dev):
+    """An ordinary B = 4 training step takes all three placeholder paths: the kernels that sum the slices ran."""
+    from ctvae_amd import kernels as K
+    from ctvae_amd import native
+    B, seed = 4, 41
+    x, eps = filler.synthetic_batch(seed, B)
+    m = build_vanilla(dev, seed)
+    _placeholder_paths_are_live(m, B, dev)
+    native.prof_report()
+    native.prof_enable(True)
+    try:
+        out = m(x.to(dev), eps=eps.to(dev))
+        K.backward(m.loss_function(*out, M_N=0.00025)["loss"])
+        torch.cuda.synchronize()
+    finally:
+        native.prof_enable(False)
+    rep = native.prof_report()
+    for name in ("gauss_latent_fwd_kernel", "gauss_latent_bwd_kernel", "splitk_permute_kernel", "bn_fused_bwd_kernel"):
+        assert name in rep and rep[name]["count"] >= 1, (name, sorted(rep))
+    assert not K._lazy_grads and torch.isfinite(m.flat_grads).all()
+
+
 def test_vanilla_vs_oracle_b16(dev):
     from oracle import vae_cpu as O
     seed, B = 77, 16

@@ -208,6 +208,41 @@ def test_conv_bn_lrelu(K, C, R_shape):
     np.testing.assert_allclose(bp.grad.cpu().numpy(), b.grad.numpy(), atol=TOL * 10, rtol=0)   # analytically zero
 
 
+def test_conv_bn_act_tags_the_tensor_it_returns(K):
+    """ConvBNAct.apply(lazy_out=True) in training: the BN link and the lazy-BN coefficients hang on the returned tensor itself --
+    nothing waits in module state for the caller to pick up."""
+    dev = torch.device("cuda")
+    B, H, Ci, C = 4, 8, 32, 64
+    g = torch.Generator().manual_seed(8)
+    spec = K.ConvSpec(K.CONV, Ci, C, 3, 1, 1, 0, K.ACT_NONE)
+    x = torch.randn(B, H, H, Ci, generator=g).to(dev).requires_grad_(True)
+    w = torch.randn(C, Ci, 3, 3, generator=g) / (Ci * 9) ** 0.5
+    wp = as_param(pack(w, False).to(dev), False)
+    bp, gp, btp = (torch.nn.Parameter(t.to(dev)) for t in (torch.randn(C, generator=g), torch.rand(C, generator=g) + 0.5, torch.rand(C, generator=g) - 0.5))
+    nbt = torch.zeros((), dtype=torch.long, device=dev)
+    y = K.ConvBNAct.apply(x, wp, bp, gp, btp, torch.zeros(C, device=dev), torch.ones(C, device=dev), True, spec, K.ACT_LRELU, nbt, True)
+    torch.cuda.synchronize()
+    t = K.tag_of(y)
+    assert isinstance(t.bn_link, K.BNLink) and t.bn_link.y is y and t.bn_link.sole is False
+    coef, act = t.lazy_bn
+    assert coef.numel() == 2 * C and act == K.ACT_LRELU
+    assert t.fwd_slices is None and t.grad_slices_ok is False
+    # y is the raw conv output; the coefficients are the BatchNorm's scale | shift over it
+    ref = F.conv2d(x.detach().cpu().permute(0, 3, 1, 2), w, bp.detach().cpu(), stride=1, padding=1)
+    np.testing.assert_allclose(y.detach().cpu().permute(0, 3, 1, 2).numpy(), ref.numpy(), atol=TOL, rtol=1e-4)
+    want = F.batch_norm(ref, None, None, gp.detach().cpu(), btp.detach().cpu(), True, 0.1, 1e-5)
+    got = y.detach().cpu() * coef[:C].cpu() + coef[C:].cpu()
+    np.testing.assert_allclose(got.permute(0, 3, 1, 2).numpy(), want.numpy(), atol=TOL, rtol=1e-4)
+    assert K.tag_of(y.view(B, H * H, C)).bn_link is None                 # tags do not follow views
+    # without lazy_out: the link only; in eval mode: neither
+    a = K.ConvBNAct.apply(x, wp, bp, gp, btp, torch.zeros(C, device=dev), torch.ones(C, device=dev), True, spec, K.ACT_LRELU, nbt)
+    assert K.tag_of(a).bn_link is not None and K.tag_of(a).lazy_bn is None
+    e = K.ConvBNAct.apply(x, wp, bp, gp, btp, torch.zeros(C, device=dev), torch.ones(C, device=dev), False, spec, K.ACT_LRELU, None)
+    assert K.tag_of(e).bn_link is None and K.tag_of(e).lazy_bn is None
+    for gone in ("_last_link", "_last_lazy", "_last_fwd_slices", "pop_bn_link", "pop_lazy_bn", "pop_fwd_slices"):
+        assert not hasattr(K, gone), gone
+
+
 def test_reparam_and_loss(K):
     g = torch.Generator().manual_seed(5)
     B, L = 6, 128
@@ -446,9 +481,9 @@ def test_bn_backward_sums_fused_into_dgrad(K, transposed, B, H):
         c1, c2, n1, n2 = mkconv(w1, b1), mkconv(w2, b2), mkbn(gm1, bt1), mkbn(gm2, bt2)
         xd = x.detach().permute(0, 2, 3, 1).contiguous().to(dev).requires_grad_(True)
         a1 = blocks.conv_bn_leaky(xd, c1, n1, sp1, True)
-        assert hasattr(a1, "_ctvae_bn_link")
+        assert K.tag_of(a1).bn_link is not None, "the output of conv_bn_leaky carries a BN link"
         if not fused:
-            del a1._ctvae_bn_link
+            K.tag(a1).bn_link = None
         a2 = blocks.conv_bn_leaky(a1, c2, n2, sp2, True)
         native.prof_enable(True)
         a2.backward(go.permute(0, 2, 3, 1).contiguous().to(dev))
