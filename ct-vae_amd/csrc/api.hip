@@ -32,7 +32,7 @@ int launch_bn_forward(const float* y, int R, int C, const float* gamma, const fl
 int launch_bn_finish_forward(const float* y, int R, int C, int nparts, const float* gamma, const float* beta,
                              float* running_mean, float* running_var, float momentum, float eps, int training, int act,
                              float* out, float* save_mean, float* save_invstd, float* ws, long long* nbt, hipStream_t st,
-                             float* coef_out = nullptr);
+                             float* coef_out = nullptr, const float* mean_base = nullptr);
 size_t bn_workspace_floats(int C, int nparts);
 int launch_bn_backward(const float* ga, const float* beta, const float* y, int R, int C, const float* gamma,
                        const float* save_mean, const float* save_invstd, int act, float* gy, float* dgamma, float* dbeta,

@@ -33,7 +33,10 @@ __device__ __forceinline__ void chan_merge(float& n, float& mean, float& m2, flo
 }
 
 // ---- forward statistics (stand-alone form; the conv epilogue normally provides the partials) -----------
-// thread = (column quad, row lane); part[blk][c] = (n, mean, M2).  Requires (C/4) | 256.
+// thread = (column quad, row lane); part[blk][c] = (n, mean - y[0][c], M2).  Requires (C/4) | 256.
+// The means are kept relative to row 0 of their channel until the finalize adds it back (its `mean_base`): a float32 mean
+// carries a rounding of u|mu|, and the d*d term of a Chan merge would turn it into a variance error ~ u|mu|*sigma.  Relative
+// to a sample of the channel every merged quantity is of the order of sigma.
 __global__ __launch_bounds__(256) void bn_stats_partial_kernel(const float* __restrict__ y, float* __restrict__ part,
                                                                int R, int C, int rows_per_block) {
   __shared__ float sm[256 * 9];
@@ -47,6 +50,7 @@ __global__ __launch_bounds__(256) void bn_stats_partial_kernel(const float* __re
   if (r1 > R) r1 = R;
   for (int q0 = 0; q0 < Q; q0 += qpp) {
     const int col = 4 * (q0 + ql);
+    const f32x4 base = *reinterpret_cast<const f32x4*>(y + col);
     float n = 0.f;
     f32x4 mean = {0.f, 0.f, 0.f, 0.f}, m2 = {0.f, 0.f, 0.f, 0.f};
     if (r0 + rlane < r1) {
@@ -67,7 +71,7 @@ __global__ __launch_bounds__(256) void bn_stats_partial_kernel(const float* __re
       n = (float)cnt;
 #pragma unroll
       for (int k = 0; k < 4; ++k) {
-        mean[k] = shift[k] + s1[k] / n;
+        mean[k] = (shift[k] - base[k]) + s1[k] / n;
         float q = s2[k] - s1[k] * s1[k] / n;
         m2[k] = q > 0.f ? q : 0.f;
       }
@@ -107,7 +111,8 @@ __global__ __launch_bounds__(256) void bn_finalize_kernel(const float* __restric
                                                           float* __restrict__ running_mean, float* __restrict__ running_var,
                                                           float momentum, float eps, float* __restrict__ save_mean,
                                                           float* __restrict__ save_invstd, float* __restrict__ scale,
-                                                          float* __restrict__ shift, long long* __restrict__ num_batches_tracked) {
+                                                          float* __restrict__ shift, long long* __restrict__ num_batches_tracked,
+                                                          const float* __restrict__ mean_base) {
   __shared__ float sm[256 * 3];
   const int tid = threadIdx.x;
   const int c = blockIdx.x;
@@ -141,6 +146,7 @@ __global__ __launch_bounds__(256) void bn_finalize_kernel(const float* __restric
     __syncthreads();
   }
   if (tid == 0) {
+    if (mean_base != nullptr) mean += mean_base[c];   // partial means relative to row 0 (bn_stats_partial_kernel)
     const float var = m2 / n;
     const float invstd = 1.0f / sqrtf(var + eps);
     save_mean[c] = mean;
@@ -168,7 +174,7 @@ __global__ __launch_bounds__(256) void bn_finalize_apply_kernel(const float* __r
                                                                 float* __restrict__ save_mean, float* __restrict__ save_invstd,
                                                                 float* __restrict__ scale, float* __restrict__ shift,
                                                                 long long* __restrict__ num_batches_tracked, float* __restrict__ out,
-                                                                int act) {
+                                                                int act, const float* __restrict__ mean_base) {
   __shared__ float sm[256 * 3];
   __shared__ __attribute__((aligned(16))) float sSc[32], sSh[32];
   const int tid = threadIdx.x, cb = blockIdx.x, rs = blockIdx.y;
@@ -195,6 +201,7 @@ __global__ __launch_bounds__(256) void bn_finalize_apply_kernel(const float* __r
       chan_merge(n, mean, m2, o[0], o[1], o[2]);
     }
     const int c = c0 + ch;
+    if (mean_base != nullptr) mean += mean_base[c];   // partial means relative to row 0 (bn_stats_partial_kernel)
     const float var = m2 / n;
     const float invstd = 1.0f / sqrtf(var + eps);
     const float sc = gamma[c] * invstd, sh = beta[c] - mean * sc;
@@ -576,7 +583,7 @@ __device__ __forceinline__ void slice_sum4(f32x4 (&v)[CPW], const float* __restr
 // write-backs and eight fills per line.  Whole lines per XCD instead: id = (line % 8) + 8 * (slot + slots * (line / 8)).
 __device__ __forceinline__ int fused_group(int id, int C, int cpw) {
   const int slots = 32 / cpw, lines = C / 32;
-  if (lines % 8 != 0) return id;
+  if (lines == 0 || lines % 8 != 0) return id;   // fewer than 32 channels: one partial line, nothing to deal out
   const int x = id & 7, t = id >> 3, slot = t % slots, jh = t / slots;
   return (jh * 8 + x) * slots + slot;
 }
@@ -817,11 +824,12 @@ size_t bn_workspace_floats(int C, int nparts) {
   return parts * C * 3 + 5 * (size_t)C;
 }
 
-// finalize (from `nparts` partial triples already in ws) or eval coefficients, then apply + activation
+// finalize (from `nparts` partial triples already in ws) or eval coefficients, then apply + activation.  mean_base [C]: what
+// the means of the triples are relative to (null: absolute, as the conv epilogues write them)
 int launch_bn_finish_forward(const float* y, int R, int C, int nparts, const float* gamma, const float* beta,
                              float* running_mean, float* running_var, float momentum, float eps, int training, int act,
                              float* out, float* save_mean, float* save_invstd, float* ws, long long* nbt, hipStream_t st,
-                             float* coef_out) {
+                             float* coef_out, const float* mean_base) {
   const size_t parts = nparts > kBnMaxBlocks ? (size_t)nparts : (size_t)kBnMaxBlocks;
   float* scale = coef_out != nullptr ? coef_out : ws + parts * C * 3;   // coef_out [2][C]: kept by the caller (lazy apply)
   float* shift = scale + C;
@@ -831,14 +839,14 @@ int launch_bn_finish_forward(const float* y, int R, int C, int nparts, const flo
     if (rsn < 1) rsn = 1;
     ProfScope ps("bn_finalize_apply_kernel", st, 0.0, 8.0 * (double)R * C + 12.0 * (double)nparts * C * rsn);
     hipLaunchKernelGGL(bn_finalize_apply_kernel, dim3(C / 32, rsn), dim3(256), 0, st, y, ws, nparts, R, C, gamma, beta, running_mean,
-                       running_var, momentum, eps, save_mean, save_invstd, scale, shift, nbt, out, act);
+                       running_var, momentum, eps, save_mean, save_invstd, scale, shift, nbt, out, act, mean_base);
     CTVAE_LAUNCH_CHECK();
     return 0;
   }
   if (training) {
     ProfScope ps("bn_finalize_kernel", st, 0.0, 12.0 * (double)nparts * C);
     hipLaunchKernelGGL(bn_finalize_kernel, dim3(C), dim3(256), 0, st, ws, nparts, C, gamma, beta, running_mean,
-                       running_var, momentum, eps, save_mean, save_invstd, scale, shift, nbt);
+                       running_var, momentum, eps, save_mean, save_invstd, scale, shift, nbt, mean_base);
     CTVAE_LAUNCH_CHECK();
   } else {
     hipLaunchKernelGGL(bn_eval_coeff_kernel, dim3(ceil_div(C, 256)), dim3(256), 0, st, C, gamma, beta, running_mean,
@@ -870,7 +878,7 @@ int launch_bn_forward(const float* y, int R, int C, const float* gamma, const fl
     CTVAE_LAUNCH_CHECK();
   }
   return launch_bn_finish_forward(y, R, C, nb, gamma, beta, running_mean, running_var, momentum, eps, training, act, out,
-                                  save_mean, save_invstd, ws, nbt, st, coef_out);
+                                  save_mean, save_invstd, ws, nbt, st, coef_out, training ? y : nullptr);
 }
 
 int launch_bn_backward(const float* ga, const float* beta, const float* y, int R, int C, const float* gamma,

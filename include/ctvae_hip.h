@@ -185,7 +185,9 @@ int ctvae_conv_wgrad_bn_apply_supported(int kind, int B, int H, int W, int Ci, i
 /* Train/eval BatchNorm2d + activation on an [R=B*H*W][C] matrix (vanilla_vae.py:30-31,56-57,71-72).
  * training: batch statistics (biased var, eps), running stats updated with `momentum` and the unbiased
  * variance; save_mean/save_invstd [C] are written for the backward pass; num_batches_tracked (may be NULL) is
- * incremented on the device (nn.BatchNorm2d bookkeeping without an extra launch). */
+ * incremented on the device (nn.BatchNorm2d bookkeeping without an extra launch).
+ * Shapes (ctvae_bn_forward and ctvae_bn_backward; kErrBadArg otherwise): R > 0, C % 4 == 0, and C/4 divides 256 or is a
+ * multiple of it (C = 4, 8, 16, ... 1024, 2048, 3072, ...).  ws: at least (2048 * 3 + 5) * C floats, kErrWorkspace otherwise. */
 int ctvae_bn_forward(const float* y, int R, int C, const float* gamma, const float* beta, float* running_mean,
                      float* running_var, float momentum, float eps, int training, int act, float* out,
                      float* save_mean, float* save_invstd, int64_t* num_batches_tracked, float* ws, size_t ws_bytes,
