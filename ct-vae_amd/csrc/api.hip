@@ -173,6 +173,10 @@ int launch_image_grid_each_u8(const float* x, long sN, long sC, long sH, long sW
                               int normalize, int has_range, float lo, float hi, float pad_value, int scanlines, uint8_t* out,
                               size_t out_bytes, float* ws, size_t ws_bytes, hipStream_t st);
 int launch_action_hits(const float* probas, const float* action, int N, int A, int* counts, hipStream_t st);
+int launch_graph_accumulate(const float* adj, const int* group, const float* mask, float thr, int B, int S, int G, double* adj_sum,
+                            int* edge_count, double* mask_sum, int* rows, int* mask_rows, int* skipped, hipStream_t st);
+int launch_heatmap_u8(const float* values, int M, int H, int W, float lo, float hi, int cell, int nrow, int pad, int pad_r, int pad_g,
+                      int pad_b, const uint8_t* table, int scanlines, uint8_t* out, size_t out_bytes, hipStream_t st);
 int launch_loss_forward(const float* r, const float* x, long n, const float* mu, long mu_rs, const float* lv, long lv_rs,
                         int B, int L, float M_N, const float* extra, float* out4, float* ws, size_t ws_bytes,
                         hipStream_t st, float logcosh_alpha, float* g_r = nullptr, float* g_mu = nullptr, float* g_lv = nullptr,
@@ -1062,6 +1066,19 @@ int ctvae_image_grid_each_u8(const float* x, long stride_n, long stride_c, long 
 
 int ctvae_action_hits(const float* probas, const float* action, int N, int A, int* counts, void* stream) {
   return launch_action_hits(probas, action, N, A, counts, (hipStream_t)stream);
+}
+
+int ctvae_graph_accumulate(const float* adj, const int32_t* group, const float* mask, float threshold, int B, int S, int G,
+                           double* adj_sum, int32_t* edge_count, double* mask_sum, int32_t* rows, int32_t* mask_rows,
+                           int32_t* skipped, void* stream) {
+  return launch_graph_accumulate(adj, group, mask, threshold, B, S, G, adj_sum, edge_count, mask_sum, rows, mask_rows, skipped,
+                                 (hipStream_t)stream);
+}
+
+int ctvae_heatmap_u8(const float* values, int M, int H, int W, float lo, float hi, int cell, int nrow, int padding, int pad_r,
+                     int pad_g, int pad_b, const uint8_t* table, int scanlines, uint8_t* out, size_t out_bytes, void* stream) {
+  return launch_heatmap_u8(values, M, H, W, lo, hi, cell, nrow, padding, pad_r, pad_g, pad_b, table, scanlines, out, out_bytes,
+                           (hipStream_t)stream);
 }
 
 size_t ctvae_adam_state_floats(void) { return adam_state_floats(); }

@@ -26,6 +26,17 @@ hand out, is passed on as its one mode, so that ``CTMCQVAE.generate``'s causal -
 run as it found it: eval mode and ``no_grad`` (no BatchNorm statistics, no in-kernel noise state, no parameter epoch move), its
 ``torch.randn`` draws come from generators seeded from ``manual_seed`` and the epoch, and torch's CPU / device generator states
 are put back afterwards.
+
+``val_graphs`` (CT-MCQ-VAE only; ``exp_params.val_graphs`` in run.py): during every validation epoch a
+``causalgraph.GraphStats`` is the ``graph_observer`` of the model's causal-transition layer, so the validation steps' own
+launches leave their per-sample adjacencies and intervention masks in per-group sums (group 0: base mode, group 1 + a: action a;
+the causal-mode batches' hypothesised actions are not observed).  Afterwards rank 0 writes
+``Graphs/adjacency_<name>_Epoch_<e>.png`` -- the mean adjacency of every group that had rows, group 0 first, one tile each --
+and ``Graphs/mask_<name>_Epoch_<e>.png`` -- the mean mask of every action that had rows as an h x w picture -- under
+``sample_dir``, and adds ``val_graph_edges_<group>``, the mean number of edges above 0.5 per graph, to the epoch record and the
+JSONL log.  Validation is eager, the captured training steps never see the observer, and it draws nothing: the run's
+trajectory is the same with and without it.  With several ranks the pictures and numbers are rank 0's own validation rows; the
+graphs are not reduced across ranks.
 """
 import contextlib
 import json
@@ -156,11 +167,22 @@ def seeded_torch_rng(seed: int, device):
 class VAEXperiment:
 
     SAMPLE_DIRS = ("Inputs", "Reconstructions", "Samples")
+    GRAPH_DIR = "Graphs"
+    MASK_CELL = 16             # pixels per latent position in the mask sheet (the adjacency sheet: causalgraph's 4 per edge)
 
     def __init__(self, vae_model, params: dict, ddp: GradBucketAllReduce = None, log_every: int = 50, log_file=None,
                  gradient_clip_val=None, gradient_clip_algorithm=None, val_metric=None, val_sampling: bool = False,
-                 sample_dir=None, run_name=None):
+                 sample_dir=None, run_name=None, val_graphs: bool = False):
         self.val_metric = val_metric
+        self.val_graphs = bool(val_graphs)
+        if self.val_graphs:
+            from .models.ct_mcq_vae import CTMCQVAE
+            if not isinstance(vae_model, CTMCQVAE):
+                raise ValueError(f"val_graphs needs a CTMCQVAE (the graphs are its causal-transition layer's), got "
+                                 f"{type(vae_model).__name__}")
+            if vae_model.ct_layer.action_dim < 2 or vae_model.ct_layer.action_dim % 2:
+                raise ValueError(f"val_graphs names its groups as factors in two directions: action_dim must be even and at least "
+                                 f"2, got {vae_model.ct_layer.action_dim}")
         self.val_sampling, self.sample_dir = bool(val_sampling), sample_dir
         self.run_name = run_name if run_name is not None else type(vae_model).__name__
         self.gradient_clip_val, self.gradient_clip_algorithm = clip_settings(gradient_clip_val, gradient_clip_algorithm)
@@ -264,8 +286,34 @@ class VAEXperiment:
                 pass
         return written
 
+    def write_graphs(self, stats, epoch: int) -> dict:
+        """What ``val_graphs`` leaves of one validation epoch (module docstring): the two sheets under ``sample_dir`` (when there
+        is one, and only for groups that had rows) and the ``val_graph_edges_<group>`` scalars, which also go to the JSONL
+        log.  One device -> host copy."""
+        from . import causalgraph
+        res = stats.result()
+        summary = causalgraph.summarize(res)
+        rec = {f"val_graph_edges_{k}": v["edges"] for k, v in summary.items() if v["edges"] is not None}
+        if self.sample_dir is not None:
+            d = os.path.join(self.sample_dir, self.GRAPH_DIR)
+            seen = [g for g in range(stats.G) if res["rows"][g] > 0]
+            masked = [g for g in range(1, stats.G) if res["mask_rows"][g] > 0]
+            if seen or masked:
+                os.makedirs(d, exist_ok=True)
+            if seen:
+                causalgraph.save_heatmaps(res["adjacency_mean"][seen], os.path.join(d, f"adjacency_{self.run_name}_Epoch_{epoch}.png"))
+            if masked and res["hw"] is not None:
+                h, w = res["hw"]
+                causalgraph.save_heatmaps(res["mask_mean"][masked].reshape(len(masked), -1, w),
+                                          os.path.join(d, f"mask_{self.run_name}_Epoch_{epoch}.png"), cell=self.MASK_CELL)
+        if self.log_file is not None and rec:
+            self.log_file.write(json.dumps({**rec, "step": self.global_step}) + "\n")
+            self.log_file.flush()
+        return rec
+
     def log_all(self, losses: dict, batch_size, validation: bool = False, force: bool = False):
-        """Scalar tensors only (strings / images are dropped like experiment.py:93-106); one fused all-reduce over
+        """Scalar tensors only (strings are dropped like experiment.py:93-106; the reference logs the 2-D ``ct_adjacency`` /
+        ``ct_mask`` batch means as images, here ``val_graphs`` writes them per action instead); one fused all-reduce over
         ranks (sync_dist=True) and one D2H copy."""
         if not force and (self.global_step % self.log_every) != 0:
             return None
@@ -407,13 +455,26 @@ class VAEXperiment:
             if val_batches is not None:
                 self.model.eval()
                 sums, cnt = {}, 0
-                for i, batch in enumerate(val_batches()):
-                    r = self.validation_step(batch, i)
-                    for k, v in r.items():
-                        if k != "step":
-                            sums[k] = sums.get(k, 0.0) + v
-                    cnt += 1
+                stats = None
+                if self.val_graphs and self._rank0():
+                    from . import causalgraph
+                    ct = self.model.ct_layer
+                    stats = causalgraph.GraphStats(ct.action_dim + 1, causalgraph.model_nodes(self.model),
+                                                   next(self.model.parameters()).device)
+                    ct.graph_observer = stats.observe
+                try:
+                    for i, batch in enumerate(val_batches()):
+                        r = self.validation_step(batch, i)
+                        for k, v in r.items():
+                            if k != "step":
+                                sums[k] = sums.get(k, 0.0) + v
+                        cnt += 1
+                finally:
+                    if stats is not None:
+                        self.model.ct_layer.graph_observer = None
                 rec.update({k: v / max(cnt, 1) for k, v in sums.items()})
+                if stats is not None:
+                    rec.update(self.write_graphs(stats, epoch))
                 rec.update(self.validation_metrics(epoch))
                 if self.val_sampling and self.sample_dir is not None and test_batches is not None and self._rank0():
                     first = next(iter(test_batches()), None)

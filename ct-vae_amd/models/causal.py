@@ -281,6 +281,10 @@ class CausalTransition(nn.Module):
         self.mask = nn.Sequential(nn.Linear(action_dim + input_dim, input_dim), nn.Sigmoid())
         self.nb_heads = 1 + action_dim
         self.graph_transitioner = _GraphTransitioner(input_dim, latent_dims[1:], self.nb_heads)
+        # None, or a callable (adjacency [B,S,S], mask [B,S] or None, group int32 [B] or None, (h, w)) that forward / forward_action
+        # hand the per-sample adjacency to before its batch mean (causalgraph.GraphStats.observe); forward_transition's
+        # hypothesised actions are not shown to it
+        self.graph_observer = None
 
     # ---- pieces ----------------------------------------------------------------------------------
     def _pair_coeffs(self, disc, x):
@@ -403,6 +407,8 @@ class CausalTransition(nn.Module):
         pos = self.pos_encoding(lat)
         action = torch.zeros(lat.size(0), self.action_dim, device=lat.device)
         adj = self._compute_adj(pos, action, None)             # mask == 0 in base mode
+        if self.graph_observer is not None:
+            self.graph_observer(adj, None, None, tuple(shape[2:]))
         graph, weighted = sample_bernoulli_st(adj, "adj_gumbel", True)
         latent_y = self._compute_y(pos, action, weighted, None)
         ident = torch.eye(graph.size(-1), device=lat.device, dtype=graph.dtype).expand_as(graph)
@@ -418,6 +424,8 @@ class CausalTransition(nn.Module):
         mask = self._compute_mask(lat, action)
         pos = self.pos_encoding(lat)
         adj = self._compute_adj(pos, action, mask)
+        if self.graph_observer is not None and kwargs.get("_observe", True):
+            self.graph_observer(adj, mask.reshape(shape[0], -1), self._action_group(action), tuple(shape[2:]))
         graph, weighted = sample_bernoulli_st(adj, "adj_gumbel", True)
         latent_y = self._compute_y(pos, action, weighted, mask)
         if adj.is_cuda and adj.size(-1) == 64:            # the three regularisers in one launch each way (csrc/ctmisc.hip)
@@ -435,7 +443,7 @@ class CausalTransition(nn.Module):
         dist = []
         for i in range(A):
             a = F.one_hot(torch.full((B,), i, device=latent.device), A).to(latent.dtype)
-            y = self.forward_action(latent, a)[0]
+            y = self.forward_action(latent, a, _observe=False)[0]
             y_log = y.permute(0, 2, 3, 1).reshape(-1, latent_y.size(1)).clamp(min=1e-4).log()
             dist.append(F.cross_entropy(y_log, y_inds, reduction='none').view(B, -1).mean(dim=-1))
         return [F.softmin(torch.stack(dist, 1), dim=-1), torch.zeros((), device=latent.device), {}]

@@ -14,6 +14,9 @@ ground-truth factor grid the ``hbm_images`` rows enumerate row-major) adds the d
 ``exp_params.val_sampling: true`` (the reference's run.py hard-wires it on; here it defaults to false) writes the input,
 reconstruction and sample PNG grids of the first test batch after every validation epoch into ``Inputs/``, ``Reconstructions/``
 and ``Samples/`` of the run's log directory, named after ``logging_params.name`` (experiment.py: ``sample_images``).
+``exp_params.val_graphs: true`` (CT-MCQ-VAE only) writes the mean learned adjacency per action and the mean intervention mask
+per action after every validation epoch into ``Graphs/`` of the log directory and adds ``val_graph_edges_<group>`` to the epoch
+records (experiment.py: ``val_graphs``); with several ranks they show rank 0's own validation rows.
 """
 import argparse
 import json
@@ -188,6 +191,11 @@ def main(argv=None):
     torch.manual_seed(seed)                                           # seed_everything (run.py:48)
     mp = dict(config['model_params'])
     model = vae_models[mp['name']](**mp).to(dev)
+    val_graphs = bool(config['exp_params'].get('val_graphs', False))
+    if val_graphs:
+        from .models.ct_mcq_vae import CTMCQVAE
+        if not isinstance(model, CTMCQVAE):
+            raise SystemExit(f"exp_params.val_graphs needs a CTMCQVAE, model_params.name is {mp['name']!r}")
     # trainer_params.resume_from_checkpoint (run.py:85-101): with load_weights_only the reference loads the model's weights
     # (strict=False) and drops the key; without it the path is splatted into the Lightning Trainer, which restores optimizer,
     # scheduler, epoch and global step and continues -- the "trainer" entry of our checkpoints carries exactly that state
@@ -206,9 +214,11 @@ def main(argv=None):
     if val_sampling and rank == 0:
         for d in VAEXperiment.SAMPLE_DIRS:
             os.makedirs(os.path.join(log_dir, d), exist_ok=True)
+    if val_graphs and rank == 0:
+        os.makedirs(os.path.join(log_dir, VAEXperiment.GRAPH_DIR), exist_ok=True)
     exp = VAEXperiment(model, config['exp_params'], ddp=ddp, log_file=log_file, gradient_clip_val=tp.get('gradient_clip_val'),
                        gradient_clip_algorithm=tp.get('gradient_clip_algorithm'), val_sampling=val_sampling, sample_dir=log_dir,
-                       run_name=config['logging_params'].get('name', mp['name']))
+                       run_name=config['logging_params'].get('name', mp['name']), val_graphs=val_graphs)
     if config['data_params'].get('hbm_images'):
         data = HbmData(config['data_params'], mp, dev, rank, world, seed)
     else:

@@ -581,6 +581,36 @@ int ctvae_image_grid_each_u8(const float* x, long stride_n, long stride_c, long 
  * and the first NaN wins.  A even, 2 <= A <= 256; N == 0 is a successful no-op; N < 0, another A or a NULL pointer returns -22. */
 int ctvae_action_hits(const float* probas, const float* action, int N, int A, int* counts, void* stream);
 
+/* Per-group statistics of CT-MCQ-VAE's learned graphs (causalgraph.py: GraphStats).  One batch -- adj [B][S][S], the per-sample
+ * adjacency; group [B] int32, 0 = no intervention, 1 + a = action a; mask [B][S], the intervention mask, or NULL -- is ADDED
+ * into accumulators for G groups (device memory, zero before the first call):
+ *   adj_sum [G][S][S] double     sum of the group's adjacencies
+ *   edge_count [G][S][S] int32   rows with adj > threshold (strict; NaN does not count)
+ *   mask_sum [G][S] double       sum of the group's masks          (untouched when mask is NULL)
+ *   rows [G] int32               rows of the group
+ *   mask_rows [G] int32          rows of the group that came with a mask (untouched when mask is NULL)
+ *   skipped [1] int32            rows whose group lies outside [0, G); such a row touches nothing else
+ * Every element ends up as if the rows had been added one at a time in ascending row order onto what earlier calls left
+ * (float -> double conversion, then one double add per row): one owner per element, no atomics, so the result is bit-identical
+ * however the rows are split into calls and from run to run.  One launch, no host synchronisation; the int32 counts hold up to
+ * 2^31 - 1 rows.  Any S in 1 .. 46340 and G in 1 .. 65535; B == 0 is a successful no-op; B < 0, another S or G or a NULL pointer
+ * (mask excepted) returns -22 and launches nothing. */
+int ctvae_graph_accumulate(const float* adj, const int32_t* group, const float* mask, float threshold, int B, int S, int G,
+                           double* adj_sum, int32_t* edge_count, double* mask_sum, int32_t* rows, int32_t* mask_rows,
+                           int32_t* skipped, void* stream);
+
+/* values [M][H][W] f32 (contiguous) as a colour-mapped, tiled sheet (causalgraph.py: heatmap_u8): every value becomes cell x cell
+ * pixels of colour table[floor(t*255 + 0.5)] with t = (clamp(v, lo, hi) - lo) / (hi - lo), every operation rounded to f32 on its
+ * own (ctvae_image_grid_u8's byte conversion); NaN takes entry 0, +-inf clamp.  table: 256 x RGB bytes in HOST memory, read
+ * before the call returns.  The layout is ctvae_image_grid_u8's for M images of H*cell x W*cell pixels: xmaps = min(nrow, M),
+ * ymaps = ceil(M / xmaps), borders and the empty cells of the last grid row hold the colour (pad_r, pad_g, pad_b), each 0 .. 255;
+ * out is Hg rows of 3*Wg bytes, or with scanlines != 0 of 1 + 3*Wg bytes led by PNG filter type 0; 16-byte aligned, out_bytes at
+ * least the stream's length rounded up to a multiple of 4, bytes past the stream's length are not written.  One pass, no
+ * upscaled intermediate.  A bad argument (M / H / W / cell / nrow < 1, padding < 0, hi <= lo or NaN, a colour outside 0 .. 255,
+ * NULL pointers, a stream of 2^31 bytes or more, out too small or misaligned) returns -22 and launches nothing. */
+int ctvae_heatmap_u8(const float* values, int M, int H, int W, float lo, float hi, int cell, int nrow, int padding, int pad_r,
+                     int pad_g, int pad_b, const uint8_t* table, int scanlines, uint8_t* out, size_t out_bytes, void* stream);
+
 /* MSSIMVAE's reconstruction loss (mssim_vae.py:182-279): 1 - prod_{i<4} (mcs_i^w_i * mssim_4^w_4) over five levels of SSIM with the
  * reference's 11-tap window (2x2 average pooling between levels), for NHWC pictures a (the reconstruction) and b [B,64,64,C].
  * window [11] and weights [5]: HOST arrays (the window as the reference builds it: exp(+(x-5)^2 / 4.5), normalised).
