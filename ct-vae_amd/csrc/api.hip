@@ -135,6 +135,9 @@ int launch_adam_block_flags_finish(const float* bstate, int* active, int nb, int
 int launch_adam_blocks(float* p, const float* g, float* m, float* v, float* state, long n, float grad_scale, int algorithm,
                        float clip, float* ws, float* norm_out, const int* blk_lo, const int* blk_hi, float* bstate,
                        const int* active, int nb, hipStream_t st);
+size_t grad_accumulate_pass_floats();
+int launch_grad_accumulate(float* acc, float* g, long n, int mode, hipStream_t st);
+int launch_adam_flags_window(int* window, int* active, int nb, int mode, hipStream_t st);
 int launch_ssim_forward(const float* a, const float* b, const float* window, float* part, float* loss, float* coef, int B, int C, int H,
                         int W, const float* weights, hipStream_t st);
 int launch_ssim_backward(const float* a, const float* b, const float* window, const float* coef, const float* g_loss, float* g_a, int B,
@@ -1141,6 +1144,16 @@ int ctvae_adam_step_blocks(float* params, const float* grads, float* exp_avg, fl
   if (algorithm == CTVAE_CLIP_NORM && !workspace) return kErrBadArg;
   return launch_adam_blocks(params, grads, exp_avg, exp_avg_sq, state, n, grad_scale, algorithm, clip_val, workspace, norm_out,
                             block_lo, block_hi, block_state, active, nb, (hipStream_t)stream);
+}
+
+size_t ctvae_grad_accumulate_pass_floats(void) { return grad_accumulate_pass_floats(); }
+
+int ctvae_grad_accumulate(float* acc, float* grads, long n, int mode, void* stream) {
+  return launch_grad_accumulate(acc, grads, n, mode, (hipStream_t)stream);
+}
+
+int ctvae_adam_flags_window(int* window, int* active, int nb, int mode, void* stream) {
+  return launch_adam_flags_window(window, active, nb, mode, (hipStream_t)stream);
 }
 
 }  // extern "C"

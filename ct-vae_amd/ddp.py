@@ -22,6 +22,7 @@ class GradBucketAllReduce:
         self.active = self.world > 1 or (force and dist.is_initialized())
         self.bucket_elems = max(1, bucket_bytes // 4)
         self.range = None
+        self.accumulate = 1        # VAEXperiment sets its accumulate_grad_batches here (all_reduce_range)
         if self.active and broadcast_from is not None:
             self.broadcast_parameters(broadcast_from)
 
@@ -66,7 +67,11 @@ class GradBucketAllReduce:
 
     def all_reduce_range(self, lo, hi, async_op=True):
         """Asynchronous SUM all-reduce of flat_grads[lo:hi] (bucketed), ordered behind everything issued so far on the
-        current stream.  Returns the work handles for wait()."""
+        current stream.  Returns the work handles for wait().  Refused under gradient accumulation: a range of ONE
+        micro-batch's gradients would travel while the window's sum is still being formed (SplitBackward's overlap)."""
+        if self.accumulate > 1:
+            raise RuntimeError(f"all_reduce_range (SplitBackward's ranged exchange) is not available with accumulate_grad_batches="
+                               f"{self.accumulate}: the gradients are exchanged once per window, after its last micro-batch")
         if not self.active or hi <= lo:
             return []
         if hasattr(self.model, "gather_torch_grads"):

@@ -10,6 +10,19 @@ a DDP gradient exchange the two skip modes MAX-reduce their per-block activity f
 machinery: one flat fused Adam launch, one bucketed RCCL all-reduce, and scalars fetched with ONE device
 -> host copy every ``log_every`` steps instead of one ``.item()`` sync per key per step (experiment.py:95-96).
 
+``accumulate_grad_batches`` (the Trainer key of that name, an integer k >= 1; 1 is the path above, launch for launch): Lightning
+1.6.5's gradient accumulation.  The batch index counts from 0 in every epoch; batch i ends a window when (i + 1) % k == 0 or it
+is the epoch's last batch (``fit()`` looks one batch ahead, so the loader's batches must not share storage), and the optimizer
+steps there, on (sum of the window's gradients) / k -- divided by k, not by the window's length, in an incomplete last window
+too.  No window state crosses an epoch boundary.  ``zero_grad`` runs before every micro-batch; BatchNorm statistics, the models'
+loss-call counters and the in-kernel noise advance per micro-batch; clipping and weight decay apply once per window
+(``FlatAdam.stash`` / ``step``, optim.py).  ``global_step`` counts optimizer steps, a training record is logged on a window's last
+micro-batch (its own un-normalised losses) when ``global_step % log_every == 0``, ``train_images`` counts every image.  Captured
+steps end behind ``gather_torch_grads()`` when k > 1, as they do under DDP, and the stash or step launches follow the replay
+eagerly: one graph per signature serves every position in a window.  Under DDP a micro-batch inside a window issues no
+collective at all; the one that ends it sends the merged block flags (skip modes) and the window's sum, and steps with
+``grad_scale = 1 / (world * k)``.  ``ddp.SplitBackward``'s ranged exchange is refused in this mode.
+
 ``val_metric`` (a ``metrics.MetricSet``): the reference recomputes the disentanglement metrics inside EVERY validation batch
 and lets Lightning average the copies (experiment.py:72-74).  That is a cost, not a semantic -- the metric does not read the
 batch -- so ``fit()`` computes it ONCE per validation epoch, after the validation batches, on rank 0 only and without a
@@ -50,7 +63,7 @@ from . import imagegrid
 from . import kernels as K
 from .ddp import GradBucketAllReduce
 from .metrics import _eval_mode as eval_mode
-from .optim import ExponentialLR, FlatAdam, absent_grad_setting, clip_settings
+from .optim import ExponentialLR, FlatAdam, absent_grad_setting, accumulate_setting, clip_settings, with_window_ends
 
 
 def _graph_key(real_img, kwargs):
@@ -69,8 +82,9 @@ def _graph_key(real_img, kwargs):
 
 
 class _GraphedTrainStep:
-    """zero_grad + forward + loss + backward (+ Adam when there is no gradient exchange) of one batch signature, captured
-    once into a hipGraph and replayed: ~130 launches per VanillaVAE step -- ~400 per CT-MCQ-VAE step -- are host-bound when
+    """zero_grad + forward + loss + backward (+ Adam when there is neither a gradient exchange nor gradient accumulation: with
+    either, what follows the gradients runs eagerly behind the replay) of one batch signature, captured once into a hipGraph
+    and replayed: ~130 launches per VanillaVAE step -- ~400 per CT-MCQ-VAE step -- are host-bound when
     issued eagerly (VanillaVAE bs=256: 3.5 vs 1.8 ms; CT-MCQ-VAE at the YAML's 16 pairs per GPU: 7.5 vs 3.4 ms).
     The first WARM batches of a signature run eagerly as ordinary training steps; capture itself executes nothing, so the
     training trajectory is exactly the eager one.  A signature = input shape + the shapes of the tensor options (input_y,
@@ -103,7 +117,7 @@ class _GraphedTrainStep:
         # its flat view and copies nothing, while every replay rewrites the graph-pool tensors autograd produced: from the second
         # replay on those parameters would be exchanged and stepped with a zero gradient
         exp.model.gather_torch_grads()
-        if exp.ddp is None:
+        if exp.ddp is None and exp.accumulate == 1:
             exp.optimizer.step()
             pat = exp.optimizer.host_pattern
             if pat is not None:              # constant per signature: a replay repeats the capture step's launches and flags
@@ -121,8 +135,10 @@ class _GraphedTrainStep:
         # signature's capture, where running them on that other stream ends the capture with a fault
         return {k: (v.detach() if torch.is_tensor(v) else v) for k, v in losses.items()}
 
-    def run(self, real_img, kwargs=None):
+    def run(self, real_img, kwargs=None, ends_window=True):
+        """ends_window (gradient accumulation only): whether this micro-batch is followed by the optimizer step."""
         exp = self.exp
+        in_graph = exp.ddp is None and exp.accumulate == 1       # Adam is part of the body
         K.stage_batch(self.x, real_img)
         for k, t in self.static.items():
             t.copy_(kwargs[k], non_blocking=True)
@@ -134,15 +150,18 @@ class _GraphedTrainStep:
             self.graph = g
         if self.graph is not None:
             self.graph.replay()
-            if exp.ddp is None:
+            if in_graph:
                 K.bump_param_epoch()       # the replayed Adam launch changed the parameters behind Python's back
             losses = self.losses
         else:
             losses = self._body()
         self.seen += 1
-        if exp.ddp is not None:
+        if exp.accumulate > 1:
+            exp.window_step(ends_window, self.pattern)
+        elif exp.ddp is not None:
             exp.ddp_step(self.pattern)
-        exp.global_step += 1
+        if ends_window:
+            exp.global_step += 1
         return losses
 
 
@@ -172,7 +191,9 @@ class VAEXperiment:
 
     def __init__(self, vae_model, params: dict, ddp: GradBucketAllReduce = None, log_every: int = 50, log_file=None,
                  gradient_clip_val=None, gradient_clip_algorithm=None, val_metric=None, val_sampling: bool = False,
-                 sample_dir=None, run_name=None, val_graphs: bool = False):
+                 sample_dir=None, run_name=None, val_graphs: bool = False, accumulate_grad_batches=None):
+        self.accumulate = accumulate_setting(accumulate_grad_batches)
+        self._log_train = True      # training_step logs; fit() clears it for micro-batches that do not end their window
         self.val_metric = val_metric
         self.val_graphs = bool(val_graphs)
         if self.val_graphs:
@@ -200,6 +221,8 @@ class VAEXperiment:
         self.optimizer, self.scheduler = self.configure_optimizers()
         if ddp is not None and "update_parameters" in params:
             ddp.restrict(self.optimizer.slice)
+        if ddp is not None and self.accumulate > 1:
+            ddp.accumulate = self.accumulate      # (the exchange refuses ranged, SplitBackward-style calls from now on)
         self._graphed = {}          # (shape, dtype) -> _GraphedTrainStep
 
     def forward(self, input, **kwargs):
@@ -217,7 +240,8 @@ class VAEXperiment:
         results = self.forward(real_img, labels=labels, **kwargs)
         train_loss = self.model.loss_function(*results, M_N=self.params['kld_weight'], optimizer_idx=optimizer_idx,
                                               batch_idx=batch_idx)
-        self.log_all(train_loss, batch_size=real_img.size(0), validation=False)
+        if self._log_train:
+            self.log_all(train_loss, batch_size=real_img.size(0), validation=False)
         return train_loss['loss']
 
     def validation_step(self, batch, batch_idx, optimizer_idx=0):
@@ -338,7 +362,7 @@ class VAEXperiment:
             sl = self.model.flat_range(self.params["update_parameters"])
         opt = FlatAdam(self.model, lr=self.params['LR'], weight_decay=self.params.get('weight_decay', 0.0), params_slice=sl,
                        clip_val=self.gradient_clip_val, clip_algorithm=self.gradient_clip_algorithm,
-                       absent_grad=absent_grad_setting(self.params.get("adam_absent_grad")))
+                       absent_grad=absent_grad_setting(self.params.get("adam_absent_grad")), accumulate=self.accumulate)
         sched = None
         if self.params.get('scheduler_gamma') is not None:
             sched = ExponentialLR(opt, self.params['scheduler_gamma'])
@@ -395,21 +419,41 @@ class VAEXperiment:
         """Gradient exchange + optimizer step of a data-parallel run (1 / world folded into the step).  In the skip modes the
         step first forms this rank's block flags; their MAX all-reduce goes out from inside the step (``reduce_flags``) with
         the gradient buckets right behind it, so the small collective is under way before the large ones are queued.
-        pattern: see FlatAdam.step (a replayed captured step hands over its capture step's)."""
+        pattern: see FlatAdam.step (a replayed captured step hands over its capture step's).  Under gradient accumulation this
+        is the step of the micro-batch that ends a window: the window's sum is finished into the flat gradient buffer before
+        the buckets travel, the merged flags before theirs do, and 1 / k joins 1 / world in ``grad_scale``."""
         ddp, opt = self.ddp, self.optimizer
+        scale = ddp.grad_scale / self.accumulate
         if opt.absent_grad == "zero":
+            if self.accumulate > 1:
+                opt.finish_window()
             ddp.all_reduce()
-            opt.step(grad_scale=ddp.grad_scale)
+            opt.step(grad_scale=scale)
             return
 
         def flags_then_grads(flags):
             ddp.all_reduce_flags(flags)
             ddp.all_reduce()
 
-        opt.step(grad_scale=ddp.grad_scale, reduce_flags=flags_then_grads, pattern=pattern)
+        opt.step(grad_scale=scale, reduce_flags=flags_then_grads, pattern=pattern)
+
+    def window_step(self, ends_window, pattern=None):
+        """What follows a micro-batch's backward pass under gradient accumulation (``accumulate`` > 1).  A micro-batch inside
+        its window is stashed (``FlatAdam.stash``: no collective, no step).  The one that ends the window steps on (stashed sum
+        + its own gradients) / k -- divided by k, not by the window's length, also in an epoch's incomplete last window, as
+        Lightning divides every loss by k -- with clipping and weight decay applied once, to that gradient."""
+        if not ends_window:
+            self.optimizer.stash(pattern)
+        elif self.ddp is not None:
+            self.ddp_step(pattern)
+        else:
+            self.optimizer.step(grad_scale=1.0 / self.accumulate, pattern=pattern)
 
     def optimizer_step(self):
-        if self.ddp is not None:
+        """One optimizer step on the gradients in the flat buffer (under gradient accumulation: the end of a window)."""
+        if self.accumulate > 1:
+            self.window_step(True)
+        elif self.ddp is not None:
             self.ddp_step()
         else:
             self.optimizer.step()
@@ -425,7 +469,11 @@ class VAEXperiment:
             self.model.train()
             t0 = time.time()
             n = 0
-            for i, batch in enumerate(train_batches()):
+            k = self.accumulate
+            # k > 1: the batch index counts from 0 in every epoch, and the epoch's last batch ends its window whatever its index
+            # (one batch of look-ahead: the loader is an iterable) -- no window state crosses an epoch boundary
+            stream = ((b, True) for b in train_batches()) if k == 1 else with_window_ends(train_batches(), k)
+            for i, (batch, ends) in enumerate(stream):
                 real_img, _labels, kwargs = self._unpack(batch)
                 # graph_safe = False: the model's step depends on host state that changes per call (e.g. BetaVAE type 'B':
                 # the capacity C follows the loss-call counter), so a captured step would freeze it
@@ -438,16 +486,25 @@ class VAEXperiment:
                     if gs is None:
                         gs = self._graphed[key] = _GraphedTrainStep(self, real_img, kwargs)
                     self.curr_device = real_img.device
-                    losses = gs.run(real_img, kwargs)
-                    self.global_step -= 1                  # log_all keys on the step that just ran
-                    self.log_all(losses, batch_size=real_img.size(0), validation=False)
-                    self.global_step += 1
+                    losses = gs.run(real_img, kwargs, ends)
+                    if ends:
+                        self.global_step -= 1              # log_all keys on the step that just ran
+                        self.log_all(losses, batch_size=real_img.size(0), validation=False)
+                        self.global_step += 1
                 else:
                     self.model.zero_grad(lazy=True)
-                    loss = self.training_step(batch, i)
+                    self._log_train = ends                 # a record per optimizer step, with the losses of its last micro-batch
+                    try:
+                        loss = self.training_step(batch, i)
+                    finally:
+                        self._log_train = True
                     K.backward(loss)
                     self.model.settle_grads()
-                    self.optimizer_step()
+                    if k == 1:
+                        self.optimizer_step()
+                    else:
+                        self.window_step(ends)
+                        self.global_step += int(ends)
                 n += batch[0].size(0)
             if self.scheduler is not None:
                 self.scheduler.step()                      # Lightning steps ExponentialLR once per epoch

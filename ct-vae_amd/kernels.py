@@ -2578,3 +2578,35 @@ def adam_step_blocks(flat_params, flat_grads, exp_avg, exp_avg_sq, state, table,
                 state.data_ptr(), flat_params.numel(), float(grad_scale), CLIP_OFF if algorithm is None else CLIP_ALGORITHMS[algorithm],
                 0.0 if clip_val is None else float(clip_val), native.ptr(workspace), native.ptr(norm_out), table.lo.data_ptr(),
                 table.hi.data_ptr(), table.state.data_ptr(), table.active.data_ptr(), table.nb)
+
+
+GRAD_ACCUM_MODES = {"store": 0, "add": 1, "finish": 2}          # CTVAE_ACCUM_STORE / _ADD / _FINISH
+
+
+def grad_accumulate(acc, grads, mode):
+    """One micro-batch of a gradient-accumulation window (ctvae_grad_accumulate), on two equally long fp32 vectors: "store"
+    acc = grads, "add" acc += grads, "finish" grads = acc + grads (the window's sum lands in the gradient buffer, acc stays)."""
+    _req_cuda(acc, grads)
+    if acc.numel() != grads.numel() or acc.dtype != torch.float32 or grads.dtype != torch.float32 \
+            or not (acc.is_contiguous() and grads.is_contiguous()):
+        raise ValueError("grad_accumulate: acc and grads are contiguous fp32 vectors of one length")
+    native.call("ctvae_grad_accumulate", acc.data_ptr(), grads.data_ptr(), acc.numel(), GRAD_ACCUM_MODES[mode])
+
+
+def grad_accumulator_like(grads):
+    """A zeroed accumulator for ``grads`` (a slice of the flat gradient buffer) that sits at the same offset from a 16-byte
+    boundary as the slice does, so that grad_accumulate runs its 16-byte loop on both."""
+    n = grads.numel()
+    buf = torch.zeros(n + 3, dtype=torch.float32, device=grads.device)
+    shift = ((grads.data_ptr() - buf.data_ptr()) // 4) % 4
+    return buf[shift:shift + n]
+
+
+def adam_flags_window(window, table, mode):
+    """The block-activity words of one micro-batch (table.active, after adam_block_flags_local) against the window's
+    (ctvae_adam_flags_window): "store" window = active, "add" window = max(window, active), "finish" active = max(window,
+    active) -- what adam_block_flags_finish and adam_step_blocks(flags_final=True) then read."""
+    _req_cuda(window, table.active)
+    if window.numel() != table.nb or window.dtype != torch.int32:
+        raise ValueError("adam_flags_window: window is one int32 word per block of the table")
+    native.call("ctvae_adam_flags_window", window.data_ptr(), table.active.data_ptr(), table.nb, GRAD_ACCUM_MODES[mode])

@@ -42,6 +42,19 @@ slice of the gradient after the DDP scale and before the weight decay, on the de
 ``"norm"`` = ``torch.nn.utils.clip_grad_norm_(max_norm=clip_val)`` (one extra launch, the squared-norm pass; the pre-clip
 norm is left in the device tensor ``grad_norm``), ``"value"`` = ``clip_grad_value_(clip_val)`` (folded into the Adam launch).
 Non-finite norms behave as in torch: NaN makes every updated element NaN, inf clips everything to zero.
+
+Gradient accumulation (Lightning's ``accumulate_grad_batches: k``, ``FlatAdam(accumulate=k)``; k = 1 allocates and launches
+nothing).  ``zero_grad`` still runs before every micro-batch; the sum of a window's gradients lives in a buffer of its own, the
+size of the optimizer's slice.  ``stash()`` takes a micro-batch that does not end its window into that buffer (one
+``ctvae_grad_accumulate`` launch: "store" for the first, "add" after it), ``step()`` ends the window: a "finish" launch leaves
+stashed sum + current gradients in the flat gradient buffer, and the exchange, the clip and the Adam kernels run on it as on a
+single batch's -- so clipping and weight decay apply once per window, and ``grad_norm`` is the norm of the gradient that is
+stepped.  The caller folds 1 / k into ``grad_scale`` next to 1 / world (also for an epoch's incomplete last window: Lightning
+divides every loss by k).  In the skip modes a block is active in the window's step iff it was active in at least one
+micro-batch, by host pattern and device hit words as in a single step: every stash forms its micro-batch's flags
+(``adam_block_flags_local``, which consumes the hit words) and merges them into the window's (``ctvae_adam_flags_window``); the
+step merges its own, reduces them across ranks if asked to, and only then does "skip_until_first" add the blocks that have
+stepped before.  ``accumulation_schedule`` / ``with_window_ends`` say which batches of an epoch end a window.
 """
 import math
 
@@ -63,6 +76,43 @@ def clip_settings(clip_val, algorithm=None):
     return (float(clip_val) if clip_val > 0 else None), algo.lower()
 
 
+ACCUMULATE_KEY = "accumulate_grad_batches"
+
+
+def accumulate_setting(value):
+    """Validated ``accumulate_grad_batches``: an integer k >= 1, None meaning 1.  A bool, a float, a number below 1 or a dict
+    (Lightning's per-epoch schedule, which is not supported) raises a ValueError that names the key."""
+    if value is None:
+        return 1
+    if isinstance(value, dict):
+        raise ValueError(f"{ACCUMULATE_KEY} {value!r} is invalid: a per-epoch schedule {{epoch: k}} is not supported, give one "
+                         "integer >= 1")
+    if isinstance(value, bool) or not isinstance(value, int) or value < 1:
+        raise ValueError(f"{ACCUMULATE_KEY} {value!r} is invalid: it must be an integer >= 1")
+    return int(value)
+
+
+def with_window_ends(batches, k):
+    """``(batch, ends_window)`` over one epoch's iterable of batches, by Lightning 1.6.5's rule: batch i (counted from 0 in every
+    epoch) ends a window, i.e. is followed by the optimizer step, when (i + 1) % k == 0 or it is the epoch's last batch.  The
+    loader's length need not be known: the generator looks one batch ahead."""
+    it = iter(batches)
+    try:
+        cur = next(it)
+    except StopIteration:
+        return
+    i = 0
+    for nxt in it:
+        yield cur, (i + 1) % k == 0
+        cur, i = nxt, i + 1
+    yield cur, True
+
+
+def accumulation_schedule(n_batches, k):
+    """``with_window_ends``' rule for an epoch of ``n_batches`` batches: one bool per batch, True where a window ends."""
+    return [ends for _, ends in with_window_ends(range(n_batches), k)]
+
+
 def absent_grad_setting(value):
     """Validated ``absent_grad`` (module docstring); None means the default, "zero"."""
     v = "zero" if value is None else value
@@ -73,8 +123,12 @@ def absent_grad_setting(value):
 
 class FlatAdam:
     def __init__(self, model, lr, weight_decay=0.0, betas=(0.9, 0.999), eps=1e-8, params_slice=None, clip_val=None,
-                 clip_algorithm="norm", absent_grad="zero"):
+                 clip_algorithm="norm", absent_grad="zero", accumulate=1):
         self.model = model
+        self.accumulate = accumulate_setting(accumulate)
+        self.acc = self.window_flags = None         # the window's gradient sum / block flags: exist only when accumulate > 1
+        self.stashed = 0                            # micro-batches of the current window in `acc`
+        self._merge_flags = False                   # finish_window() ran: the coming step merges the window's block flags
         flat = model.flat_params
         self.slice = params_slice if params_slice is not None else slice(0, flat.numel())
         n = flat[self.slice].numel()
@@ -91,6 +145,10 @@ class FlatAdam:
         self.blocks = self.table = self.host_pattern = None
         if self.absent_grad != "zero":
             self._build_block_table(n, flat.device)
+        if self.accumulate > 1:
+            self.acc = K.grad_accumulator_like(model._flat_grads[self.slice])    # (flat_params above built both buffers)
+            if self.table is not None:
+                self.window_flags = torch.zeros_like(self.table.active)
 
     # -- block table (absent_grad "skip" / "skip_until_first") ---------------------------------------------
     def _build_block_table(self, n, device):
@@ -147,30 +205,71 @@ class FlatAdam:
         self.lr = lr
         self.state[1:2].fill_(lr)
 
+    def _present(self, pattern, device):
+        """The device words of the host-known activity ``pattern`` (None: the model's current one); sets ``host_pattern``."""
+        pat = self._host_pattern() if pattern is None else tuple(pattern)
+        present = self._patterns.get(pat)
+        if present is None:
+            if device.type == "cuda" and torch.cuda.is_current_stream_capturing():
+                raise RuntimeError("FlatAdam: the step being captured has gradients for other blocks than every eager step "
+                                   "before it; a captured step's host-known activity must be constant")
+            present = self._patterns[pat] = torch.tensor(pat, dtype=torch.int32, device=device)
+        self.host_pattern = pat
+        return present
+
+    def stash(self, pattern=None):
+        """Gradient accumulation (``accumulate`` > 1): add the current micro-batch's gradients to the window's sum instead of
+        stepping.  One ``grad_accumulate`` launch over the slice ("store" for a window's first micro-batch, "add" after it); in
+        the skip modes also this micro-batch's block flags (``adam_block_flags_local``, which consumes the hit words) and their
+        merge into the window's (``adam_flags_window``).  The micro-batch that ends the window is not stashed: ``step()`` adds
+        the sum to it.  pattern: as in ``step``."""
+        if self.acc is None:
+            raise RuntimeError("FlatAdam.stash: this optimizer was built without gradient accumulation (accumulate=1)")
+        self.model.gather_torch_grads()
+        mode = "store" if self.stashed == 0 else "add"
+        K.grad_accumulate(self.acc, self.model.flat_grads[self.slice], mode)
+        if self.absent_grad != "zero":
+            K.adam_block_flags_local(self.table, self._present(pattern, self.acc.device))
+            K.adam_flags_window(self.window_flags, self.table, mode)
+        self.stashed += 1
+
+    def finish_window(self):
+        """The "finish" ``grad_accumulate`` launch of a window with stashed micro-batches: stashed sum + current gradients, left
+        in the flat gradient buffer.  ``step()`` runs it itself; a caller that exchanges the gradients in front of the step
+        (data-parallel training without block flags) calls it before the exchange.  Nothing without a stash."""
+        self.model.gather_torch_grads()
+        if self.stashed:
+            K.grad_accumulate(self.acc, self.model.flat_grads[self.slice], "finish")
+            self.stashed, self._merge_flags = 0, True
+
     def step(self, grad_scale=1.0, reduce_flags=None, pattern=None):
         """reduce_flags (skip modes only; data-parallel training): a callable that MAX-reduces the int32 [nb] flags tensor it
         is handed across ranks, in place and ordered on the current stream.  The step then runs local flags -> reduce_flags ->
         finish -> update, so that a block steps on every rank iff it got a gradient on at least one.  pattern: the host-known
         activity to use instead of the model's current one (a replayed captured step: the host still holds whatever the last
-        step that ran Python left)."""
-        self.model.gather_torch_grads()
+        step that ran Python left).
+
+        After ``stash()`` calls the step ends their window: the "finish" ``grad_accumulate`` launch first leaves stashed sum +
+        current gradients in the flat gradient buffer, where the exchange (``reduce_flags`` is called behind it), the clip pass
+        and the Adam kernels find it as they find a single batch's; in the skip modes the flags run local -> window merge ->
+        [reduce_flags] -> finish, so a block steps iff some micro-batch of the window had a gradient for it.  The caller folds
+        the window's 1 / k into ``grad_scale``.  Without a stash the step issues no accumulation launch."""
+        self.finish_window()
         p, g = self.model.flat_params[self.slice], self.model.flat_grads[self.slice]
+        window, self._merge_flags = self._merge_flags, False
         if self.absent_grad != "zero":
-            pat = self._host_pattern() if pattern is None else tuple(pattern)
-            present = self._patterns.get(pat)
-            if present is None:
-                if p.is_cuda and torch.cuda.is_current_stream_capturing():
-                    raise RuntimeError("FlatAdam: the step being captured has gradients for other blocks than every eager step "
-                                       "before it; a captured step's host-known activity must be constant")
-                present = self._patterns[pat] = torch.tensor(pat, dtype=torch.int32, device=p.device)
-            self.host_pattern = pat
-            if reduce_flags is not None:
+            present = self._present(pattern, p.device)
+            split = window or reduce_flags is not None
+            if split:
                 K.adam_block_flags_local(self.table, present)
-                reduce_flags(self.table.active)
+                if window:
+                    K.adam_flags_window(self.window_flags, self.table, "finish")
+                if reduce_flags is not None:
+                    reduce_flags(self.table.active)
                 K.adam_block_flags_finish(self.table, self.absent_grad)
             K.adam_step_blocks(p, g, self.exp_avg, self.exp_avg_sq, self.state, self.table, present, self.absent_grad, grad_scale,
                                None if self.clip_val is None else self.clip_algorithm, self.clip_val, self.clip_ws, self.grad_norm,
-                               flags_final=reduce_flags is not None)
+                               flags_final=split)
         elif self.clip_val is None:
             K.adam_step(p, g, self.exp_avg, self.exp_avg_sq, self.state, grad_scale)
         else:

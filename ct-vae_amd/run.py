@@ -9,6 +9,8 @@ so they interchange with the reference's (run.py:85-97), plus a ``trainer`` entr
 step, random streams) for ``trainer_params.resume_from_checkpoint`` without ``load_weights_only`` (run.py:85-101: full resume).
 ``trainer_params.gradient_clip_val`` / ``gradient_clip_algorithm`` clip the gradients before every optimizer step as the
 Lightning Trainer does (configs/gammavae.yaml); without them the step is unchanged.
+``trainer_params.accumulate_grad_batches: k`` (an integer >= 1; Lightning's ``{epoch: k}`` schedule is refused) steps the
+optimizer once per window of k batches on the window's gradient sum / k (experiment.py, optim.py); absent or 1 changes nothing.
 ``exp_params.metrics`` (run.py:64-76; "MIG", "FactorVaeScore") with ``data_params.hbm_factor_sizes`` (the sizes of the
 ground-truth factor grid the ``hbm_images`` rows enumerate row-major) adds the disentanglement metrics to every validation epoch.
 ``exp_params.val_sampling: true`` (the reference's run.py hard-wires it on; here it defaults to false) writes the input,
@@ -30,6 +32,7 @@ from . import filler
 from .ddp import GradBucketAllReduce
 from .experiment import VAEXperiment
 from .models import vae_models
+from .optim import accumulate_setting
 
 
 class SyntheticData:
@@ -165,6 +168,15 @@ def build_val_metric(config, data):
         raise SystemExit(f"exp_params.metrics: {e}")
 
 
+def trainer_accumulate(trainer_params) -> int:
+    """``trainer_params.accumulate_grad_batches`` as the k of VAEXperiment (absent: 1); a value that is not an integer >= 1
+    -- a bool, a float, Lightning's ``{epoch: k}`` schedule -- is a SystemExit that names the key."""
+    try:
+        return accumulate_setting(trainer_params.get('accumulate_grad_batches'))
+    except ValueError as e:
+        raise SystemExit(f"trainer_params.{e}")
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser(description='MI355X runner for the ct-vae models')
     ap.add_argument('--config', '-c', dest="filename", metavar='FILE', default='configs/vae.yaml')
@@ -210,6 +222,7 @@ def main(argv=None):
     os.makedirs(os.path.join(log_dir, "checkpoints"), exist_ok=True)
     log_file = open(os.path.join(log_dir, f"metrics_rank{rank}.jsonl"), "a") if rank == 0 else None
     tp = config['trainer_params']
+    accumulate = trainer_accumulate(tp)
     val_sampling = bool(config['exp_params'].get('val_sampling', False))
     if val_sampling and rank == 0:
         for d in VAEXperiment.SAMPLE_DIRS:
@@ -218,7 +231,8 @@ def main(argv=None):
         os.makedirs(os.path.join(log_dir, VAEXperiment.GRAPH_DIR), exist_ok=True)
     exp = VAEXperiment(model, config['exp_params'], ddp=ddp, log_file=log_file, gradient_clip_val=tp.get('gradient_clip_val'),
                        gradient_clip_algorithm=tp.get('gradient_clip_algorithm'), val_sampling=val_sampling, sample_dir=log_dir,
-                       run_name=config['logging_params'].get('name', mp['name']), val_graphs=val_graphs)
+                       run_name=config['logging_params'].get('name', mp['name']), val_graphs=val_graphs,
+                       accumulate_grad_batches=accumulate)
     if config['data_params'].get('hbm_images'):
         data = HbmData(config['data_params'], mp, dev, rank, world, seed)
     else:

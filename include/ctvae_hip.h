@@ -692,6 +692,26 @@ int ctvae_adam_step_blocks(float* params, const float* grads, float* exp_avg, fl
                            float grad_scale, int algorithm, float clip_val, float* workspace, float* norm_out,
                            const int* block_lo, const int* block_hi, float* block_state, const int* active, int nb, void* stream);
 
+/* Gradient accumulation over the micro-batches of one optimizer step (Lightning's accumulate_grad_batches): the window's running
+ * sum `acc` (n floats of the caller's) against the optimizer's slice `grads` of the flat gradient buffer, one launch:
+ *   CTVAE_ACCUM_STORE   acc = grads            the first micro-batch of a window
+ *   CTVAE_ACCUM_ADD     acc = acc + grads      every further one that does not end the window
+ *   CTVAE_ACCUM_FINISH  grads = acc + grads    the one that ends it; acc is left as it is
+ * One correctly rounded fp32 add per element with acc as the left operand, so the result depends on the values alone.  Either
+ * pointer may sit at any float; 16-byte accesses are used where grads and acc have the same offset from a 16-byte boundary
+ * (otherwise the range is walked float by float).  The two ranges must not overlap.  Nothing outside [0, n) is touched.
+ * ctvae_grad_accumulate_pass_floats: the floats one turn of the kernel's full grid covers (a longer range wraps its loop).
+ * ctvae_adam_flags_window: the same three modes on the nb int32 block-activity words of ctvae_adam_block_flags_local, a
+ * launch of its own: window = active, window = max(window, active), active = max(window, active) -- a block steps at the end
+ * of a window iff some micro-batch of it had a gradient for it.  The caller then runs ctvae_adam_block_flags_finish (behind
+ * its reduction across ranks, if any) and ctvae_adam_step_blocks on `active`. */
+#define CTVAE_ACCUM_STORE 0
+#define CTVAE_ACCUM_ADD 1
+#define CTVAE_ACCUM_FINISH 2
+size_t ctvae_grad_accumulate_pass_floats(void);
+int ctvae_grad_accumulate(float* acc, float* grads, long n, int mode, void* stream);
+int ctvae_adam_flags_window(int* window, int* active, int nb, int mode, void* stream);
+
 /* Input side: the reference's per-sample pipeline ToTensor -> CenterCrop(crop) -> Resize(size)
  * (dataset.py:72-80; bilinear, align_corners=False, no antialias -- what transforms.Resize does to a tensor; images smaller
  * than the crop are zero-padded as torchvision's center_crop does) for a batch of rows of a uint8 dataset
