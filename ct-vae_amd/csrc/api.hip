@@ -138,6 +138,13 @@ int launch_adam_blocks(float* p, const float* g, float* m, float* v, float* stat
 size_t grad_accumulate_pass_floats();
 int launch_grad_accumulate(float* acc, float* g, long n, int mode, hipStream_t st);
 int launch_adam_flags_window(int* window, int* active, int nb, int mode, hipStream_t st);
+size_t grad_segment_chunk_floats();
+int launch_grad_segment_stats(const float* g, long n, float scale, float p, const long* seg, int nseg, const int* chunk_seg,
+                              const long* chunk_first, const int* seg_chunk_begin, int nchunks, double* part_sum, float* part_f,
+                              int* part_bad, double* out_sum, float* out_range, int* out_bad, int* out_hist, const int* flags_in,
+                              int* flags_out, int nflags, hipStream_t st);
+int launch_grad_segment_hist(const float* g, long n, float scale, const long* seg, int nseg, const int* chunk_seg,
+                             const long* chunk_first, int nchunks, const float* out_range, int* out_hist, hipStream_t st);
 int launch_ssim_forward(const float* a, const float* b, const float* window, float* part, float* loss, float* coef, int B, int C, int H,
                         int W, const float* weights, hipStream_t st);
 int launch_ssim_backward(const float* a, const float* b, const float* window, const float* coef, const float* g_loss, float* g_a, int B,
@@ -1154,6 +1161,23 @@ int ctvae_grad_accumulate(float* acc, float* grads, long n, int mode, void* stre
 
 int ctvae_adam_flags_window(int* window, int* active, int nb, int mode, void* stream) {
   return launch_adam_flags_window(window, active, nb, mode, (hipStream_t)stream);
+}
+
+size_t ctvae_grad_segment_chunk_floats(void) { return grad_segment_chunk_floats(); }
+
+int ctvae_grad_segment_stats(const float* grads, long n, float scale, float norm_type, const long* segments, int nseg,
+                             const int* chunk_seg, const long* chunk_first, const int* seg_chunk_begin, int nchunks,
+                             double* part_sum, float* part_f, int* part_bad, double* out_sum, float* out_range, int* out_bad,
+                             int* out_hist, const int* flags_in, int* flags_out, int nflags, void* stream) {
+  return launch_grad_segment_stats(grads, n, scale, norm_type, segments, nseg, chunk_seg, chunk_first, seg_chunk_begin, nchunks,
+                                   part_sum, part_f, part_bad, out_sum, out_range, out_bad, out_hist, flags_in, flags_out, nflags,
+                                   (hipStream_t)stream);
+}
+
+int ctvae_grad_segment_hist(const float* grads, long n, float scale, const long* segments, int nseg, const int* chunk_seg,
+                            const long* chunk_first, int nchunks, const float* out_range, int* out_hist, void* stream) {
+  return launch_grad_segment_hist(grads, n, scale, segments, nseg, chunk_seg, chunk_first, nchunks, out_range, out_hist,
+                                  (hipStream_t)stream);
 }
 
 }  // extern "C"

@@ -50,6 +50,17 @@ and ``Graphs/mask_<name>_Epoch_<e>.png`` -- the mean mask of every action that h
 JSONL log.  Validation is eager, the captured training steps never see the observer, and it draws nothing: the run's
 trajectory is the same with and without it.  With several ranks the pictures and numbers are rank 0's own validation rows; the
 graphs are not reduced across ranks.
+
+``track_grad_norm`` (Lightning's Trainer flag: a norm type > 0 or 'inf'; None / -1 off) and ``watch_gradients`` with
+``watch_log_freq`` (the reference's ``wb_logger.watch(model, log_freq=500)``, run.py:55; off by default): gradient tracking by
+``optim.GradientTracker``, which ``track_gradients()`` drives eagerly right behind the optimizer step of a batch that ends a
+window -- never inside a captured graph, and only on tracking steps: the norm record joins ``log_file`` where the training
+scalars are logged (``global_step % log_every == 0``), the histogram record goes to ``grad_log_file`` every ``watch_log_freq``
+optimizer steps.  No Adam kernel writes the gradient, so at that point the optimizer's slice of the flat buffer holds exactly
+what was stepped, before any scale; with the step's ``grad_scale`` 1 / (world * k) the tracker sees the averaged pre-clip
+gradient, where Lightning's ``_track_grad_norm`` sits.  Rank 0 measures and writes (three launches, one device-to-host copy);
+the other ranks build no tracker.  The run ends bit for bit as it does without tracking; without both keys there is no tracker,
+no launch and no key.
 """
 import contextlib
 import json
@@ -63,7 +74,8 @@ from . import imagegrid
 from . import kernels as K
 from .ddp import GradBucketAllReduce
 from .metrics import _eval_mode as eval_mode
-from .optim import ExponentialLR, FlatAdam, absent_grad_setting, accumulate_setting, clip_settings, with_window_ends
+from .optim import (ExponentialLR, FlatAdam, GradientTracker, absent_grad_setting, accumulate_setting, clip_settings,
+                    track_grad_norm_setting, watch_settings, with_window_ends)
 
 
 def _graph_key(real_img, kwargs):
@@ -161,6 +173,7 @@ class _GraphedTrainStep:
         elif exp.ddp is not None:
             exp.ddp_step(self.pattern)
         if ends_window:
+            exp.track_gradients()          # eager, behind the replay: the flat buffer holds the gradient that was just stepped
             exp.global_step += 1
         return losses
 
@@ -191,7 +204,8 @@ class VAEXperiment:
 
     def __init__(self, vae_model, params: dict, ddp: GradBucketAllReduce = None, log_every: int = 50, log_file=None,
                  gradient_clip_val=None, gradient_clip_algorithm=None, val_metric=None, val_sampling: bool = False,
-                 sample_dir=None, run_name=None, val_graphs: bool = False, accumulate_grad_batches=None):
+                 sample_dir=None, run_name=None, val_graphs: bool = False, accumulate_grad_batches=None, track_grad_norm=None,
+                 watch_gradients: bool = False, watch_log_freq=None, grad_log_file=None):
         self.accumulate = accumulate_setting(accumulate_grad_batches)
         self._log_train = True      # training_step logs; fit() clears it for micro-batches that do not end their window
         self.val_metric = val_metric
@@ -224,6 +238,10 @@ class VAEXperiment:
         if ddp is not None and self.accumulate > 1:
             ddp.accumulate = self.accumulate      # (the exchange refuses ranged, SplitBackward-style calls from now on)
         self._graphed = {}          # (shape, dtype) -> _GraphedTrainStep
+        # gradient tracking (optim.GradientTracker): validated on every rank, built on rank 0 only -- the others launch nothing
+        self.grad_log_file = grad_log_file
+        self.last_grad_norms = self.last_grad_hists = None      # the records of the last tracking step (also without log files)
+        self.grad_tracker = self._build_tracker(track_grad_norm, watch_gradients, watch_log_freq)
 
     def forward(self, input, **kwargs):
         return self.model(input, **kwargs)
@@ -457,7 +475,43 @@ class VAEXperiment:
             self.ddp_step()
         else:
             self.optimizer.step()
+        self.track_gradients()
         self.global_step += 1
+
+    # -- gradient tracking (trainer_params.track_grad_norm, exp_params.watch_gradients; optim.GradientTracker) -----
+    def _build_tracker(self, track_grad_norm, watch_gradients, watch_log_freq):
+        """The tracker of this run, or None: the settings are validated on every rank, the tracker (its tables and output
+        buffers) is built on rank 0 only and only when a key is set -- the other ranks launch nothing."""
+        norm_type = track_grad_norm_setting(track_grad_norm)
+        watch, freq = watch_settings(watch_gradients, watch_log_freq)
+        if (norm_type is None and not watch) or not self._rank0():
+            return None
+        return GradientTracker(self.optimizer, norm_type, watch, freq)
+
+    def track_gradients(self):
+        """Called eagerly right behind an optimizer step, ``global_step`` still naming the step that ran; never inside a capture.
+        On a step where a record is due (norms: where the training scalars are logged; histograms: every ``watch_log_freq``
+        steps) rank 0 measures the stepped gradient -- the optimizer's slice of the flat buffer times the step's ``grad_scale``
+        1 / (world * k) -- and writes ``{"grad_<p>_norm/model.<name>": ..., "grad_<p>_norm_total": ..., "lr-Adam": lr, "step": s}``
+        to the metrics log and ``{"step": s, "gradients/<name>": {"min", "max", "counts", "nonfinite"}, ...}`` to the gradient
+        log.  On every other step, and without a tracker, nothing is launched or allocated."""
+        tr = self.grad_tracker
+        if tr is None:
+            return
+        scale = (self.ddp.grad_scale if self.ddp is not None else 1.0) / self.accumulate
+        norms, hists = tr.record(self.global_step, self.log_every, scale)
+        if norms is not None:
+            norms = {**norms, "lr-Adam": float(self.optimizer.lr), "step": self.global_step}   # (the rate itself, unrounded)
+            self.last_grad_norms = norms
+            if self.log_file is not None:
+                self.log_file.write(json.dumps(norms) + "\n")
+                self.log_file.flush()
+        if hists is not None:
+            hists = {"step": self.global_step, **hists}
+            self.last_grad_hists = hists
+            if self.grad_log_file is not None:
+                self.grad_log_file.write(json.dumps(hists) + "\n")
+                self.grad_log_file.flush()
 
     def fit(self, train_batches, val_batches=None, max_epochs=1, on_epoch_end=None, start_epoch=0, test_batches=None):
         """train_batches / val_batches / test_batches: callables returning an iterable of batches for one epoch.  start_epoch:
@@ -504,7 +558,9 @@ class VAEXperiment:
                         self.optimizer_step()
                     else:
                         self.window_step(ends)
-                        self.global_step += int(ends)
+                        if ends:
+                            self.track_gradients()
+                            self.global_step += 1
                 n += batch[0].size(0)
             if self.scheduler is not None:
                 self.scheduler.step()                      # Lightning steps ExponentialLR once per epoch

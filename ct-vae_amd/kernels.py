@@ -2610,3 +2610,124 @@ def adam_flags_window(window, table, mode):
     if window.numel() != table.nb or window.dtype != torch.int32:
         raise ValueError("adam_flags_window: window is one int32 word per block of the table")
     native.call("ctvae_adam_flags_window", window.data_ptr(), table.active.data_ptr(), table.nb, GRAD_ACCUM_MODES[mode])
+
+
+# ---------------------------------------------------------------------------------------------------
+# gradient tracking: per-parameter norms and histograms from the flat gradient buffer (csrc/gradstat.hip)
+# ---------------------------------------------------------------------------------------------------
+GRAD_HIST_BINS = 64
+_GUARD_WORD = 0x5A5A5A5A
+
+
+def _guarded(sizes, guard, device):
+    """One int32 buffer holding regions of ``sizes`` words, each between ``guard`` words of _GUARD_WORD (the first region starts
+    on an 8-byte boundary); returns the buffer and the regions' (lo, hi)."""
+    guard = (int(guard) + 1) // 2 * 2
+    spans, cur = [], guard
+    for n in sizes:
+        spans.append((cur, cur + n))
+        cur += n + guard
+    raw = torch.full((max(cur, 1),), _GUARD_WORD, dtype=torch.int32, device=device)
+    for lo, hi in spans:
+        raw[lo:hi] = 0
+    return raw, spans
+
+
+def _guards_intact(raw, spans):
+    keep = torch.ones(raw.numel(), dtype=torch.bool)
+    for lo, hi in spans:
+        keep[lo:hi] = False
+    return bool((raw.cpu()[keep] == _GUARD_WORD).all())
+
+
+class GradSegmentTable:
+    """Device side of the gradient-tracking kernels (ctvae_grad_segment_stats / _hist), everything allocated once: the segment
+    descriptors ``segments`` = [(base, rows, period, col_lo, width)] inside a gradient range of ``n`` floats (the elements
+    base + r * period + col_lo + c; FlatParamMixin.grad_segments, offsets relative to the range), the chunk list made from them
+    (``chunk_seg``, ``chunk_first``, ``seg_chunk_begin``: every segment's rows * width elements in pieces of
+    ctvae_grad_segment_chunk_floats()), the per-chunk partials and the outputs.  The outputs are regions of ONE int32 buffer,
+    ``raw``, so that ``fetch()`` is one device-to-host copy: ``out_sum`` float64 [nseg, 2] (sum |v|^p, max |v|), ``out_range``
+    float32 [nseg, 2] (finite min, max), ``out_bad`` int32 [nseg] (non-finite count), ``out_hist`` int32 [nseg, 64] and
+    ``out_flags`` int32 [nflags] (the caller's block flags, copied along).  guard: words of a fixed pattern around every region of
+    the outputs and the partials (``guards_intact()``).  On the CPU the table can be built and inspected; the launches cannot run
+    there."""
+
+    def __init__(self, segments, n, device, nflags=0, guard=0):
+        segs = [tuple(int(v) for v in s) for s in segments]
+        if not segs or n >= 2 ** 40 or nflags < 0:
+            raise ValueError("segment table: needs at least one segment")
+        spans = []
+        for base, rows, period, col_lo, width in segs:
+            first, end = base + col_lo, base + (rows - 1) * period + col_lo + width
+            if min(base, col_lo) < 0 or rows < 1 or width < 1 or (rows > 1 and col_lo + width > period) or end > n:
+                raise ValueError(f"segment table: segment {(base, rows, period, col_lo, width)} is malformed or leaves the {n} floats")
+            spans.append((first, end, base, rows, period, col_lo, width))
+        spans.sort()
+        for a, b in zip(spans, spans[1:]):
+            if a[1] > b[0] and not (a[2:5] == b[2:5] and a[5] + a[6] <= b[5]):
+                raise ValueError(f"segment table: segments {a[2:]} and {b[2:]} overlap")
+        chunk = int(native.load().ctvae_grad_segment_chunk_floats())
+        chunk_seg, chunk_first, begin = [], [], [0]
+        for s, (_, rows, _, _, width) in enumerate(segs):
+            for first in range(0, rows * width, chunk):
+                chunk_seg.append(s)
+                chunk_first.append(first)
+            begin.append(len(chunk_seg))
+        dev = torch.device(device)
+        self.nseg, self.n, self.nflags, self.nchunks, self.chunk = len(segs), int(n), int(nflags), len(chunk_seg), chunk
+        self.segments = torch.tensor(segs, dtype=torch.int64, device=dev)
+        self.chunk_seg = torch.tensor(chunk_seg, dtype=torch.int32, device=dev)
+        self.chunk_first = torch.tensor(chunk_first, dtype=torch.int64, device=dev)
+        self.seg_chunk_begin = torch.tensor(begin, dtype=torch.int32, device=dev)
+        ns, nc = self.nseg, self.nchunks
+        self.raw, self._spans = _guarded([4 * ns, 2 * ns, ns, GRAD_HIST_BINS * ns, self.nflags], guard, dev)
+        self.ws, self._ws_spans = _guarded([2 * nc, 3 * nc, nc], guard, dev)
+        self.out_sum, self.out_range, self.out_bad, self.out_hist, self.out_flags = self._views(self.raw)
+        (a, b), (c, d), (e, f) = self._ws_spans
+        self.part_sum, self.part_f, self.part_bad = self.ws[a:b].view(torch.float64), self.ws[c:d].view(torch.float32), self.ws[e:f]
+
+    def _views(self, raw):
+        (a, b), (c, d), (e, f), (g, h), (i, j) = self._spans
+        return (raw[a:b].view(torch.float64).view(self.nseg, 2), raw[c:d].view(torch.float32).view(self.nseg, 2), raw[e:f],
+                raw[g:h].view(self.nseg, GRAD_HIST_BINS), raw[i:j])
+
+    def fetch(self):
+        """The outputs on the host, by ONE device-to-host copy: (sum [nseg, 2] float64, range [nseg, 2] float32, bad [nseg],
+        hist [nseg, 64], flags [nflags])."""
+        return self._views(self.raw.cpu())
+
+    def guards_intact(self) -> bool:
+        return _guards_intact(self.raw, self._spans) and _guards_intact(self.ws, self._ws_spans)
+
+
+def _grad_segment_args(table, grads):
+    _req_cuda(grads, table.raw)
+    if grads.dtype != torch.float32 or grads.dim() != 1 or not grads.is_contiguous() or grads.numel() != table.n:
+        raise ValueError(f"gradient tracking: grads is the contiguous fp32 range of {table.n} floats the table was built for")
+
+
+def grad_segment_stats(table, grads, scale=1.0, norm_type=2.0, flags=None):
+    """ctvae_grad_segment_stats: for every segment of ``table`` over v = fl32(grads * scale): sum |v|^norm_type in double and
+    max |v| (``out_sum``), finite min / max (``out_range``), the non-finite count (``out_bad``); zeroes ``out_hist``.  Two launches.
+    flags: int32 [table.nflags] device words copied into ``out_flags`` by the second launch.  norm_type travels as fp32."""
+    _grad_segment_args(table, grads)
+    norm_type = float(norm_type)
+    if not norm_type > 0:
+        raise ValueError(f"gradient tracking: norm_type {norm_type!r} must be > 0 (inf: the largest magnitude)")
+    if (flags is None) != (table.nflags == 0) or (flags is not None and (flags.dtype != torch.int32 or flags.numel() != table.nflags
+                                                                         or not flags.is_cuda or not flags.is_contiguous())):
+        raise ValueError(f"gradient tracking: flags is {table.nflags} contiguous int32 device words (None for 0)")
+    native.call("ctvae_grad_segment_stats", grads.data_ptr(), table.n, float(scale), norm_type, table.segments.data_ptr(),
+                table.nseg, table.chunk_seg.data_ptr(), table.chunk_first.data_ptr(), table.seg_chunk_begin.data_ptr(),
+                table.nchunks, table.part_sum.data_ptr(), table.part_f.data_ptr(), table.part_bad.data_ptr(),
+                table.out_sum.data_ptr(), table.out_range.data_ptr(), table.out_bad.data_ptr(), table.out_hist.data_ptr(),
+                native.ptr(flags), table.out_flags.data_ptr() if table.nflags else None, table.nflags)
+
+
+def grad_segment_hist(table, grads, scale=1.0):
+    """ctvae_grad_segment_hist, behind grad_segment_stats with the same ``grads`` and ``scale``: the finite values of every
+    segment into the 64 bins between its finished min and max (torch.histc's rule on the CPU, in fp32).  One launch."""
+    _grad_segment_args(table, grads)
+    native.call("ctvae_grad_segment_hist", grads.data_ptr(), table.n, float(scale), table.segments.data_ptr(), table.nseg,
+                table.chunk_seg.data_ptr(), table.chunk_first.data_ptr(), table.nchunks, table.out_range.data_ptr(),
+                table.out_hist.data_ptr())

@@ -124,6 +124,21 @@ class PackedEmbedding(nn.Module):
         return [(self.K * self.D, [(self.weight, 0, (self.K, self.D), (self.D, 1))])]
 
 
+def _segment_shape(size, stride):
+    """(rows, period, width) of a strided view's element set: ``width`` = the elements its densely packed dimensions cover
+    (strides 1, s0, s0 * s1, ... in some order of the dimensions), repeated ``rows`` times at a distance of ``period`` by the one
+    dimension that may remain.  A dense view is one row."""
+    dims = sorted((st, sz) for sz, st in zip(size, stride) if sz > 1)
+    width = 1
+    while dims and dims[0][0] == width:
+        width *= dims.pop(0)[1]
+    if not dims:
+        return 1, width, width
+    if len(dims) > 1 or dims[0][0] < width:
+        raise ValueError(f"view of size {tuple(size)} and stride {tuple(stride)} is not rows of one dense run")
+    return dims[0][1], dims[0][0], width
+
+
 class _GradBlock:
     """One storage block of the flat gradient buffer, [lo, hi) floats.  ``fresh``: zero_grad(lazy=True) declared the block zero
     without writing it -- the first kernel that writes the block's gradient overwrites instead of accumulating
@@ -262,6 +277,31 @@ class FlatParamMixin:
             elif views:
                 out.append((off, off + n, "kernel", views[0][0]._grad_block, None))
             off += n
+        return out
+
+    def grad_segments(self):
+        """Where every named parameter's gradient lies in the flat gradient buffer, for the gradient-tracking kernels
+        (kernels.GradSegmentTable): [(name, base, rows, period, col_lo, width)] in buffer order, names as ``named_parameters()``
+        gives them, the elements being base + r * period + col_lo + c for r < rows, c < width.  Derived from the views of
+        ``_collect_blocks``: a view that covers one dense range (a conv weight in its packed order, a PackedLinear's weight
+        without its padding rows, any contiguous parameter) is one row; the heads of a PackedLinearGroup are column ranges of
+        the rows of their block.  Every named parameter appears once, the segments are pairwise disjoint, and alignment gaps and
+        padding rows belong to none."""
+        self.flat_params                                   # (flattens on first use)
+        names = {id(p): n for n, p in self.named_parameters()}
+        out, off = [], 0
+        for n, views in self._collect_blocks():
+            if n < 0:
+                off = -(-off // -n) * -n
+                continue
+            for p, o, size, stride in views:
+                if id(p) in names:
+                    rows, period, width = _segment_shape(size, stride)
+                    col_lo = o % period if rows > 1 else 0
+                    out.append((names.pop(id(p)), off + o - col_lo, rows, period, col_lo, width))
+            off += n
+        if names:
+            raise RuntimeError(f"grad_segments: no storage view for {sorted(names.values())}")
         return out
 
     def torch_grad_present(self, p) -> bool:

@@ -120,6 +120,8 @@ SIGNATURES = {
     "ctvae_adam_step_blocks": [_fp, _fp, _fp, _fp, _fp, _l, _f, _i, _f, _fp, _fp, _fp, _fp, _fp, _fp, _i, _vp],
     "ctvae_grad_accumulate": [_fp, _fp, _l, _i, _vp],
     "ctvae_adam_flags_window": [_fp, _fp, _i, _i, _vp],
+    "ctvae_grad_segment_stats": [_fp, _l, _f, _f, _fp, _i, _fp, _fp, _fp, _i, _fp, _fp, _fp, _fp, _fp, _fp, _fp, _fp, _fp, _i, _vp],
+    "ctvae_grad_segment_hist": [_fp, _l, _f, _fp, _i, _fp, _fp, _i, _fp, _fp, _vp],
     "ctvae_mssim_forward": [_fp, _fp, _fp, _fp, _fp, _fp, _fp, _i, _i, _i, _i, _vp],
     "ctvae_mssim_backward": [_fp, _fp, _fp, _fp, _fp, _fp, _i, _i, _i, _i, _vp],
     "ctvae_defer_begin": [_fp, _sz],
@@ -143,6 +145,7 @@ _RESTYPES = {
     "ctvae_adam_state_floats": _c.c_size_t,
     "ctvae_grad_clip_workspace_floats": _c.c_size_t,
     "ctvae_grad_accumulate_pass_floats": _c.c_size_t,
+    "ctvae_grad_segment_chunk_floats": _c.c_size_t,
     "ctvae_mssim_part_floats": _c.c_size_t,
     "ctvae_glinear_wgrad_ws_bytes": _c.c_size_t,
     "ctvae_conv_input_transform_supported": _c.c_int,

@@ -300,6 +300,195 @@ class FlatAdam:
         self.state[:8].copy_(sd["state"][:8])      # (states saved before the ticket word existed have 8 entries)
 
 
+TRACK_NORM_KEY = "track_grad_norm"
+WATCH_KEY, WATCH_FREQ_KEY = "watch_gradients", "watch_log_freq"
+
+
+def track_grad_norm_setting(value):
+    """Validated ``track_grad_norm`` with Lightning 1.6.5's rule: None or -1 is off (returned as None); a number > 0, or
+    ``'inf'`` / ``inf``, is the norm type (returned as a float).  A bool, 0, any other negative number, NaN or any other string
+    raises a ValueError that names the key."""
+    if value is None:
+        return None
+    if isinstance(value, str):
+        if value != "inf":
+            raise ValueError(f"{TRACK_NORM_KEY} {value!r} is invalid: it must be a number > 0, 'inf' or -1 (off)")
+        return math.inf
+    if isinstance(value, bool) or not isinstance(value, (int, float)) or math.isnan(value):
+        raise ValueError(f"{TRACK_NORM_KEY} {value!r} is invalid: it must be a number > 0, 'inf' or -1 (off)")
+    if value == -1:
+        return None
+    if value <= 0:
+        raise ValueError(f"{TRACK_NORM_KEY} {value!r} is invalid: it must be a number > 0, 'inf' or -1 (off)")
+    return float(value)
+
+
+def watch_settings(watch, log_freq=None):
+    """Validated ``(watch_gradients, watch_log_freq)``: a bool (None: False) and an integer >= 1 (None: 500, wandb's
+    ``watch(log_freq=500)`` of the reference's run.py).  Anything else raises a ValueError that names the key."""
+    if watch is not None and not isinstance(watch, bool):
+        raise ValueError(f"{WATCH_KEY} {watch!r} is invalid: it must be true or false")
+    if log_freq is None:
+        log_freq = 500
+    if isinstance(log_freq, bool) or not isinstance(log_freq, int) or log_freq < 1:
+        raise ValueError(f"{WATCH_FREQ_KEY} {log_freq!r} is invalid: it must be an integer >= 1")
+    return bool(watch), int(log_freq)
+
+
+def grad_norm_key(norm_type) -> str:
+    """Lightning's key stem: ``grad_<float(p)>_norm`` (``grad_2.0_norm``, ``grad_inf_norm``)."""
+    return f"grad_{float(norm_type)}_norm"
+
+
+def histc_bins(values, lo, hi, bins=K.GRAD_HIST_BINS):
+    """The bin of every entry of the float32 numpy array ``values`` (finite, inside [lo, hi]) by the rule the histogram kernel
+    restates from ``torch.histc`` on the CPU, carried out in fp32: min((long)((v - lo) / (hi - lo) * bins), bins - 1), with
+    lo == hi widened to lo - 1, hi + 1 and a quotient that is not a number counted in bin 0.  The kernel's reference in the tests."""
+    import numpy as np
+    lo, hi = np.float32(lo), np.float32(hi)
+    if lo == hi:
+        lo, hi = np.float32(lo - np.float32(1)), np.float32(hi + np.float32(1))
+    with np.errstate(all="ignore"):
+        q = ((values.astype(np.float32) - lo) / np.float32(hi - lo) * np.float32(bins)).astype(np.float32)
+    out = np.zeros(q.shape, dtype=np.int64)
+    ok = q >= 0                                     # (NaN: False)
+    out[ok] = np.minimum(q[ok], np.float32(bins - 1)).astype(np.int64)
+    return out
+
+
+class GradientTracker:
+    """Per-parameter gradient norms (Lightning 1.6.5's ``track_grad_norm``) and 64-bin gradient histograms (wandb's
+    ``watch(log="gradients")``) of the gradient an optimizer step was handed, read from the flat gradient buffer by the HIP
+    kernels of csrc/gradstat.hip: two launches for the norms, a third for the histograms, ONE device-to-host copy.
+
+    What is measured.  ``record()`` is called eagerly behind the optimizer step of a batch that ends a window.  No Adam kernel
+    writes the gradient (``ctvae_adam_step``, ``_clipped`` and ``_blocks`` all take it as ``const float*``; the clip factor is
+    applied in registers), so by then the optimizer's slice of the flat buffer still holds exactly what was stepped, before any
+    scale: the batch's gradient, the DDP sum, or the window's sum.  With ``scale`` = the step's ``grad_scale`` (1 / (world * k))
+    the kernels see the averaged PRE-CLIP gradient -- where Lightning's ``_track_grad_norm`` sits: behind accumulation and the DDP
+    average, in front of the clip.  wandb hooks every micro-batch's local gradient instead; this records the gradient that is
+    stepped (a deliberate difference).
+
+    Which parameters.  The named parameters whose segment (``FlatParamMixin.grad_segments``) lies inside the optimizer's slice:
+    with ``update_parameters`` only that range is exchanged and stepped, so only it is tracked -- Lightning walks every module
+    parameter and would report the frozen ones too (as whatever their stale ``.grad`` holds).  In the two ``absent_grad`` skip modes
+    a parameter whose Adam block's ``active`` word was 0 in the step is left out of both records (Lightning: ``p.grad is None``);
+    the words travel in the same copy.  Under "zero" every parameter is reported.
+
+    Parity.  The norm record restates ``pytorch_lightning.utilities.grads.grad_norm`` of 1.6.5 (keys ``grad_<p>_norm/<name>``
+    with the LightningModule's ``model.`` prefix, ``grad_<p>_norm_total`` = the p-norm of the per-parameter norms, every value
+    rounded to 4 decimals) and the histogram record wandb's ``log_tensor_stats`` (finite values only, 64 bins between their min
+    and max); neither package is installed, so both parities are UNPINNED.  The norm type travels to the kernel as fp32 and the
+    root is taken with the same value.  NaN in a gradient gives a NaN norm, as ``torch.norm`` does."""
+
+    def __init__(self, optimizer, norm_type=None, watch=False, watch_log_freq=None):
+        self.opt = optimizer
+        self.norm_type = track_grad_norm_setting(norm_type)
+        self.watch, self.watch_log_freq = watch_settings(watch, watch_log_freq)
+        self.table = self.names = self.block_of = None
+        if not self.enabled:
+            return
+        model = optimizer.model
+        model.flat_params                                  # (flattens on first use: both buffers exist from here on)
+        grads = model._flat_grads[optimizer.slice]
+        start, n = int(optimizer.slice.start or 0), grads.numel()
+        names, segs = [], []
+        for name, base, rows, period, col_lo, width in model.grad_segments():
+            first, end = base + col_lo, base + (rows - 1) * period + col_lo + width
+            if start <= first and end <= start + n:
+                names.append(name)
+                segs.append((base - start, rows, period, col_lo, width))
+        if not segs:
+            raise ValueError("gradient tracking: no named parameter lies inside the optimizer's slice")
+        self.names = names
+        if optimizer.absent_grad != "zero":            # the Adam block that holds each segment's first element
+            self.block_of = []
+            for (base, _, _, col_lo, _) in segs:
+                first = base + col_lo
+                hit = [i for i, b in enumerate(optimizer.blocks) if b[0] <= first < b[1]]
+                if len(hit) != 1:
+                    raise RuntimeError(f"gradient tracking: offset {first} of the slice lies in {len(hit)} Adam blocks")
+                self.block_of.append(hit[0])
+        nflags = 0 if self.block_of is None else optimizer.table.nb
+        self.table = K.GradSegmentTable(segs, n, grads.device, nflags=nflags)
+
+    @property
+    def enabled(self) -> bool:
+        return self.norm_type is not None or self.watch
+
+    def due(self, step: int, log_every: int):
+        """(norms, histograms) wanted for optimizer step ``step`` (counted from 0): norms where the training scalars are logged,
+        histograms every ``watch_log_freq`` steps."""
+        return (self.norm_type is not None and step % log_every == 0, self.watch and step % self.watch_log_freq == 0)
+
+    def measure(self, scale: float, hist: bool):
+        """The launches and the one copy.  Returns (names, present, sum [nseg, 2], range [nseg, 2], bad [nseg], hist [nseg, 64])
+        on the host; present[i]: whether segment i's Adam block stepped (always True under absent_grad "zero")."""
+        opt = self.opt
+        g = opt.model._flat_grads[opt.slice]           # (not ``flat_grads``: behind the step the buffer is complete as it is)
+        p = self.norm_type if self.norm_type is not None else 2.0
+        K.grad_segment_stats(self.table, g, scale, p, opt.table.active if self.block_of is not None else None)
+        if hist:
+            K.grad_segment_hist(self.table, g, scale)
+        s, r, bad, h, flags = self.table.fetch()
+        if self.block_of is None:
+            present = [True] * len(self.names)
+        else:
+            fl = flags.tolist()
+            present = [fl[b] != 0 for b in self.block_of]
+        return self.names, present, s, r, bad, h
+
+    def norm_record(self, names, present, sums):
+        """Lightning's ``grad_norm`` dict from the kernels' sums: per-parameter norms, their p-norm as the total, 4 decimals."""
+        p = self.norm_type
+        stem = grad_norm_key(p)
+        p32 = p if math.isinf(p) else float(torch.tensor(p, dtype=torch.float32))
+        norms = []
+        rec = {}
+        for i, name in enumerate(names):
+            if not present[i]:
+                continue
+            total, amax = float(sums[i, 0]), float(sums[i, 1])
+            v = amax if math.isinf(p) else (math.sqrt(total) if p32 == 2.0 else (total if p32 == 1.0 else total ** (1.0 / p32)))
+            norms.append(v)
+            rec[f"{stem}/model.{name}"] = round(v, 4)
+        if norms:
+            if any(math.isnan(v) for v in norms):
+                tot = math.nan
+            elif math.isinf(p):
+                tot = max(norms)
+            elif any(math.isinf(v) for v in norms):
+                tot = math.inf
+            elif p32 == 2.0:
+                tot = math.sqrt(math.fsum(v * v for v in norms))
+            else:
+                tot = math.fsum(v ** p32 for v in norms) ** (1.0 / p32)
+            rec[f"{stem}_total"] = round(tot, 4)
+        return rec
+
+    @staticmethod
+    def hist_record(names, present, rng, bad, hist):
+        rec = {}
+        for i, name in enumerate(names):
+            if not present[i]:
+                continue
+            lo, hi = float(rng[i, 0]), float(rng[i, 1])
+            none = not lo <= hi                            # +inf, -inf: the segment holds no finite value
+            rec[f"gradients/{name}"] = {"min": None if none else lo, "max": None if none else hi,
+                                        "counts": [int(c) for c in hist[i].tolist()], "nonfinite": int(bad[i])}
+        return rec
+
+    def record(self, step: int, log_every: int, scale: float):
+        """What is due at optimizer step ``step``: (norm record or None, histogram record or None), without the ``step`` and
+        ``lr-Adam`` entries the caller adds.  Launches, copies and allocates nothing when nothing is due."""
+        want_norm, want_hist = self.due(step, log_every) if self.enabled else (False, False)
+        if not (want_norm or want_hist):
+            return None, None
+        names, present, sums, rng, bad, hist = self.measure(scale, want_hist)
+        return (self.norm_record(names, present, sums) if want_norm else None,
+                self.hist_record(names, present, rng, bad, hist) if want_hist else None)
+
+
 class ExponentialLR:
     """lr_epoch = lr0 * gamma**epoch (torch.optim.lr_scheduler.ExponentialLR), stepped once per epoch."""
 

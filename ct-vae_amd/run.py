@@ -19,6 +19,14 @@ and ``Samples/`` of the run's log directory, named after ``logging_params.name``
 ``exp_params.val_graphs: true`` (CT-MCQ-VAE only) writes the mean learned adjacency per action and the mean intervention mask
 per action after every validation epoch into ``Graphs/`` of the log directory and adds ``val_graph_edges_<group>`` to the epoch
 records (experiment.py: ``val_graphs``); with several ranks they show rank 0's own validation rows.
+``trainer_params.track_grad_norm`` (Lightning's flag: a number > 0 or 'inf' is the norm type, -1 or absent is off; a bool, 0 or
+anything else is refused by name) adds one line ``{"grad_<p>_norm/model.<name>": ..., "grad_<p>_norm_total": ..., "lr-Adam": lr,
+"step": s}`` to ``metrics_rank0.jsonl`` on every step whose training scalars are logged (the reference's ``LearningRateMonitor``
+rides along as ``lr-Adam``).  ``exp_params.watch_gradients: true`` (the reference's run.py:55 hard-wires
+``wb_logger.watch(model, log_freq=500)``; here it defaults to false) with ``exp_params.watch_log_freq`` (an integer >= 1, default
+500) writes one line of 64-bin per-parameter gradient histograms to ``gradients_rank0.jsonl`` every ``watch_log_freq`` optimizer
+steps.  Both read the gradient that is stepped, from the flat buffer, by HIP kernels (optim.py: ``GradientTracker``); without
+the keys no file, no key and no launch is added.
 """
 import argparse
 import json
@@ -32,7 +40,7 @@ from . import filler
 from .ddp import GradBucketAllReduce
 from .experiment import VAEXperiment
 from .models import vae_models
-from .optim import accumulate_setting
+from .optim import accumulate_setting, track_grad_norm_setting, watch_settings
 
 
 class SyntheticData:
@@ -177,6 +185,24 @@ def trainer_accumulate(trainer_params) -> int:
         raise SystemExit(f"trainer_params.{e}")
 
 
+def trainer_track_grad_norm(trainer_params):
+    """``trainer_params.track_grad_norm`` as VAEXperiment's norm type (None: off); a refused value is a SystemExit that names
+    the key."""
+    try:
+        return track_grad_norm_setting(trainer_params.get('track_grad_norm'))
+    except ValueError as e:
+        raise SystemExit(f"trainer_params.{e}")
+
+
+def exp_watch_gradients(exp_params):
+    """``exp_params.watch_gradients`` / ``watch_log_freq`` as ``(watch, log_freq)``; a refused value is a SystemExit that names
+    the key."""
+    try:
+        return watch_settings(exp_params.get('watch_gradients'), exp_params.get('watch_log_freq'))
+    except ValueError as e:
+        raise SystemExit(f"exp_params.{e}")
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser(description='MI355X runner for the ct-vae models')
     ap.add_argument('--config', '-c', dest="filename", metavar='FILE', default='configs/vae.yaml')
@@ -223,6 +249,9 @@ def main(argv=None):
     log_file = open(os.path.join(log_dir, f"metrics_rank{rank}.jsonl"), "a") if rank == 0 else None
     tp = config['trainer_params']
     accumulate = trainer_accumulate(tp)
+    track_norm = trainer_track_grad_norm(tp)
+    watch, watch_freq = exp_watch_gradients(config['exp_params'])
+    grad_log_file = open(os.path.join(log_dir, f"gradients_rank{rank}.jsonl"), "a") if rank == 0 and watch else None
     val_sampling = bool(config['exp_params'].get('val_sampling', False))
     if val_sampling and rank == 0:
         for d in VAEXperiment.SAMPLE_DIRS:
@@ -232,7 +261,8 @@ def main(argv=None):
     exp = VAEXperiment(model, config['exp_params'], ddp=ddp, log_file=log_file, gradient_clip_val=tp.get('gradient_clip_val'),
                        gradient_clip_algorithm=tp.get('gradient_clip_algorithm'), val_sampling=val_sampling, sample_dir=log_dir,
                        run_name=config['logging_params'].get('name', mp['name']), val_graphs=val_graphs,
-                       accumulate_grad_batches=accumulate)
+                       accumulate_grad_batches=accumulate, track_grad_norm=track_norm, watch_gradients=watch,
+                       watch_log_freq=watch_freq, grad_log_file=grad_log_file)
     if config['data_params'].get('hbm_images'):
         data = HbmData(config['data_params'], mp, dev, rank, world, seed)
     else:

@@ -712,6 +712,33 @@ size_t ctvae_grad_accumulate_pass_floats(void);
 int ctvae_grad_accumulate(float* acc, float* grads, long n, int mode, void* stream);
 int ctvae_adam_flags_window(int* window, int* active, int nb, int mode, void* stream);
 
+/* Gradient tracking: per-parameter norms and 64-bin histograms from the flat gradient buffer (Lightning's track_grad_norm, wandb's
+ * watch).  `grads` (n floats) is read only.  A segment is five 64-bit words (base, rows, period, col_lo, width) and names the
+ * elements base + r * period + col_lo + c, r < rows, c < width (a contiguous parameter: one row; the heads of a grouped Linear
+ * block: column ranges of its rows).  The caller cuts every segment's rows * width elements (row-major) into chunks of
+ * ctvae_grad_segment_chunk_floats() elements: chunk k covers the elements from chunk_first[k] on of segment chunk_seg[k], the
+ * chunks of segment s are seg_chunk_begin[s] .. seg_chunk_begin[s + 1] - 1 (nseg + 1 words, every segment has at least one).
+ * All tables are device memory.  The kernels work on v = fl32(grads * scale).
+ *   ctvae_grad_segment_stats  two launches.  One workgroup per chunk writes a partial (part_sum: nchunks doubles, part_f:
+ *       3 * nchunks floats, part_bad: nchunks words), one workgroup per segment merges them in index order:
+ *       out_sum[2 s] = sum |v|^norm_type over ALL elements, in double (norm_type > 0; 2 and 1 without pow; +inf: left 0),
+ *       out_sum[2 s + 1] = max |v| (NaN once an element is NaN), out_range[2 s], [2 s + 1] = min, max over the FINITE elements
+ *       (-0 orders below +0; +inf, -inf when there is none), out_bad[s] = the number of non-finite elements, out_hist[64 s ..]
+ *       = 0.  No floating-point atomics: the results depend on the values and the tables alone.  The nflags words of flags_in
+ *       (e.g. ctvae_adam_step_blocks' active words; may be NULL with nflags 0) are copied to flags_out.
+ *   ctvae_grad_segment_hist   one launch behind it: out_hist[64 s + b] += the number of finite elements of segment s in bin
+ *       b = min((long)((v - lo) / (hi - lo) * 64.0f), 63), in fp32 with a correctly rounded division -- torch.histc's rule on
+ *       the CPU -- where lo, hi = out_range[2 s], [2 s + 1], widened to lo - 1, hi + 1 when equal; a quotient that is not a
+ *       number counts in bin 0; a segment without a finite element keeps its zeros.
+ * Nothing but the part_* and out_* arrays and flags_out is written. */
+size_t ctvae_grad_segment_chunk_floats(void);
+int ctvae_grad_segment_stats(const float* grads, long n, float scale, float norm_type, const long* segments, int nseg,
+                             const int* chunk_seg, const long* chunk_first, const int* seg_chunk_begin, int nchunks,
+                             double* part_sum, float* part_f, int* part_bad, double* out_sum, float* out_range, int* out_bad,
+                             int* out_hist, const int* flags_in, int* flags_out, int nflags, void* stream);
+int ctvae_grad_segment_hist(const float* grads, long n, float scale, const long* segments, int nseg, const int* chunk_seg,
+                            const long* chunk_first, int nchunks, const float* out_range, int* out_hist, void* stream);
+
 /* Input side: the reference's per-sample pipeline ToTensor -> CenterCrop(crop) -> Resize(size)
  * (dataset.py:72-80; bilinear, align_corners=False, no antialias -- what transforms.Resize does to a tensor; images smaller
  * than the crop are zero-padded as torchvision's center_crop does) for a batch of rows of a uint8 dataset
