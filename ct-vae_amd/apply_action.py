@@ -10,7 +10,9 @@ the first action-mode batch of the test split (``run.py``'s own ``HbmData`` / ``
   applied action over that batch, and causal accuracy over the causal-mode batches of the test split, both by action
 
 Factor names: ``--factor-names a,b,c``, else ``data_params.hbm_factor_names`` (a list of length action_dim / 2), else
-``action<i>``.  Seeded with ``exp_params.manual_seed``.  Bad input ends with a SystemExit that says why.
+``action<i>``.  Seeded with ``exp_params.manual_seed``.  ``--ema`` loads the checkpoint's averaged weights (``ema_state_dict``, written
+under ``exp_params.ema_decay``) in place of ``state_dict``; a checkpoint without them is refused.  Bad input ends with a
+SystemExit that says why.
 """
 import argparse
 import json
@@ -32,6 +34,7 @@ def main(argv=None):
     ap.add_argument('--image-index', type=int, default=0, help="row of the first action-mode test batch")
     ap.add_argument('--out', default=None, help="default: <save_dir>/<name>/apply_action")
     ap.add_argument('--factor-names', default=None, help="comma-separated, action_dim / 2 of them")
+    ap.add_argument('--ema', action='store_true', help="load the checkpoint's averaged weights (ema_state_dict) in place of state_dict")
     args = ap.parse_args(argv)
     with open(args.filename) as f:
         config = yaml.safe_load(f)
@@ -59,6 +62,11 @@ def main(argv=None):
         _fail(f"checkpoint {ckpt_path} does not exist")
     if args.steps < 1:
         _fail(f"--steps must be at least 1, got {args.steps}")
+    ckpt = None
+    if args.ema:          # (asked for by name: a checkpoint without the average is refused before anything is built)
+        ckpt = torch.load(ckpt_path, map_location="cpu", weights_only=True)
+        if 'ema_state_dict' not in ckpt:
+            _fail(f"--ema: checkpoint {ckpt_path} holds no ema_state_dict (it was written without exp_params.ema_decay)")
     if not torch.cuda.is_available():
         _fail("ctvae_amd runs on MI355X GPUs only: the hot path has no CPU fallback")
 
@@ -68,8 +76,10 @@ def main(argv=None):
     seed = int(config.get('exp_params', {}).get('manual_seed', 0) or 0)
     torch.manual_seed(seed)
     model = cls(**mp).to(dev)
-    ckpt = torch.load(ckpt_path, map_location="cpu", weights_only=True)
-    model.load_state_dict({k[6:]: v for k, v in ckpt['state_dict'].items() if k.startswith("model.")}, strict=True)
+    if ckpt is None:
+        ckpt = torch.load(ckpt_path, map_location="cpu", weights_only=True)
+    weights = ckpt['ema_state_dict' if args.ema else 'state_dict']
+    model.load_state_dict({k[6:]: v for k, v in weights.items() if k.startswith("model.")}, strict=True)
     data = HbmData(dp, mp, dev, 0, 1, seed) if dp.get('hbm_images') else SyntheticData(dp, mp, dev, 0, 1, seed=seed)
 
     def mode_of(batch):

@@ -13,8 +13,9 @@ batches of the test split through it (``causalgraph.collect_graphs``) and writes
   edges, the node with the largest mean mask (``causalgraph.summarize``)
 
 All pictures map [0, 1] onto ``causalgraph.colormap()``, so they compare across actions and runs.  Factor names: ``--factor-names
-a,b,c``, else ``data_params.hbm_factor_names``, else ``action<i>``.  Seeded with ``exp_params.manual_seed``.  Bad input ends with
-a SystemExit that says why.
+a,b,c``, else ``data_params.hbm_factor_names``, else ``action<i>``.  Seeded with ``exp_params.manual_seed``.  ``--ema`` loads the
+checkpoint's averaged weights (``ema_state_dict``, written under ``exp_params.ema_decay``) in place of ``state_dict``; a checkpoint
+without them is refused.  Bad input ends with a SystemExit that says why.
 """
 import argparse
 import io
@@ -51,6 +52,7 @@ def main(argv=None):
     ap.add_argument('--checkpoint', default=None, help="default: trainer_params.resume_from_checkpoint")
     ap.add_argument('--out', default=None, help="default: <save_dir>/<name>/causal_graph")
     ap.add_argument('--factor-names', default=None, help="comma-separated, action_dim / 2 of them")
+    ap.add_argument('--ema', action='store_true', help="load the checkpoint's averaged weights (ema_state_dict) in place of state_dict")
     ap.add_argument('--threshold', type=float, default=0.5, help="an edge counts when its coefficient lies above it")
     ap.add_argument('--cell', type=int, default=4, help="pixels per matrix element (the mask sheet: four times as many)")
     args = ap.parse_args(argv)
@@ -82,6 +84,11 @@ def main(argv=None):
         _fail(f"--cell must be at least 1, got {args.cell}")
     if not args.threshold == args.threshold:
         _fail("--threshold is not a number")
+    ckpt = None
+    if args.ema:          # (asked for by name: a checkpoint without the average is refused before anything is built)
+        ckpt = torch.load(ckpt_path, map_location="cpu", weights_only=True)
+        if 'ema_state_dict' not in ckpt:
+            _fail(f"--ema: checkpoint {ckpt_path} holds no ema_state_dict (it was written without exp_params.ema_decay)")
     if not torch.cuda.is_available():
         _fail("ctvae_amd runs on MI355X GPUs only: the hot path has no CPU fallback")
 
@@ -91,8 +98,10 @@ def main(argv=None):
     seed = int(config.get('exp_params', {}).get('manual_seed', 0) or 0)
     torch.manual_seed(seed)
     model = cls(**mp).to(dev)
-    ckpt = torch.load(ckpt_path, map_location="cpu", weights_only=True)
-    model.load_state_dict({k[6:]: v for k, v in ckpt['state_dict'].items() if k.startswith("model.")}, strict=True)
+    if ckpt is None:
+        ckpt = torch.load(ckpt_path, map_location="cpu", weights_only=True)
+    weights = ckpt['ema_state_dict' if args.ema else 'state_dict']
+    model.load_state_dict({k[6:]: v for k, v in weights.items() if k.startswith("model.")}, strict=True)
     data = HbmData(dp, mp, dev, 0, 1, seed) if dp.get('hbm_images') else SyntheticData(dp, mp, dev, 0, 1, seed=seed)
 
     stats = causalgraph.collect_graphs(model, data.test(), seed=seed, threshold=args.threshold)

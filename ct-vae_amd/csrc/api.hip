@@ -137,6 +137,8 @@ int launch_adam_blocks(float* p, const float* g, float* m, float* v, float* stat
                        const int* active, int nb, hipStream_t st);
 size_t grad_accumulate_pass_floats();
 int launch_grad_accumulate(float* acc, float* g, long n, int mode, hipStream_t st);
+int launch_ema_update(float* ema, const float* p, long n, float one_minus_decay, hipStream_t st);
+int launch_buffer_swap(float* a, float* b, long n, hipStream_t st);
 int launch_adam_flags_window(int* window, int* active, int nb, int mode, hipStream_t st);
 size_t grad_segment_chunk_floats();
 int launch_grad_segment_stats(const float* g, long n, float scale, float p, const long* seg, int nseg, const int* chunk_seg,
@@ -1162,6 +1164,12 @@ int ctvae_grad_accumulate(float* acc, float* grads, long n, int mode, void* stre
 int ctvae_adam_flags_window(int* window, int* active, int nb, int mode, void* stream) {
   return launch_adam_flags_window(window, active, nb, mode, (hipStream_t)stream);
 }
+
+int ctvae_ema_update(float* ema, const float* p, long n, float one_minus_decay, void* stream) {
+  return launch_ema_update(ema, p, n, one_minus_decay, (hipStream_t)stream);
+}
+
+int ctvae_buffer_swap(float* a, float* b, long n, void* stream) { return launch_buffer_swap(a, b, n, (hipStream_t)stream); }
 
 size_t ctvae_grad_segment_chunk_floats(void) { return grad_segment_chunk_floats(); }
 

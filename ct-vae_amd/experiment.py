@@ -61,6 +61,19 @@ what was stepped, before any scale; with the step's ``grad_scale`` 1 / (world * 
 gradient, where Lightning's ``_track_grad_norm`` sits.  Rank 0 measures and writes (three launches, one device-to-host copy);
 the other ranks build no tracker.  The run ends bit for bit as it does without tracking; without both keys there is no tracker,
 no launch and no key.
+
+``exp_params.ema_decay`` (a float, 0 < d < 1; absent: off) with ``ema_warmup`` (default false) and ``ema_eval`` (default true): an
+exponential moving average of the weights the optimizer steps, kept by ``optim.WeightEMA`` on the optimizer's slice of the flat
+parameter buffer.  ``ema_update()`` runs once per optimizer step, eagerly, right behind it and next to ``track_gradients()`` --
+never inside a captured graph (the decay is a by-value kernel argument, which a captured launch would freeze), once per window
+under ``accumulate_grad_batches``, and on every rank without a collective: the stepped parameters are identical on all ranks, so
+the averages are too.  With ``ema_eval`` the validation part of ``fit()`` -- the validation steps, ``write_graphs``,
+``validation_metrics`` and ``sample_images`` -- runs with the averaged weights swapped into the flat buffer
+(``WeightEMA.swapped_in``): the epoch record's ``val_*`` values, and what run.py chooses by them, describe the averaged weights;
+BatchNorm running statistics and all random streams are the live ones, and the live weights come back bit for bit, so the run
+trains exactly as it does without the key.  ``state_dict()`` carries ``"ema": {decay, warmup, updates}``; the buffer itself
+travels as weights (``ema_model_state_dict`` / ``load_ema_model_state_dict``, the checkpoint's ``ema_state_dict``).  Without
+``ema_decay`` there is no buffer, no launch and no entry.
 """
 import contextlib
 import json
@@ -74,8 +87,8 @@ from . import imagegrid
 from . import kernels as K
 from .ddp import GradBucketAllReduce
 from .metrics import _eval_mode as eval_mode
-from .optim import (ExponentialLR, FlatAdam, GradientTracker, absent_grad_setting, accumulate_setting, clip_settings,
-                    track_grad_norm_setting, watch_settings, with_window_ends)
+from .optim import (ExponentialLR, FlatAdam, GradientTracker, WeightEMA, absent_grad_setting, accumulate_setting, clip_settings,
+                    ema_settings, track_grad_norm_setting, watch_settings, with_window_ends)
 
 
 def _graph_key(real_img, kwargs):
@@ -174,6 +187,7 @@ class _GraphedTrainStep:
             exp.ddp_step(self.pattern)
         if ends_window:
             exp.track_gradients()          # eager, behind the replay: the flat buffer holds the gradient that was just stepped
+            exp.ema_update()               # eager too: the decay is a by-value argument that a captured launch would freeze
             exp.global_step += 1
         return losses
 
@@ -242,6 +256,9 @@ class VAEXperiment:
         self.grad_log_file = grad_log_file
         self.last_grad_norms = self.last_grad_hists = None      # the records of the last tracking step (also without log files)
         self.grad_tracker = self._build_tracker(track_grad_norm, watch_gradients, watch_log_freq)
+        # weight average (optim.WeightEMA): on every rank -- the stepped parameters are the same everywhere, so are the averages
+        decay, warmup, self.ema_eval = ema_settings(params.get("ema_decay"), params.get("ema_warmup"), params.get("ema_eval"))
+        self.ema = WeightEMA(self.optimizer, decay, warmup) if decay is not None else None
 
     def forward(self, input, **kwargs):
         return self.model(input, **kwargs)
@@ -409,6 +426,8 @@ class VAEXperiment:
         rng = getattr(self.model, "_rng_state", None)
         if rng is not None:
             sd["model_rng"] = rng.detach().cpu()
+        if self.ema is not None:           # (the buffer itself travels as weights: the checkpoint's ema_state_dict, run.py)
+            sd["ema"] = {"decay": float(self.ema.decay), "warmup": bool(self.ema.warmup), "updates": int(self.ema.updates)}
         return sd
 
     def load_state_dict(self, sd):
@@ -431,6 +450,10 @@ class VAEXperiment:
             torch.cuda.set_rng_state(sd["device_rng"].cpu(), dev)
         if "model_rng" in sd:
             self.model._rng_state = sd["model_rng"].to(dev)
+        if self.ema is not None:           # (a run without the key ignores the entry; run.py refuses a checkpoint without it)
+            if "ema" not in sd:
+                raise RuntimeError("checkpoint holds no weight average (trainer['ema']), this run keeps one (exp_params.ema_decay)")
+            self.ema.load_state_dict(sd["ema"])
         K.bump_param_epoch()
 
     def ddp_step(self, pattern=None):
@@ -476,6 +499,7 @@ class VAEXperiment:
         else:
             self.optimizer.step()
         self.track_gradients()
+        self.ema_update()
         self.global_step += 1
 
     # -- gradient tracking (trainer_params.track_grad_norm, exp_params.watch_gradients; optim.GradientTracker) -----
@@ -512,6 +536,65 @@ class VAEXperiment:
             if self.grad_log_file is not None:
                 self.grad_log_file.write(json.dumps(hists) + "\n")
                 self.grad_log_file.flush()
+
+    # -- weight average (exp_params.ema_decay / ema_warmup / ema_eval; optim.WeightEMA) ------------------------------
+    def ema_update(self):
+        """Called eagerly right behind an optimizer step, next to ``track_gradients()`` and never inside a capture: one
+        ``ctvae_ema_update`` launch on every rank, no collective.  Nothing without ``ema_decay``."""
+        if self.ema is not None:
+            self.ema.update()
+
+    def ema_weights(self):
+        """A context inside which the model holds the averaged weights (``WeightEMA.swapped_in``); without a weight average it
+        does nothing."""
+        return self.ema.swapped_in() if self.ema is not None else contextlib.nullcontext()
+
+    def ema_model_state_dict(self):
+        """The model's ``state_dict()`` with the averaged weights in place of the live ones, on the host: a checkpoint's
+        ``ema_state_dict`` without its ``model.`` prefix.  Entries outside the optimizer's slice equal the live ones."""
+        with self.ema.swapped_in():
+            return {k: v.detach().cpu().contiguous() for k, v in self.model.state_dict().items()}
+
+    def load_ema_model_state_dict(self, sd, strict=True):
+        """Inverse of ``ema_model_state_dict()``: ``sd`` is read into the average's buffer through the model's own
+        ``load_state_dict`` while the average is swapped in; the live weights come back untouched."""
+        live = {k: v.detach().clone() for k, v in self.model.state_dict().items()}
+        with self.ema.swapped_in():
+            self.model.load_state_dict(sd, strict=strict)
+        self.model.load_state_dict(live)          # (what lies outside the slice -- BatchNorm statistics among it -- stays live)
+
+    def _validate(self, epoch, val_batches, test_batches):
+        """The validation part of one epoch of ``fit()``: the validation steps' means, ``write_graphs``, ``validation_metrics``
+        and ``sample_images``; returns what joins the epoch record."""
+        rec = {}
+        self.model.eval()
+        sums, cnt = {}, 0
+        stats = None
+        if self.val_graphs and self._rank0():
+            from . import causalgraph
+            ct = self.model.ct_layer
+            stats = causalgraph.GraphStats(ct.action_dim + 1, causalgraph.model_nodes(self.model),
+                                           next(self.model.parameters()).device)
+            ct.graph_observer = stats.observe
+        try:
+            for i, batch in enumerate(val_batches()):
+                r = self.validation_step(batch, i)
+                for k, v in r.items():
+                    if k != "step":
+                        sums[k] = sums.get(k, 0.0) + v
+                cnt += 1
+        finally:
+            if stats is not None:
+                self.model.ct_layer.graph_observer = None
+        rec.update({k: v / max(cnt, 1) for k, v in sums.items()})
+        if stats is not None:
+            rec.update(self.write_graphs(stats, epoch))
+        rec.update(self.validation_metrics(epoch))
+        if self.val_sampling and self.sample_dir is not None and test_batches is not None and self._rank0():
+            first = next(iter(test_batches()), None)
+            if first is not None:
+                self.sample_images(first, epoch)
+        return rec
 
     def fit(self, train_batches, val_batches=None, max_epochs=1, on_epoch_end=None, start_epoch=0, test_batches=None):
         """train_batches / val_batches / test_batches: callables returning an iterable of batches for one epoch.  start_epoch:
@@ -560,39 +643,16 @@ class VAEXperiment:
                         self.window_step(ends)
                         if ends:
                             self.track_gradients()
+                            self.ema_update()
                             self.global_step += 1
                 n += batch[0].size(0)
             if self.scheduler is not None:
                 self.scheduler.step()                      # Lightning steps ExponentialLR once per epoch
             rec = {"epoch": epoch, "train_images": n, "epoch_seconds": time.time() - t0}
             if val_batches is not None:
-                self.model.eval()
-                sums, cnt = {}, 0
-                stats = None
-                if self.val_graphs and self._rank0():
-                    from . import causalgraph
-                    ct = self.model.ct_layer
-                    stats = causalgraph.GraphStats(ct.action_dim + 1, causalgraph.model_nodes(self.model),
-                                                   next(self.model.parameters()).device)
-                    ct.graph_observer = stats.observe
-                try:
-                    for i, batch in enumerate(val_batches()):
-                        r = self.validation_step(batch, i)
-                        for k, v in r.items():
-                            if k != "step":
-                                sums[k] = sums.get(k, 0.0) + v
-                        cnt += 1
-                finally:
-                    if stats is not None:
-                        self.model.ct_layer.graph_observer = None
-                rec.update({k: v / max(cnt, 1) for k, v in sums.items()})
-                if stats is not None:
-                    rec.update(self.write_graphs(stats, epoch))
-                rec.update(self.validation_metrics(epoch))
-                if self.val_sampling and self.sample_dir is not None and test_batches is not None and self._rank0():
-                    first = next(iter(test_batches()), None)
-                    if first is not None:
-                        self.sample_images(first, epoch)
+                # ema_eval: everything validation computes -- losses, graphs, metrics, sample sheets -- sees the averaged weights
+                with self.ema_weights() if self.ema_eval else contextlib.nullcontext():
+                    rec.update(self._validate(epoch, val_batches, test_batches))
             history.append(rec)
             if on_epoch_end is not None:
                 on_epoch_end(epoch, rec)

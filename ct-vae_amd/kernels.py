@@ -2602,6 +2602,27 @@ def grad_accumulator_like(grads):
     return buf[shift:shift + n]
 
 
+def _same_fp32_vectors(what, a, b):
+    _req_cuda(a, b)
+    if a.numel() != b.numel() or a.dtype != torch.float32 or b.dtype != torch.float32 \
+            or not (a.is_contiguous() and b.is_contiguous()):
+        raise ValueError(f"{what}: both arguments are contiguous fp32 vectors of one length")
+
+
+def ema_update(ema, params, one_minus_decay):
+    """One step of a weight average (ctvae_ema_update): ema = fmaf(one_minus_decay, params - ema, ema) per element; ``params`` is
+    read only.  one_minus_decay: a float inside (0, 1), handed to the launch by value."""
+    _same_fp32_vectors("ema_update", ema, params)
+    native.call("ctvae_ema_update", ema.data_ptr(), params.data_ptr(), ema.numel(), float(one_minus_decay))
+
+
+def buffer_swap(a, b):
+    """Exchange the contents of two equally long fp32 vectors word for word (ctvae_buffer_swap).  The caller bumps the parameter
+    epoch when one of them holds parameters."""
+    _same_fp32_vectors("buffer_swap", a, b)
+    native.call("ctvae_buffer_swap", a.data_ptr(), b.data_ptr(), a.numel())
+
+
 def adam_flags_window(window, table, mode):
     """The block-activity words of one micro-batch (table.active, after adam_block_flags_local) against the window's
     (ctvae_adam_flags_window): "store" window = active, "add" window = max(window, active), "finish" active = max(window,

@@ -120,6 +120,8 @@ SIGNATURES = {
     "ctvae_adam_step_blocks": [_fp, _fp, _fp, _fp, _fp, _l, _f, _i, _f, _fp, _fp, _fp, _fp, _fp, _fp, _i, _vp],
     "ctvae_grad_accumulate": [_fp, _fp, _l, _i, _vp],
     "ctvae_adam_flags_window": [_fp, _fp, _i, _i, _vp],
+    "ctvae_ema_update": [_fp, _fp, _l, _f, _vp],
+    "ctvae_buffer_swap": [_fp, _fp, _l, _vp],
     "ctvae_grad_segment_stats": [_fp, _l, _f, _f, _fp, _i, _fp, _fp, _fp, _i, _fp, _fp, _fp, _fp, _fp, _fp, _fp, _fp, _fp, _i, _vp],
     "ctvae_grad_segment_hist": [_fp, _l, _f, _fp, _i, _fp, _fp, _i, _fp, _fp, _vp],
     "ctvae_mssim_forward": [_fp, _fp, _fp, _fp, _fp, _fp, _fp, _i, _i, _i, _i, _vp],

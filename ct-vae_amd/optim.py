@@ -55,8 +55,15 @@ micro-batch, by host pattern and device hit words as in a single step: every sta
 (``adam_block_flags_local``, which consumes the hit words) and merges them into the window's (``ctvae_adam_flags_window``); the
 step merges its own, reduces them across ranks if asked to, and only then does "skip_until_first" add the blocks that have
 stepped before.  ``accumulation_schedule`` / ``with_window_ends`` say which batches of an epoch end a window.
+
+Weight average (``exp_params.ema_decay``; ``WeightEMA`` beside ``FlatAdam``, ``ema_settings`` its validator): an exponential
+moving average of the optimizer's slice of the flat parameter buffer in a buffer of its own, one ``ctvae_ema_update`` launch per
+optimizer step and one ``ctvae_buffer_swap`` launch to exchange it with the live weights for evaluation (csrc/ema.hip).  The
+reference keeps no such average: what it computes is defined here.  Without the key nothing is allocated or launched.
 """
+import contextlib
 import math
+import struct
 
 import torch
 
@@ -298,6 +305,108 @@ class FlatAdam:
         self.exp_avg.copy_(sd["exp_avg"])
         self.exp_avg_sq.copy_(sd["exp_avg_sq"])
         self.state[:8].copy_(sd["state"][:8])      # (states saved before the ticket word existed have 8 entries)
+
+
+EMA_DECAY_KEY, EMA_WARMUP_KEY, EMA_EVAL_KEY = "ema_decay", "ema_warmup", "ema_eval"
+
+
+def _fp32(x: float) -> float:
+    """x rounded to the nearest fp32 value (what a ``float`` kernel argument receives)."""
+    return struct.unpack("f", struct.pack("f", x))[0]
+
+
+def ema_settings(decay, warmup=None, eval=None):
+    """Validated ``(ema_decay, ema_warmup, ema_eval)``.  ``decay`` None means off: (None, False, False), and then neither of the
+    other two may be set.  Otherwise ``decay`` is a float with 0 < d < 1 whose 1 - d is still below 1 in fp32 (the kernel's
+    argument); ``warmup`` (None: False) and ``eval`` (None: True) are real bools.  Anything else -- a bool, a string or an int as
+    the decay, a value outside the range, a number where a bool belongs -- raises a ValueError that names the key."""
+    for key, v in ((EMA_WARMUP_KEY, warmup), (EMA_EVAL_KEY, eval)):
+        if v is not None and not isinstance(v, bool):
+            raise ValueError(f"{key} {v!r} is invalid: it must be true or false")
+        if v is not None and decay is None:
+            raise ValueError(f"{key} is set without {EMA_DECAY_KEY}: there is no weight average to apply it to")
+    if decay is None:
+        return None, False, False
+    if isinstance(decay, bool) or not isinstance(decay, float) or not 0.0 < decay < 1.0 or not 0.0 < _fp32(1.0 - decay) < 1.0:
+        raise ValueError(f"{EMA_DECAY_KEY} {decay!r} is invalid: it must be a float with 0 < {EMA_DECAY_KEY} < 1")
+    return float(decay), bool(warmup), True if eval is None else eval
+
+
+def ema_decay_at(decay: float, warmup: bool, t: int) -> float:
+    """The decay of update ``t`` (counted from 1): ``decay``, or with warm-up min(decay, (1 + t) / (10 + t)) -- 2/11 at the
+    first update, so that a young average follows the weights instead of its starting point."""
+    return min(decay, (1.0 + t) / (10.0 + t)) if warmup else decay
+
+
+class WeightEMA:
+    """An exponential moving average of the weights an optimizer steps (``exp_params.ema_decay``), kept by HIP kernels of its
+    own on the flat buffer (csrc/ema.hip): ``update()`` is one ``ctvae_ema_update`` launch, ema += (1 - decay) * (p - ema), and
+    ``swap()`` one ``ctvae_buffer_swap`` launch that exchanges the average with the live weights -- captured steps hold the flat
+    buffer's addresses, so evaluating with the average means exchanging contents, not pointers.
+
+    What is averaged.  The optimizer's whole slice of ``model.flat_params``, element by element, in the buffer's own packed
+    order: alignment gaps and bank padding (constant zeros) are averaged along with the rest, which is harmless and keeps the
+    kernel free of tables.  Under ``adam_absent_grad`` "skip" / "skip_until_first" a block that did not step is still averaged:
+    its parameter did not move, so its average keeps approaching it (and stays on it once it is there: the kernel's arithmetic
+    form leaves ema == p exactly p).  BatchNorm running statistics are buffers, not parameters, and are not averaged.
+
+    The buffer sits at the slice's offset from a 16-byte boundary (``K.grad_accumulator_like``), so both kernels run their 16-byte
+    loop, and starts as a copy of the slice.  ``updates`` counts the launches on the host; the decay of update t is
+    ``decay_at(t)``, and 1 - decay is formed in double precision and rounded to fp32 once, as the launch's by-value argument."""
+
+    def __init__(self, optimizer, decay, warmup=False):
+        self.decay, self.warmup, _ = ema_settings(decay, bool(warmup), None)
+        if self.decay is None:
+            raise ValueError(f"{EMA_DECAY_KEY} is None: no weight average is wanted, build no WeightEMA")
+        self.opt = optimizer
+        live = self.live
+        self.buffer = K.grad_accumulator_like(live)
+        self.buffer.copy_(live)
+        self.updates = 0
+        self.swapped = False           # the average is in the flat buffer right now (between swap() and swap())
+
+    @property
+    def live(self):
+        """The optimizer's slice of the model's flat parameter buffer."""
+        return self.opt.model.flat_params[self.opt.slice]
+
+    def decay_at(self, t: int) -> float:
+        return ema_decay_at(self.decay, self.warmup, t)
+
+    def update(self):
+        if self.swapped:
+            raise RuntimeError("WeightEMA.update: the average is swapped in; the flat buffer does not hold the live weights")
+        K.ema_update(self.buffer, self.live, _fp32(1.0 - self.decay_at(self.updates + 1)))
+        self.updates += 1
+
+    def swap(self):
+        """Exchange the average with the live slice.  The parameter epoch moves: cached Winograd filters and whatever else is
+        keyed on it were made from the other values."""
+        K.buffer_swap(self.buffer, self.live)
+        self.swapped = not self.swapped
+        K.bump_param_epoch()
+
+    @contextlib.contextmanager
+    def swapped_in(self):
+        """The model computes with the averaged weights inside; the live ones come back on exit, also when the body raises."""
+        self.swap()
+        try:
+            yield self
+        finally:
+            self.swap()
+
+    def state_dict(self):
+        return {"decay": self.decay, "warmup": self.warmup, "updates": int(self.updates), "buffer": self.buffer}
+
+    def load_state_dict(self, sd):
+        if float(sd["decay"]) != self.decay or bool(sd["warmup"]) != self.warmup:
+            raise RuntimeError(f"weight average was kept under {EMA_DECAY_KEY}={sd['decay']!r}, {EMA_WARMUP_KEY}={sd['warmup']!r}, "
+                               f"this run uses {self.decay!r}, {self.warmup!r}")
+        if "buffer" in sd:
+            if sd["buffer"].numel() != self.buffer.numel():
+                raise RuntimeError("weight average covers another parameter range than this optimizer's slice")
+            self.buffer.copy_(sd["buffer"])
+        self.updates = int(sd["updates"])
 
 
 TRACK_NORM_KEY = "track_grad_norm"

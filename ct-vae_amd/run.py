@@ -27,6 +27,12 @@ rides along as ``lr-Adam``).  ``exp_params.watch_gradients: true`` (the referenc
 500) writes one line of 64-bin per-parameter gradient histograms to ``gradients_rank0.jsonl`` every ``watch_log_freq`` optimizer
 steps.  Both read the gradient that is stepped, from the flat buffer, by HIP kernels (optim.py: ``GradientTracker``); without
 the keys no file, no key and no launch is added.
+``exp_params.ema_decay`` (a float, 0 < d < 1) with ``ema_warmup`` (default false) and ``ema_eval`` (default true) keeps an
+exponential moving average of the optimized weights and, under ``ema_eval``, validates with it -- so the top-k choice on
+``val_Reconstruction_Loss`` is made on the averaged weights (experiment.py, optim.py: ``WeightEMA``).  ``state_dict`` stays the live
+weights; the checkpoint gains ``ema_state_dict`` (the same keys, the averaged weights) and ``trainer['ema']``.  A full resume under
+the key needs both, written under the same decay and warm-up; ``load_weights_only`` starts the average from the loaded weights; a
+run without the key ignores them.  A refused value is a SystemExit that names ``exp_params.<key>``.
 """
 import argparse
 import json
@@ -40,7 +46,7 @@ from . import filler
 from .ddp import GradBucketAllReduce
 from .experiment import VAEXperiment
 from .models import vae_models
-from .optim import accumulate_setting, track_grad_norm_setting, watch_settings
+from .optim import accumulate_setting, ema_settings, track_grad_norm_setting, watch_settings
 
 
 class SyntheticData:
@@ -203,6 +209,28 @@ def exp_watch_gradients(exp_params):
         raise SystemExit(f"exp_params.{e}")
 
 
+def exp_ema(exp_params):
+    """``exp_params.ema_decay`` / ``ema_warmup`` / ``ema_eval`` as ``(decay, warmup, eval)`` (decay None: off); a refused value is
+    a SystemExit that names the key."""
+    try:
+        return ema_settings(exp_params.get('ema_decay'), exp_params.get('ema_warmup'), exp_params.get('ema_eval'))
+    except ValueError as e:
+        raise SystemExit(f"exp_params.{e}")
+
+
+def check_ema_checkpoint(ckpt, path, decay, warmup):
+    """Full resume of a run that keeps a weight average: the checkpoint must hold the average (``ema_state_dict``) and its
+    settings (``trainer['ema']``), written under this run's decay and warm-up; otherwise a SystemExit names the key and the path."""
+    ema = ckpt.get("trainer", {}).get("ema")
+    if "ema_state_dict" not in ckpt or ema is None:
+        raise SystemExit(f"exp_params.ema_decay is set, but {path} holds no weight average (no 'ema_state_dict' / trainer['ema']): "
+                         "it was written by a run without the key; set trainer_params.load_weights_only to start the average "
+                         "from its weights")
+    if float(ema["decay"]) != decay or bool(ema["warmup"]) != warmup:
+        raise SystemExit(f"exp_params.ema_decay / ema_warmup are {decay!r} / {warmup!r}, but {path} kept its weight average under "
+                         f"{ema['decay']!r} / {ema['warmup']!r}")
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser(description='MI355X runner for the ct-vae models')
     ap.add_argument('--config', '-c', dest="filename", metavar='FILE', default='configs/vae.yaml')
@@ -211,8 +239,9 @@ def main(argv=None):
     args = ap.parse_args(argv)
     with open(args.filename) as f:
         config = yaml.safe_load(f)
+    ema_decay, ema_warmup, _ = exp_ema(config['exp_params'])
 
-    rank = int(os.environ.get("RANK", "0"))
+    rank =int(os.environ.get("RANK", "0"))
     world = int(os.environ.get("WORLD_SIZE", "1"))
     local = int(os.environ.get("LOCAL_RANK", "0"))
     gpus = config.get('trainer_params', {}).get('gpus', 1)
@@ -242,6 +271,8 @@ def main(argv=None):
     ckpt = None
     if ckpt_path:
         ckpt = torch.load(ckpt_path, map_location="cpu", weights_only=True)
+        if ema_decay is not None and not weights_only:
+            check_ema_checkpoint(ckpt, ckpt_path, ema_decay, ema_warmup)
         model.load_state_dict({k[6:]: v for k, v in ckpt['state_dict'].items() if k.startswith("model.")}, strict=not weights_only)
     ddp = GradBucketAllReduce(model) if world > 1 else None
     log_dir = os.path.join(config['logging_params'].get('save_dir', 'logs/'), config['logging_params'].get('name', mp['name']))
@@ -276,6 +307,8 @@ def main(argv=None):
             raise SystemExit(f"{ckpt_path} holds weights only (no 'trainer' entry: optimizer moments, scheduler, epoch); "
                              "set trainer_params.load_weights_only to start a new run from its weights")
         exp.load_state_dict(ckpt["trainer"])
+        if exp.ema is not None:                                       # the average's buffer travels as weights
+            exp.load_ema_model_state_dict({k[6:]: v for k, v in ckpt['ema_state_dict'].items() if k.startswith("model.")})
         start_epoch = int(ckpt["epoch"]) + 1
         if hasattr(data, "epoch"):
             data.epoch = start_epoch                                  # the shuffling order follows the epoch
@@ -287,6 +320,8 @@ def main(argv=None):
         print(json.dumps(rec), flush=True)
         state = {"state_dict": {"model." + k: v.detach().cpu().contiguous() for k, v in model.state_dict().items()},
                  "epoch": epoch, "global_step": exp.global_step, "trainer": exp.state_dict()}
+        if exp.ema is not None:                                       # the same keys, the averaged weights inside the slice
+            state["ema_state_dict"] = {"model." + k: v for k, v in exp.ema_model_state_dict().items()}
         torch.save(state, os.path.join(log_dir, "checkpoints", "last.ckpt"))
         score = rec.get("val_Reconstruction_Loss")
         if score is not None:                                         # ModelCheckpoint(save_top_k=2, monitor=val_Reconstruction_Loss)

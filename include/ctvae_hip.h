@@ -712,6 +712,20 @@ size_t ctvae_grad_accumulate_pass_floats(void);
 int ctvae_grad_accumulate(float* acc, float* grads, long n, int mode, void* stream);
 int ctvae_adam_flags_window(int* window, int* active, int nb, int mode, void* stream);
 
+/* Exponential moving average of the weights (exp_params.ema_decay), on the optimizer's slice of the flat parameter buffer.
+ *   ctvae_ema_update   ema = fmaf(one_minus_decay, p - ema, ema) per element, in this form only: where ema == p it stays p.  `p`
+ *                      is read only.  one_minus_decay is finite and inside (0, 1); it is passed by value, so it may change from
+ *                      launch to launch (a warm-up schedule).  One launch's error against the exact result is at most
+ *                      2^-22 * max(|ema|, |p|) per element.  A NaN or Inf in p reaches that element's average and no other.
+ *   ctvae_buffer_swap  exchanges the contents of a and b as raw 32-bit words (loads and stores only: NaN payloads and -0
+ *                      survive); swapping twice is the identity bit for bit.
+ * Either pointer may sit at any float; 16-byte accesses are used where both have the same offset from a 16-byte boundary
+ * (otherwise the range is walked float by float).  The two ranges must not overlap.  Nothing outside [0, n) is touched.  A null
+ * pointer, n <= 0, a pointer that is not 4-byte aligned, overlapping ranges or a refused one_minus_decay return the bad-argument
+ * code without a launch. */
+int ctvae_ema_update(float* ema, const float* p, long n, float one_minus_decay, void* stream);
+int ctvae_buffer_swap(float* a, float* b, long n, void* stream);
+
 /* Gradient tracking: per-parameter norms and 64-bin histograms from the flat gradient buffer (Lightning's track_grad_norm, wandb's
  * watch).  `grads` (n floats) is read only.  A segment is five 64-bit words (base, rows, period, col_lo, width) and names the
  * elements base + r * period + col_lo + c, r < rows, c < width (a contiguous parameter: one row; the heads of a grouped Linear
