@@ -139,6 +139,15 @@ size_t grad_accumulate_pass_floats();
 int launch_grad_accumulate(float* acc, float* g, long n, int mode, hipStream_t st);
 int launch_ema_update(float* ema, const float* p, long n, float one_minus_decay, hipStream_t st);
 int launch_buffer_swap(float* a, float* b, long n, hipStream_t st);
+size_t vq_usage_pass_indices();
+int launch_vq_usage(const long* inds, long* counts, long* invalid, int B, int C, int HW, int K, hipStream_t st);
+int launch_vq_pool_fill(const float* latents, float* pool, long P, int D, long R, hipStream_t st);
+int launch_vq_usage_pool_fill(const long* inds, long* counts, long* invalid, int B, int C, int HW, int K, const float* latents,
+                              float* pool, long P, int D, long R, hipStream_t st);
+int launch_vq_restart(const long* list, int n, const float* pool, int valid_rows, int D, const float* rows, float* codebooks,
+                      float* exp_avg, float* exp_avg_sq, int C, int K, int Dc, hipStream_t st);
+int launch_vq_restart_gather(const long* list, int n, const float* pool, int valid_rows, int D, int C, int Dc, float* rows,
+                             hipStream_t st);
 int launch_adam_flags_window(int* window, int* active, int nb, int mode, hipStream_t st);
 size_t grad_segment_chunk_floats();
 int launch_grad_segment_stats(const float* g, long n, float scale, float p, const long* seg, int nseg, const int* chunk_seg,
@@ -1170,6 +1179,31 @@ int ctvae_ema_update(float* ema, const float* p, long n, float one_minus_decay, 
 }
 
 int ctvae_buffer_swap(float* a, float* b, long n, void* stream) { return launch_buffer_swap(a, b, n, (hipStream_t)stream); }
+
+size_t ctvae_vq_usage_pass_indices(void) { return vq_usage_pass_indices(); }
+
+int ctvae_vq_usage(const long* inds, long* counts, long* invalid, int B, int C, int HW, int K, void* stream) {
+  return launch_vq_usage(inds, counts, invalid, B, C, HW, K, (hipStream_t)stream);
+}
+
+int ctvae_vq_pool_fill(const float* latents, float* pool, long P, int D, long R, void* stream) {
+  return launch_vq_pool_fill(latents, pool, P, D, R, (hipStream_t)stream);
+}
+
+int ctvae_vq_usage_pool_fill(const long* inds, long* counts, long* invalid, int B, int C, int HW, int K, const float* latents,
+                             float* pool, long P, int D, long R, void* stream) {
+  return launch_vq_usage_pool_fill(inds, counts, invalid, B, C, HW, K, latents, pool, P, D, R, (hipStream_t)stream);
+}
+
+int ctvae_vq_restart(const long* list, int n, const float* pool, int valid_rows, int D, const float* rows, float* codebooks,
+                     float* exp_avg, float* exp_avg_sq, int C, int K, int Dc, void* stream) {
+  return launch_vq_restart(list, n, pool, valid_rows, D, rows, codebooks, exp_avg, exp_avg_sq, C, K, Dc, (hipStream_t)stream);
+}
+
+int ctvae_vq_restart_gather(const long* list, int n, const float* pool, int valid_rows, int D, int C, int Dc, float* rows,
+                            void* stream) {
+  return launch_vq_restart_gather(list, n, pool, valid_rows, D, C, Dc, rows, (hipStream_t)stream);
+}
 
 size_t ctvae_grad_segment_chunk_floats(void) { return grad_segment_chunk_floats(); }
 

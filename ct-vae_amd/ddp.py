@@ -98,6 +98,18 @@ class GradBucketAllReduce:
         if self.active:
             dist.all_reduce(flags, op=dist.ReduceOp.MAX, group=self.pg)
 
+    def all_reduce_counts(self, counts):
+        """SUM all-reduce, in place, of the int64 codebook usage counts (``optim.CodebookUsage.restart``): a code is dead only
+        when no rank chose it often enough.  One small collective per restart, stream-ordered."""
+        if self.active:
+            dist.all_reduce(counts, op=dist.ReduceOp.SUM, group=self.pg)
+
+    def broadcast_rows(self, rows, src=0):
+        """Rank ``src``'s gathered restart rows to every rank, in place: the pools differ from rank to rank, the restarted codes
+        must not."""
+        if self.active:
+            dist.broadcast(rows, src, group=self.pg)
+
     def wait(self, works):
         for w in works:
             w.wait()

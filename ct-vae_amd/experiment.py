@@ -74,6 +74,21 @@ BatchNorm running statistics and all random streams are the live ones, and the l
 trains exactly as it does without the key.  ``state_dict()`` carries ``"ema": {decay, warmup, updates}``; the buffer itself
 travels as weights (``ema_model_state_dict`` / ``load_ema_model_state_dict``, the checkpoint's ``ema_state_dict``).  Without
 ``ema_decay`` there is no buffer, no launch and no entry.
+
+``exp_params.codebook_stats`` (a bool) and ``exp_params.codebook_restart_every`` (an integer N >= 1; with
+``codebook_restart_min_count``, default 1, and ``codebook_restart_pool``, default 1024): codebook usage of the models with a
+``vq_layer`` quantiser, by ``optim.CodebookUsage`` as the quantiser's ``usage_observer`` -- attached and detached with a
+``finally``, in the style of ``graph_observer``.  The validation counter (rank 0 only) observes the validation steps alone and
+adds ``val_codebook_perplexity_<i>`` / ``_usage_<i>`` / ``_dead_<i>`` and their means to the epoch record and the JSONL log;
+``sample_images``, ``validation_metrics``, rollouts and the tools run without an observer.  The training counter observes the
+training batches of ``fit()``: its launch is part of the forward, inside the captured body when the step is captured and
+identical in eager steps, once per micro-batch.  ``codebook_restart()`` runs eagerly behind the optimizer step that makes
+``global_step`` a multiple of N, next to ``track_gradients()`` / ``ema_update()`` and never captured (its docstring has the
+sequence); the weight average is not special-cased and goes on averaging towards a restarted row, and the per-block Adam
+counters of the skip modes are untouched.  ``state_dict()`` carries ``"codebook": {every, min_count, pool, counts, ordinal,
+restarted, valid_rows}``; a full resume restores it and refuses other ``every`` / ``min_count``.  Refused when the experiment is
+built: either key on a model without such a quantiser, and restarts when ``update_parameters`` leaves the codebooks outside the
+optimizer's slice.  Without the keys there is no buffer, no launch, no log key and no entry.
 """
 import contextlib
 import json
@@ -87,8 +102,9 @@ from . import imagegrid
 from . import kernels as K
 from .ddp import GradBucketAllReduce
 from .metrics import _eval_mode as eval_mode
-from .optim import (ExponentialLR, FlatAdam, GradientTracker, WeightEMA, absent_grad_setting, accumulate_setting, clip_settings,
-                    ema_settings, track_grad_norm_setting, watch_settings, with_window_ends)
+from .optim import (CodebookUsage, ExponentialLR, FlatAdam, GradientTracker, WeightEMA, absent_grad_setting, accumulate_setting,
+                    clip_settings, codebook_record, codebook_settings, ema_settings, track_grad_norm_setting, watch_settings,
+                    with_window_ends)
 
 
 def _graph_key(real_img, kwargs):
@@ -188,6 +204,7 @@ class _GraphedTrainStep:
         if ends_window:
             exp.track_gradients()          # eager, behind the replay: the flat buffer holds the gradient that was just stepped
             exp.ema_update()               # eager too: the decay is a by-value argument that a captured launch would freeze
+            exp.codebook_restart()         # eager too: the dead list is formed on the host
             exp.global_step += 1
         return losses
 
@@ -259,6 +276,7 @@ class VAEXperiment:
         # weight average (optim.WeightEMA): on every rank -- the stepped parameters are the same everywhere, so are the averages
         decay, warmup, self.ema_eval = ema_settings(params.get("ema_decay"), params.get("ema_warmup"), params.get("ema_eval"))
         self.ema = WeightEMA(self.optimizer, decay, warmup) if decay is not None else None
+        self._build_codebook_usage(params)
 
     def forward(self, input, **kwargs):
         return self.model(input, **kwargs)
@@ -428,6 +446,12 @@ class VAEXperiment:
             sd["model_rng"] = rng.detach().cpu()
         if self.ema is not None:           # (the buffer itself travels as weights: the checkpoint's ema_state_dict, run.py)
             sd["ema"] = {"decay": float(self.ema.decay), "warmup": bool(self.ema.warmup), "updates": int(self.ema.updates)}
+        if self.codebook is not None:      # (the pool does not travel: the next forward refills it before a restart can read it)
+            cb = self.codebook
+            sd["codebook"] = {"every": int(self.codebook_every), "min_count": int(self.codebook_min_count),
+                              "pool": int(cb.pool.size(0)), "counts": cb.read()[0].clone(), "ordinal": int(self.codebook_ordinal),
+                              "restarted": int(self.codebook_restarted),
+                              "valid_rows": -1 if cb.valid_rows is None else int(cb.valid_rows)}
         return sd
 
     def load_state_dict(self, sd):
@@ -454,6 +478,8 @@ class VAEXperiment:
             if "ema" not in sd:
                 raise RuntimeError("checkpoint holds no weight average (trainer['ema']), this run keeps one (exp_params.ema_decay)")
             self.ema.load_state_dict(sd["ema"])
+        if self.codebook is not None:      # (a run without the key ignores the entry)
+            self._load_codebook_state(sd.get("codebook"))
         K.bump_param_epoch()
 
     def ddp_step(self, pattern=None):
@@ -500,6 +526,7 @@ class VAEXperiment:
             self.optimizer.step()
         self.track_gradients()
         self.ema_update()
+        self.codebook_restart()
         self.global_step += 1
 
     # -- gradient tracking (trainer_params.track_grad_norm, exp_params.watch_gradients; optim.GradientTracker) -----
@@ -563,6 +590,108 @@ class VAEXperiment:
             self.model.load_state_dict(sd, strict=strict)
         self.model.load_state_dict(live)          # (what lies outside the slice -- BatchNorm statistics among it -- stays live)
 
+    # -- codebook usage (exp_params.codebook_stats / codebook_restart_every; optim.CodebookUsage) --------------------
+    def _build_codebook_usage(self, params):
+        """The usage counters of this run: ``codebook`` (training window, pool and restarts; on every rank) under
+        ``codebook_restart_every``, ``val_codebook`` (validation; rank 0 only) under ``codebook_stats``; both None without the
+        keys.  Refused by name: either key on a model without a ``vq_layer`` quantiser, and restarts when the codebooks lie
+        outside the optimizer's slice (``update_parameters``) -- Adam would never step a restarted code."""
+        stats, every, min_count, pool = codebook_settings(params.get("codebook_stats"), params.get("codebook_restart_every"),
+                                                          params.get("codebook_restart_min_count"),
+                                                          params.get("codebook_restart_pool"))
+        self.codebook_stats, self.codebook_every, self.codebook_min_count = stats, every, min_count
+        self.codebook = self.val_codebook = None
+        self.codebook_ordinal = self.codebook_restarted = 0      # restarts so far (the draw's seed), codes restarted so far
+        self.last_codebook_restart = None                        # the record of the last restart (also without a log file)
+        if not stats and every is None:
+            return
+        vq = getattr(self.model, "vq_layer", None)
+        if vq is None or not hasattr(vq, "usage_observer"):
+            key = "codebook_restart_every" if every is not None else "codebook_stats"
+            raise ValueError(f"{key} needs a model with a vq_layer quantiser (MCQVAE, VQVAE, CTMCQVAE), got "
+                             f"{type(self.model).__name__}")
+        if every is not None:
+            self.codebook = CodebookUsage(vq, pool)
+            if self.codebook.codebook_offset(self.optimizer) is None:
+                raise ValueError(f"codebook_restart_every cannot restart codes the optimizer does not step: update_parameters="
+                                 f"{params.get('update_parameters')!r} leaves the codebooks outside the optimizer's slice "
+                                 "(codebook_stats stays available)")
+        if stats and self._rank0():
+            self.val_codebook = CodebookUsage(vq)
+
+    @contextlib.contextmanager
+    def _counting_training_codes(self):
+        """The training counter is the quantiser's ``usage_observer`` inside (around the training batches of ``fit()`` only:
+        validation, ``sample_images``, the metrics and the tools count nothing here); nothing without restarts."""
+        if self.codebook is None:
+            yield
+            return
+        vq = self.model.vq_layer
+        vq.usage_observer = self.codebook.observe
+        try:
+            yield
+        finally:
+            vq.usage_observer = None
+
+    def codebook_restart(self):
+        """Called eagerly right behind an optimizer step, next to ``track_gradients()`` / ``ema_update()`` and never inside a
+        capture, ``global_step`` still naming the step that ran.  Every ``codebook_restart_every`` optimizer steps: [DDP: one SUM
+        all-reduce of the counts,] one device-to-host copy, the dead list, the draw from a CPU generator of its own, the
+        restart launch [DDP: on rank 0's rows, one broadcast], a parameter-epoch bump, counts back to zero and one JSONL line
+        ``{"codebook_restarts": n, "codebook_restarts_<i>": ..., "codebook_perplexity_<i>": ..., "codebook_usage_<i>": ...,
+        "step": s}`` over the window that ended.  On every other step, and without the key, nothing."""
+        cb = self.codebook
+        if cb is None or (self.global_step + 1) % self.codebook_every != 0:
+            return
+        ddp = self.ddp if self.ddp is not None and getattr(self.ddp, "active", False) else None
+        counts, dead, _ = cb.restart(self.optimizer, self.codebook_min_count, self.params.get("manual_seed", 0), self.codebook_ordinal,
+                                     reduce=ddp.all_reduce_counts if ddp is not None else None,
+                                     broadcast=ddp.broadcast_rows if ddp is not None else None)
+        self.codebook_ordinal += 1
+        self.codebook_restarted += len(dead)
+        rec = {"codebook_restarts": len(dead)}
+        for i in range(cb.C):
+            rec[f"codebook_restarts_{i}"] = sum(1 for c, _ in dead if c == i)
+        rec.update({k: v for k, v in codebook_record(counts, "").items() if "_dead" not in k and k[-1].isdigit()})
+        rec["step"] = self.global_step
+        self.last_codebook_restart = rec
+        if self.log_file is not None and self._rank0():
+            self.log_file.write(json.dumps(rec) + "\n")
+            self.log_file.flush()
+
+    def write_codebook_stats(self, usage) -> dict:
+        """What ``codebook_stats`` leaves of one validation epoch: ``val_codebook_perplexity_<i>`` / ``_usage_<i>`` / ``_dead_<i>``
+        per codebook and their unsuffixed means, computed in float64 on the host from one copy of the counts; also one JSONL
+        line.  An index outside [0, K) (NaN latents) is reported as ``val_codebook_invalid``."""
+        counts, invalid = usage.read()
+        rec = codebook_record(counts, "val_")
+        if invalid:
+            rec["val_codebook_invalid"] = invalid
+        if self.log_file is not None:
+            self.log_file.write(json.dumps({**rec, "step": self.global_step}) + "\n")
+            self.log_file.flush()
+        return rec
+
+    def _load_codebook_state(self, entry):
+        """Full resume under ``codebook_restart_every``: the window's counts, the restart ordinal and the total come back, so a
+        run resumed inside a window continues bit for bit; other ``every`` / ``min_count`` than the checkpoint's are refused."""
+        if entry is None:
+            raise RuntimeError("checkpoint holds no codebook usage (trainer['codebook']), this run restarts dead codes "
+                               "(exp_params.codebook_restart_every)")
+        if int(entry["every"]) != self.codebook_every or int(entry["min_count"]) != self.codebook_min_count:
+            raise RuntimeError(f"checkpoint counted its codes under codebook_restart_every={entry['every']!r}, "
+                               f"codebook_restart_min_count={entry['min_count']!r}, this run uses {self.codebook_every!r}, "
+                               f"{self.codebook_min_count!r}")
+        cb = self.codebook
+        if tuple(entry["counts"].shape) != tuple(cb.counts.shape):
+            raise RuntimeError("checkpoint's codebook counts have another shape than this model's codebooks")
+        cb.zero()
+        if self._rank0():                  # (the counts are rank 0's own rows; the other ranks' share of the window starts over)
+            cb.counts.copy_(entry["counts"])
+        valid = int(entry.get("valid_rows", -1))
+        cb.valid_rows = None if valid < 0 else min(valid, cb.pool.size(0))
+        self.codebook_ordinal, self.codebook_restarted = int(entry["ordinal"]), int(entry["restarted"])
+
     def _validate(self, epoch, val_batches, test_batches):
         """The validation part of one epoch of ``fit()``: the validation steps' means, ``write_graphs``, ``validation_metrics``
         and ``sample_images``; returns what joins the epoch record."""
@@ -576,6 +705,10 @@ class VAEXperiment:
             stats = causalgraph.GraphStats(ct.action_dim + 1, causalgraph.model_nodes(self.model),
                                            next(self.model.parameters()).device)
             ct.graph_observer = stats.observe
+        usage = self.val_codebook              # codebook_stats: rank 0's own validation rows, as val_graphs
+        if usage is not None:
+            usage.zero()
+            self.model.vq_layer.usage_observer = usage.observe
         try:
             for i, batch in enumerate(val_batches()):
                 r = self.validation_step(batch, i)
@@ -586,9 +719,13 @@ class VAEXperiment:
         finally:
             if stats is not None:
                 self.model.ct_layer.graph_observer = None
+            if usage is not None:
+                self.model.vq_layer.usage_observer = None
         rec.update({k: v / max(cnt, 1) for k, v in sums.items()})
         if stats is not None:
             rec.update(self.write_graphs(stats, epoch))
+        if usage is not None:
+            rec.update(self.write_codebook_stats(usage))
         rec.update(self.validation_metrics(epoch))
         if self.val_sampling and self.sample_dir is not None and test_batches is not None and self._rank0():
             first = next(iter(test_batches()), None)
@@ -605,47 +742,12 @@ class VAEXperiment:
         for epoch in range(start_epoch, max_epochs):
             self.model.train()
             t0 = time.time()
-            n = 0
             k = self.accumulate
             # k > 1: the batch index counts from 0 in every epoch, and the epoch's last batch ends its window whatever its index
             # (one batch of look-ahead: the loader is an iterable) -- no window state crosses an epoch boundary
             stream = ((b, True) for b in train_batches()) if k == 1 else with_window_ends(train_batches(), k)
-            for i, (batch, ends) in enumerate(stream):
-                real_img, _labels, kwargs = self._unpack(batch)
-                # graph_safe = False: the model's step depends on host state that changes per call (e.g. BetaVAE type 'B':
-                # the capacity C follows the loss-call counter), so a captured step would freeze it
-                if getattr(self.model, 'uses_labels', False) and torch.is_tensor(_labels):
-                    kwargs = {**kwargs, "labels": _labels.to(real_img.device)}      # part of the step's signature and inputs
-                key = _graph_key(real_img, kwargs) if (self.params.get('hipgraph', True) and real_img.is_cuda
-                                                       and getattr(self.model, 'graph_safe', True)) else None
-                if key is not None:
-                    gs = self._graphed.get(key)
-                    if gs is None:
-                        gs = self._graphed[key] = _GraphedTrainStep(self, real_img, kwargs)
-                    self.curr_device = real_img.device
-                    losses = gs.run(real_img, kwargs, ends)
-                    if ends:
-                        self.global_step -= 1              # log_all keys on the step that just ran
-                        self.log_all(losses, batch_size=real_img.size(0), validation=False)
-                        self.global_step += 1
-                else:
-                    self.model.zero_grad(lazy=True)
-                    self._log_train = ends                 # a record per optimizer step, with the losses of its last micro-batch
-                    try:
-                        loss = self.training_step(batch, i)
-                    finally:
-                        self._log_train = True
-                    K.backward(loss)
-                    self.model.settle_grads()
-                    if k == 1:
-                        self.optimizer_step()
-                    else:
-                        self.window_step(ends)
-                        if ends:
-                            self.track_gradients()
-                            self.ema_update()
-                            self.global_step += 1
-                n += batch[0].size(0)
+            with self._counting_training_codes():
+                n = self._train_epoch(stream, k)
             if self.scheduler is not None:
                 self.scheduler.step()                      # Lightning steps ExponentialLR once per epoch
             rec = {"epoch": epoch, "train_images": n, "epoch_seconds": time.time() - t0}
@@ -657,3 +759,45 @@ class VAEXperiment:
             if on_epoch_end is not None:
                 on_epoch_end(epoch, rec)
         return history
+
+    def _train_epoch(self, stream, k):
+        """The training batches of one epoch of ``fit()``: ``stream`` yields (batch, ends_window); returns the images seen."""
+        n = 0
+        for i, (batch, ends) in enumerate(stream):
+            real_img, _labels, kwargs = self._unpack(batch)
+            # graph_safe = False: the model's step depends on host state that changes per call (e.g. BetaVAE type 'B':
+            # the capacity C follows the loss-call counter), so a captured step would freeze it
+            if getattr(self.model, 'uses_labels', False) and torch.is_tensor(_labels):
+                kwargs = {**kwargs, "labels": _labels.to(real_img.device)}      # part of the step's signature and inputs
+            key = _graph_key(real_img, kwargs) if (self.params.get('hipgraph', True) and real_img.is_cuda
+                                                   and getattr(self.model, 'graph_safe', True)) else None
+            if key is not None:
+                gs = self._graphed.get(key)
+                if gs is None:
+                    gs = self._graphed[key] = _GraphedTrainStep(self, real_img, kwargs)
+                self.curr_device = real_img.device
+                losses = gs.run(real_img, kwargs, ends)
+                if ends:
+                    self.global_step -= 1              # log_all keys on the step that just ran
+                    self.log_all(losses, batch_size=real_img.size(0), validation=False)
+                    self.global_step += 1
+            else:
+                self.model.zero_grad(lazy=True)
+                self._log_train = ends                 # a record per optimizer step, with the losses of its last micro-batch
+                try:
+                    loss = self.training_step(batch, i)
+                finally:
+                    self._log_train = True
+                K.backward(loss)
+                self.model.settle_grads()
+                if k == 1:
+                    self.optimizer_step()
+                else:
+                    self.window_step(ends)
+                    if ends:
+                        self.track_gradients()
+                        self.ema_update()
+                        self.codebook_restart()
+                        self.global_step += 1
+            n += batch[0].size(0)
+        return n

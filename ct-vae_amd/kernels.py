@@ -2623,6 +2623,150 @@ def buffer_swap(a, b):
     native.call("ctvae_buffer_swap", a.data_ptr(), b.data_ptr(), a.numel())
 
 
+# ---------------------------------------------------------------------------------------------------
+# codebook usage and dead-code restarts (csrc/vqusage.hip; optim.CodebookUsage)
+# ---------------------------------------------------------------------------------------------------
+VQ_USAGE_MAX_K, VQ_USAGE_MAX_WORDS = 512, 8192      # what ctvae_vq_usage covers: K <= 512 and C * K <= 8192 (its LDS histogram)
+
+
+def vq_usage_supported(K, C):
+    return 1 <= K <= VQ_USAGE_MAX_K and C >= 1 and C * K <= VQ_USAGE_MAX_WORDS
+
+
+def _req_dense(what, name, t, dtype):
+    if not torch.is_tensor(t) or t.dtype != dtype:
+        raise ValueError(f"{what}: {name} must be a {dtype} tensor, got {getattr(t, 'dtype', type(t).__name__)}")
+    if not t.is_contiguous():
+        raise ValueError(f"{what}: {name} must be contiguous")
+
+
+def vq_usage_pass_indices() -> int:
+    """The indices one turn of the usage kernel's grid covers; a longer index tensor runs its grid-stride loop."""
+    return int(native.load().ctvae_vq_usage_pass_indices())
+
+
+def _vq_usage_args(what, inds, counts, invalid):
+    """The checks of ``vq_usage`` and its launch arguments (inds, counts, invalid, B, C, HW, K)."""
+    for name, t in (("inds", inds), ("counts", counts), ("invalid", invalid)):
+        _req_dense(what, name, t, torch.int64)
+    if inds.dim() < 3 or counts.dim() != 2 or invalid.numel() != 1 or inds.size(1) != counts.size(0) or inds.numel() == 0:
+        raise ValueError(f"{what}: inds [B, C, ...] {tuple(inds.shape)}, counts [C, K] {tuple(counts.shape)} and invalid [1] "
+                         f"{tuple(invalid.shape)} do not fit together")
+    C, K = counts.shape
+    if not vq_usage_supported(K, C):
+        raise ValueError(f"{what}: num_embeddings K={K} with C={C} codebooks is not covered: the kernel needs 1 <= K <= "
+                         f"{VQ_USAGE_MAX_K} and C * K <= {VQ_USAGE_MAX_WORDS}")
+    _req_cuda(inds, counts, invalid)
+    B = inds.size(0)
+    return inds.data_ptr(), counts.data_ptr(), invalid.data_ptr(), B, C, inds.numel() // (B * C), K
+
+
+def _vq_pool_fill_args(what, latents_nhwc, pool):
+    """The checks of ``vq_pool_fill`` and its launch arguments (latents, pool, P, D, R)."""
+    for name, t in (("latents", latents_nhwc), ("pool", pool)):
+        _req_dense(what, name, t, torch.float32)
+    if pool.dim() != 2 or latents_nhwc.dim() < 2 or latents_nhwc.size(-1) != pool.size(1) or latents_nhwc.numel() == 0 \
+            or pool.numel() == 0:
+        raise ValueError(f"{what}: latents [..., D] {tuple(latents_nhwc.shape)} and pool [R, D] {tuple(pool.shape)} do not "
+                         "fit together")
+    _req_cuda(latents_nhwc, pool)
+    R, D = pool.shape
+    return latents_nhwc.data_ptr(), pool.data_ptr(), latents_nhwc.numel() // D, D, R
+
+
+def vq_usage(inds, counts, invalid):
+    """counts[c][k] += the number of entries of inds[:, c] equal to k (ctvae_vq_usage).  inds: int64 [B, C, ...] as
+    ``vq_compute_inds`` returns it; counts: int64 [C, K]; invalid: one int64 word that counts the indices outside [0, K).  A wrong
+    dtype or shape, a non-contiguous tensor or a (K, C) outside ``vq_usage_supported`` raises a ValueError that names it, before
+    any launch."""
+    native.call("ctvae_vq_usage", *_vq_usage_args("vq_usage", inds, counts, invalid))
+
+
+def vq_pool_fill(latents_nhwc, pool) -> int:
+    """The first min(P, R) rows of the NHWC latents [..., D] (P rows) into the front of ``pool`` [R, D], word for word
+    (ctvae_vq_pool_fill); returns that row count, which the host knows from the shapes alone."""
+    args = _vq_pool_fill_args("vq_pool_fill", latents_nhwc, pool)
+    native.call("ctvae_vq_pool_fill", *args)
+    return min(args[2], args[4])
+
+
+def vq_usage_pool_fill(inds, counts, invalid, latents_nhwc, pool) -> int:
+    """``vq_usage`` and ``vq_pool_fill`` in one launch (ctvae_vq_usage_pool_fill): what a training forward issues.  Everything
+    is checked before the launch; returns the pool rows filled."""
+    what = "vq_usage_pool_fill"
+    args = _vq_pool_fill_args(what, latents_nhwc, pool)
+    native.call("ctvae_vq_usage_pool_fill", *_vq_usage_args(what, inds, counts, invalid), *args)
+    return min(args[2], args[4])
+
+
+def _restart_entries(what, entries, C, K, valid_rows):
+    """The (c, k, row) list as a host int64 [n, 3] tensor, every entry inside its range (K None: k is not checked)."""
+    ent = torch.as_tensor(entries, dtype=torch.int64, device="cpu").reshape(-1, 3)
+    if ent.numel():
+        hi = torch.tensor([C, K if K is not None else (1 << 62), valid_rows], dtype=torch.int64)
+        bad = ((ent < 0) | (ent >= hi)).any(dim=1).nonzero()
+        if bad.numel():
+            c, k, row = ent[int(bad[0])].tolist()
+            raise ValueError(f"{what}: entry {int(bad[0])} (c={c}, k={k}, row={row}) is out of range: c < {C}, "
+                             + (f"k < {K}, " if K is not None else "") + f"row < {valid_rows} valid pool rows")
+    return ent
+
+
+def _restart_shapes(what, pool, valid_rows, C, Dc):
+    _req_dense(what, "pool", pool, torch.float32)
+    if pool.dim() != 2 or not 0 <= valid_rows <= pool.size(0) or C - 1 + Dc > pool.size(1):
+        raise ValueError(f"{what}: pool [R, D] {tuple(pool.shape)} does not hold {valid_rows} valid rows of C - 1 + Dc = "
+                         f"{C - 1 + Dc} channels")
+
+
+def vq_restart_gather(entries, pool, valid_rows, C, Dc):
+    """rows[i] = pool[row_i][c_i : c_i + Dc) for the (c, k, row) entries (ctvae_vq_restart_gather): a new fp32 [n, Dc] tensor --
+    the first half of a data-parallel restart, whose rows rank 0 then broadcasts."""
+    _restart_shapes("vq_restart_gather", pool, valid_rows, C, Dc)
+    ent = _restart_entries("vq_restart_gather", entries, C, None, valid_rows)
+    _req_cuda(pool)
+    rows = torch.empty((ent.size(0), Dc), dtype=torch.float32, device=pool.device)
+    if ent.size(0):
+        dev_ent = ent.to(pool.device)
+        native.call("ctvae_vq_restart_gather", dev_ent.data_ptr(), ent.size(0), pool.data_ptr(), int(valid_rows), pool.size(1), C, Dc,
+                    rows.data_ptr())
+    return rows
+
+
+def vq_restart(entries, pool, valid_rows, codebooks, exp_avg, exp_avg_sq, rows=None):
+    """Restart the listed codes (ctvae_vq_restart).  entries: (c, k, row) triples, a list or a host int64 [n, 3] tensor;
+    codebooks / exp_avg / exp_avg_sq: fp32 [C, K, Dc] views of the flat parameter buffer and of the two Adam moments at the same
+    offsets.  For every entry E_c[k][:] = pool[row][c : c + Dc) -- the channels codebook c is compared against -- or, with
+    ``rows`` ([n, Dc], ``vq_restart_gather``'s), = rows[i]; both moments of those elements become 0.  Everything is checked on
+    the host before the launch: a wrong dtype, a non-contiguous tensor or an entry out of range raises a ValueError that names
+    it and nothing is written.  No entries: no launch.  The caller bumps the parameter epoch."""
+    what = "vq_restart"
+    for name, t in (("codebooks", codebooks), ("exp_avg", exp_avg), ("exp_avg_sq", exp_avg_sq)):
+        _req_dense(what, name, t, torch.float32)
+    if codebooks.dim() != 3 or exp_avg.shape != codebooks.shape or exp_avg_sq.shape != codebooks.shape:
+        raise ValueError(f"{what}: codebooks, exp_avg and exp_avg_sq are [C, K, Dc] tensors of one shape, got "
+                         f"{tuple(codebooks.shape)}, {tuple(exp_avg.shape)}, {tuple(exp_avg_sq.shape)}")
+    C, K, Dc = codebooks.shape
+    if rows is None:
+        _restart_shapes(what, pool, valid_rows, C, Dc)
+        ent = _restart_entries(what, entries, C, K, valid_rows)
+    else:
+        _req_dense(what, "rows", rows, torch.float32)
+        ent = _restart_entries(what, entries, C, K, 1 << 62)
+        if tuple(rows.shape) != (ent.size(0), Dc):
+            raise ValueError(f"{what}: rows must be [n, Dc] = {(ent.size(0), Dc)}, got {tuple(rows.shape)}")
+    if len({tuple(e) for e in ent[:, :2].tolist()}) != ent.size(0):
+        raise ValueError(f"{what}: a code (c, k) is listed twice")
+    _req_cuda(codebooks, exp_avg, exp_avg_sq, rows if rows is not None else pool)
+    if ent.size(0) == 0:
+        return
+    dev_ent = ent.to(codebooks.device)
+    D = pool.size(1) if rows is None else C - 1 + Dc      # (with rows the pool's width is not read: the least the launcher accepts)
+    native.call("ctvae_vq_restart", dev_ent.data_ptr(), ent.size(0), native.ptr(pool if rows is None else None),
+                int(valid_rows) if rows is None else 0, D, native.ptr(rows), codebooks.data_ptr(), exp_avg.data_ptr(),
+                exp_avg_sq.data_ptr(), C, K, Dc)
+
+
 def adam_flags_window(window, table, mode):
     """The block-activity words of one micro-batch (table.active, after adam_block_flags_local) against the window's
     (ctvae_adam_flags_window): "store" window = active, "add" window = max(window, active), "finish" active = max(window,

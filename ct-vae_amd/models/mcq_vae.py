@@ -22,10 +22,14 @@ class VectorQuantizerMS(nn.Module):
         super().__init__()
         self.K, self.D, self.beta = num_embeddings, embedding_dim, beta
         self.embedding = PackedEmbedding(self.K, self.D)
+        self.usage_observer = None      # called with (inds [B,1,H,W], latents NHWC) after every index search (optim.CodebookUsage)
 
     def compute_inds(self, latents: Tensor) -> Tensor:
         lat = K.to_nhwc(latents)
-        return K.vq_compute_inds(lat, [self.embedding.weight], self.K, 1)[:, 0]            # [B,H,W]
+        inds = K.vq_compute_inds(lat, [self.embedding.weight], self.K, 1)
+        if self.usage_observer is not None:
+            self.usage_observer(inds, lat)
+        return inds[:, 0]                                                                   # [B,H,W]
 
     def compute_latents(self, latents: Tensor, encoding_inds: Tensor):
         lat = K.to_nhwc(latents)
@@ -50,6 +54,7 @@ class MultipleCodebookVectorQuantizer(nn.Module):
         self.num_embeddings, self.beta = num_embeddings, beta
         self.quantizers = nn.ModuleList([VectorQuantizerMS(num_embeddings, self.reduced_embedding_dim, beta)
                                          for _ in range(codebooks)])
+        self.usage_observer = None      # called with (inds [B,C,H,W], latents NHWC) after every index search (optim.CodebookUsage)
 
     def _codebooks(self):
         ws = [q.embedding.weight for q in self.quantizers]
@@ -61,7 +66,11 @@ class MultipleCodebookVectorQuantizer(nn.Module):
 
     def compute_inds(self, latents: Tensor) -> Tensor:
         """[B,D,H,W] -> int64 [B,C,H,W]"""
-        return K.vq_compute_inds(K.to_nhwc(latents), self._codebooks(), self.num_embeddings, self.nb_codebooks)
+        lat = K.to_nhwc(latents)
+        inds = K.vq_compute_inds(lat, self._codebooks(), self.num_embeddings, self.nb_codebooks)
+        if self.usage_observer is not None:
+            self.usage_observer(inds, lat)
+        return inds
 
     def compute_latents(self, latents: Tensor, encoding_inds: Tensor):
         q, vq_loss = K.VQLookup.apply(K.to_nhwc(latents), encoding_inds, self.beta, self.num_embeddings, self.nb_codebooks,

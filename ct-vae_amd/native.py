@@ -122,6 +122,11 @@ SIGNATURES = {
     "ctvae_adam_flags_window": [_fp, _fp, _i, _i, _vp],
     "ctvae_ema_update": [_fp, _fp, _l, _f, _vp],
     "ctvae_buffer_swap": [_fp, _fp, _l, _vp],
+    "ctvae_vq_usage": [_fp, _fp, _fp, _i, _i, _i, _i, _vp],
+    "ctvae_vq_pool_fill": [_fp, _fp, _l, _i, _l, _vp],
+    "ctvae_vq_usage_pool_fill": [_fp, _fp, _fp, _i, _i, _i, _i, _fp, _fp, _l, _i, _l, _vp],
+    "ctvae_vq_restart": [_fp, _i, _fp, _i, _i, _fp, _fp, _fp, _fp, _i, _i, _i, _vp],
+    "ctvae_vq_restart_gather": [_fp, _i, _fp, _i, _i, _i, _i, _fp, _vp],
     "ctvae_grad_segment_stats": [_fp, _l, _f, _f, _fp, _i, _fp, _fp, _fp, _i, _fp, _fp, _fp, _fp, _fp, _fp, _fp, _fp, _fp, _i, _vp],
     "ctvae_grad_segment_hist": [_fp, _l, _f, _fp, _i, _fp, _fp, _i, _fp, _fp, _vp],
     "ctvae_mssim_forward": [_fp, _fp, _fp, _fp, _fp, _fp, _fp, _i, _i, _i, _i, _vp],
@@ -147,6 +152,7 @@ _RESTYPES = {
     "ctvae_adam_state_floats": _c.c_size_t,
     "ctvae_grad_clip_workspace_floats": _c.c_size_t,
     "ctvae_grad_accumulate_pass_floats": _c.c_size_t,
+    "ctvae_vq_usage_pass_indices": _c.c_size_t,
     "ctvae_grad_segment_chunk_floats": _c.c_size_t,
     "ctvae_mssim_part_floats": _c.c_size_t,
     "ctvae_glinear_wgrad_ws_bytes": _c.c_size_t,

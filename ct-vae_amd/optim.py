@@ -60,6 +60,14 @@ Weight average (``exp_params.ema_decay``; ``WeightEMA`` beside ``FlatAdam``, ``e
 moving average of the optimizer's slice of the flat parameter buffer in a buffer of its own, one ``ctvae_ema_update`` launch per
 optimizer step and one ``ctvae_buffer_swap`` launch to exchange it with the live weights for evaluation (csrc/ema.hip).  The
 reference keeps no such average: what it computes is defined here.  Without the key nothing is allocated or launched.
+
+Codebook usage (``exp_params.codebook_stats`` / ``codebook_restart_every``; ``CodebookUsage`` beside ``WeightEMA``,
+``codebook_settings`` its validator): how often every code of a quantising model is chosen, counted by ``ctvae_vq_usage`` from the
+index tensors the quantiser computes anyway (csrc/vqusage.hip; integer atomics, exact), the statistics of a counts tensor
+(``codebook_stats`` / ``codebook_record``: perplexity, usage, dead codes, float64 on the host), and dead-code restarts: the dead
+list (``codebook_dead_list``), the draw of pool rows (``codebook_restart_rows``) and the ``ctvae_vq_restart`` launch that writes
+the codes and zeroes their Adam moments.  The reference has neither: what they compute is defined here.  Without the keys nothing
+is allocated or launched.
 """
 import contextlib
 import math
@@ -407,6 +415,191 @@ class WeightEMA:
                 raise RuntimeError("weight average covers another parameter range than this optimizer's slice")
             self.buffer.copy_(sd["buffer"])
         self.updates = int(sd["updates"])
+
+
+CODEBOOK_STATS_KEY, CODEBOOK_EVERY_KEY = "codebook_stats", "codebook_restart_every"
+CODEBOOK_MIN_KEY, CODEBOOK_POOL_KEY = "codebook_restart_min_count", "codebook_restart_pool"
+CODEBOOK_POOL_DEFAULT = 1024
+
+
+def codebook_settings(stats=None, every=None, min_count=None, pool=None):
+    """Validated ``(codebook_stats, codebook_restart_every, codebook_restart_min_count, codebook_restart_pool)``.  ``stats``: a
+    real bool (None: False).  ``every``: an integer >= 1, None meaning no restarts -- returned as (stats, None, None, None), and
+    then neither of the other two may be set.  ``min_count`` (None: 1) and ``pool`` (None: 1024): integers >= 1.  Anything else
+    -- a bool, a float or a string where an integer belongs, a number below 1 -- raises a ValueError that names the key."""
+    if stats is not None and not isinstance(stats, bool):
+        raise ValueError(f"{CODEBOOK_STATS_KEY} {stats!r} is invalid: it must be true or false")
+
+    def integer(key, v):
+        if isinstance(v, bool) or not isinstance(v, int) or v < 1:
+            raise ValueError(f"{key} {v!r} is invalid: it must be an integer >= 1")
+        return int(v)
+
+    if every is None:
+        for key, v in ((CODEBOOK_MIN_KEY, min_count), (CODEBOOK_POOL_KEY, pool)):
+            if v is not None:
+                raise ValueError(f"{key} is set without {CODEBOOK_EVERY_KEY}: there are no restarts to apply it to")
+        return bool(stats), None, None, None
+    return (bool(stats), integer(CODEBOOK_EVERY_KEY, every), integer(CODEBOOK_MIN_KEY, 1 if min_count is None else min_count),
+            integer(CODEBOOK_POOL_KEY, CODEBOOK_POOL_DEFAULT if pool is None else pool))
+
+
+def codebook_stats(counts):
+    """Per-codebook usage statistics of an integer counts tensor [C, K], in float64 on the host: a list of C dicts with
+    ``perplexity`` = exp(-sum p ln p) over p = counts / total (the terms with p = 0 left out), ``usage`` = the fraction of
+    codes with count > 0, ``dead`` = the number of codes with count 0 and ``total``.  A codebook that was never asked (total 0)
+    reports perplexity None and usage 0.0: nothing in the result is NaN."""
+    c = torch.as_tensor(counts).detach().cpu().to(torch.float64)
+    out = []
+    for row in c:
+        total = float(row.sum())
+        used = row[row > 0]
+        perplexity = None
+        if total > 0:
+            p = used / total
+            perplexity = float(torch.exp(-(p * torch.log(p)).sum()))
+        out.append({"perplexity": perplexity, "usage": float(used.numel()) / row.numel(), "dead": int(row.numel() - used.numel()),
+                    "total": int(total)})
+    return out
+
+
+def codebook_record(counts, prefix):
+    """``codebook_stats`` as log entries: ``<prefix>codebook_perplexity_<i>`` / ``_usage_<i>`` / ``_dead_<i>`` per codebook i and
+    the unsuffixed means over codebooks (the perplexity's over the codebooks that have one; None when none has)."""
+    st = codebook_stats(counts)
+    rec = {}
+    for i, s in enumerate(st):
+        for k in ("perplexity", "usage", "dead"):
+            rec[f"{prefix}codebook_{k}_{i}"] = s[k]
+    known = [s["perplexity"] for s in st if s["perplexity"] is not None]
+    rec[f"{prefix}codebook_perplexity"] = sum(known) / len(known) if known else None
+    rec[f"{prefix}codebook_usage"] = sum(s["usage"] for s in st) / len(st)
+    rec[f"{prefix}codebook_dead"] = sum(s["dead"] for s in st) / len(st)
+    return rec
+
+
+def codebook_dead_list(counts, min_count=1):
+    """The dead codes of a window: every (c, k) with counts[c][k] < min_count, in (c, k) order."""
+    c = torch.as_tensor(counts).detach().cpu()
+    return [(int(i), int(j)) for i, j in (c < int(min_count)).nonzero().tolist()]
+
+
+def codebook_restart_seed(manual_seed, ordinal) -> int:
+    """Seed of restart number ``ordinal`` (counted from 0) of a run seeded with ``manual_seed``."""
+    return (int(manual_seed or 0) * 1_000_003 + int(ordinal)) * 2 + 1          # (odd: never a seed of sample_images / the metrics)
+
+
+def codebook_restart_rows(manual_seed, ordinal, n_dead, valid_rows):
+    """The pool row of each of ``n_dead`` dead codes, in list order: ONE ``randperm`` over the ``valid_rows`` valid pool rows
+    from a CPU generator of its own seeded with ``codebook_restart_seed``, consumed in order and wrapping around when there are
+    more dead codes than rows.  No global or device generator moves."""
+    if n_dead == 0:
+        return []
+    if valid_rows < 1:
+        raise ValueError("codebook restart: the pool holds no latent rows yet")
+    gen = torch.Generator(device="cpu")
+    gen.manual_seed(codebook_restart_seed(manual_seed, ordinal))
+    perm = torch.randperm(int(valid_rows), generator=gen).tolist()
+    return [perm[i % valid_rows] for i in range(n_dead)]
+
+
+def quantizer_codebooks(vq_layer):
+    """(the quantiser's codebooks as ONE fp32 [C, K, Dc] view of their storage, D) for the two quantiser classes of
+    models/mcq_vae.py: C codebooks stored back to back (``_codebooks()`` checks it), or the single embedding; D is the width of
+    the latents the quantiser reads."""
+    if hasattr(vq_layer, "quantizers"):
+        ws = vq_layer._codebooks()
+        C, (Kc, Dc) = len(ws), ws[0].shape
+        return ws[0].detach().as_strided((C, Kc, Dc), (Kc * Dc, Dc, 1)), C * Dc
+    w = vq_layer.embedding.weight
+    if not w.is_contiguous():
+        raise RuntimeError("the codebook is not stored row by row")
+    return w.detach().unsqueeze(0), w.size(1)
+
+
+class CodebookUsage:
+    """How often every code of a model's quantiser is chosen (``exp_params.codebook_stats`` / ``codebook_restart_every``), counted
+    by HIP kernels of its own (csrc/vqusage.hip) from the index tensors the quantiser computes anyway.
+
+    ``observe`` is what the experiment sets as the quantiser's ``usage_observer``: one launch per index search --
+    ``ctvae_vq_usage`` (``counts += histogram``; exact integers) or, with a pool, ``ctvae_vq_usage_pool_fill``, which also keeps
+    the first min(P, R) latent rows of the search as restart candidates.  It takes pointers and shapes only, so inside a captured
+    training step it replays correctly; every buffer is allocated here, outside any capture.  ``counts`` and the ``invalid`` word (indices outside
+    [0, K): none, unless the latents hold NaN) are one int64 buffer, so ``read()`` is one device-to-host copy.
+
+    ``valid_rows``: how many pool rows hold latents of the LAST search, known on the host from shapes alone -- the smallest
+    min(P, R) of all searches so far (every fill overwrites at least that many rows).  A replayed step runs no Python, but every
+    signature has run eagerly before its capture, so the value is the same in captured and eager runs.
+
+    ``restart`` (with a pool): the dead codes of a window, counts < min_count in (c, k) order, get pool rows drawn by
+    ``codebook_restart_rows`` and are overwritten by ``ctvae_vq_restart``, E_c[k] = pool[row][c : c + Dc), with both Adam
+    moments of those elements zeroed.  ``reduce`` / ``broadcast`` (data-parallel runs): one SUM all-reduce of the counts, so a
+    code used on any rank is alive, and one broadcast of rank 0's gathered rows, so every rank writes the same values."""
+
+    def __init__(self, vq_layer, pool_rows=None):
+        self.vq = vq_layer
+        cb, self.D = quantizer_codebooks(vq_layer)
+        self.C, self.K, self.Dc = cb.shape
+        if not K.vq_usage_supported(self.K, self.C):
+            raise ValueError(f"codebook usage: num_embeddings {self.K} with {self.C} codebooks is not covered by the usage kernel "
+                             f"(K <= {K.VQ_USAGE_MAX_K}, C * K <= {K.VQ_USAGE_MAX_WORDS})")
+        self.words = torch.zeros(self.C * self.K + 1, dtype=torch.int64, device=cb.device)
+        self.counts, self.invalid = self.words[:-1].view(self.C, self.K), self.words[-1:]
+        self.pool = torch.zeros((int(pool_rows), self.D), dtype=torch.float32, device=cb.device) if pool_rows else None
+        self.valid_rows = None          # no search has filled the pool yet
+
+    def observe(self, inds, latents_nhwc):
+        if self.pool is None:
+            K.vq_usage(inds, self.counts, self.invalid)
+            return
+        lat = latents_nhwc.detach()
+        rows = K.vq_usage_pool_fill(inds, self.counts, self.invalid, lat if lat.is_contiguous() else lat.contiguous(), self.pool)
+        self.valid_rows = rows if self.valid_rows is None else min(self.valid_rows, rows)
+
+    def read(self):
+        """(counts [C, K], invalid) on the host: one copy."""
+        w = self.words.cpu()
+        return w[:-1].view(self.C, self.K), int(w[-1])
+
+    def zero(self):
+        self.words.zero_()
+
+    def restart(self, optimizer, min_count, manual_seed, ordinal, reduce=None, broadcast=None):
+        """One restart behind an optimizer step (class docstring); returns (host counts of the window, dead list, rows).  The
+        counts are zeroed and the parameter epoch moves."""
+        if reduce is not None:
+            reduce(self.words)
+        counts, _ = self.read()
+        dead = codebook_dead_list(counts, min_count)
+        rows = codebook_restart_rows(manual_seed, ordinal, len(dead), self.valid_rows or 0)
+        if dead:
+            entries = [(c, k, r) for (c, k), r in zip(dead, rows)]
+            cb, m, v = self.codebook_views(optimizer)
+            if broadcast is None:
+                K.vq_restart(entries, self.pool, self.valid_rows, cb, m, v)
+            else:
+                gathered = K.vq_restart_gather(entries, self.pool, self.valid_rows, self.C, self.Dc)
+                broadcast(gathered)
+                K.vq_restart(entries, None, 0, cb, m, v, rows=gathered)
+        K.bump_param_epoch()
+        self.zero()
+        return counts, dead, rows
+
+    def codebook_offset(self, optimizer):
+        """Offset of the codebooks inside the optimizer's slice of the flat parameter buffer; None when they lie outside it."""
+        cb, _ = quantizer_codebooks(self.vq)
+        flat = optimizer.model.flat_params
+        lo = (cb.data_ptr() - flat.data_ptr()) // 4 - int(optimizer.slice.start or 0)
+        n = flat[optimizer.slice].numel()
+        return lo if 0 <= lo and lo + cb.numel() <= n else None
+
+    def codebook_views(self, optimizer):
+        """The codebooks and the two Adam moments of the same elements as [C, K, Dc] views."""
+        cb, _ = quantizer_codebooks(self.vq)
+        lo = self.codebook_offset(optimizer)
+        if lo is None:
+            raise RuntimeError("the codebooks lie outside the optimizer's slice")
+        return cb, optimizer.exp_avg[lo:lo + cb.numel()].view(cb.shape), optimizer.exp_avg_sq[lo:lo + cb.numel()].view(cb.shape)
 
 
 TRACK_NORM_KEY = "track_grad_norm"

@@ -33,6 +33,14 @@ exponential moving average of the optimized weights and, under ``ema_eval``, val
 weights; the checkpoint gains ``ema_state_dict`` (the same keys, the averaged weights) and ``trainer['ema']``.  A full resume under
 the key needs both, written under the same decay and warm-up; ``load_weights_only`` starts the average from the loaded weights; a
 run without the key ignores them.  A refused value is a SystemExit that names ``exp_params.<key>``.
+``exp_params.codebook_stats: true`` adds per-codebook usage statistics (``val_codebook_perplexity_<i>`` / ``_usage_<i>`` /
+``_dead_<i>`` and their means) to every validation epoch of a quantising model (MCQVAE, VQVAE, CTMCQVAE);
+``exp_params.codebook_restart_every: N`` (with ``codebook_restart_min_count``, default 1, and ``codebook_restart_pool``, default
+1024) counts usage during training and every N optimizer steps overwrites the codes chosen fewer than ``min_count`` times with
+encoder outputs of the last batch, zeroing their Adam moments (experiment.py, optim.py: ``CodebookUsage``).  The checkpoint
+gains ``trainer['codebook']``; a full resume under the key continues the window bit for bit and refuses other ``every`` /
+``min_count``; ``load_weights_only`` starts a fresh window; a run without the key ignores the entry.  Restarts are refused when
+``update_parameters`` leaves the codebooks outside the optimizer's slice.
 """
 import argparse
 import json
@@ -46,7 +54,7 @@ from . import filler
 from .ddp import GradBucketAllReduce
 from .experiment import VAEXperiment
 from .models import vae_models
-from .optim import accumulate_setting, ema_settings, track_grad_norm_setting, watch_settings
+from .optim import accumulate_setting, codebook_settings, ema_settings, track_grad_norm_setting, watch_settings
 
 
 class SyntheticData:
@@ -231,6 +239,44 @@ def check_ema_checkpoint(ckpt, path, decay, warmup):
                          f"{ema['decay']!r} / {ema['warmup']!r}")
 
 
+VQ_MODELS = ("MCQVAE", "VQVAE", "CTMCQVAE")        # the served models with a ``vq_layer`` quantiser
+
+
+def exp_codebook(config):
+    """``exp_params.codebook_stats`` / ``codebook_restart_every`` / ``codebook_restart_min_count`` / ``codebook_restart_pool`` as
+    ``(stats, every, min_count, pool)`` (every None: no restarts).  A refused value, either feature on a model that does not
+    quantise, and restarts under an ``update_parameters`` other than ``vq_layer`` (the optimizer would not step the codebooks) are
+    a SystemExit that names the key."""
+    ep = config['exp_params']
+    try:
+        stats, every, min_count, pool = codebook_settings(ep.get('codebook_stats'), ep.get('codebook_restart_every'),
+                                                          ep.get('codebook_restart_min_count'), ep.get('codebook_restart_pool'))
+    except ValueError as e:
+        raise SystemExit(f"exp_params.{e}")
+    name = config['model_params'].get('name')
+    if (stats or every is not None) and name not in VQ_MODELS:
+        key = 'codebook_restart_every' if every is not None else 'codebook_stats'
+        raise SystemExit(f"exp_params.{key} needs a model with a vq_layer quantiser ({', '.join(VQ_MODELS)}), model_params.name "
+                         f"is {name!r}")
+    if every is not None and ep.get('update_parameters') not in (None, 'vq_layer'):
+        raise SystemExit(f"exp_params.codebook_restart_every cannot restart codes the optimizer does not step: "
+                         f"exp_params.update_parameters is {ep.get('update_parameters')!r} (codebook_stats stays available)")
+    return stats, every, min_count, pool
+
+
+def check_codebook_checkpoint(ckpt, path, every, min_count):
+    """Full resume of a run that restarts dead codes: the checkpoint must hold ``trainer['codebook']``, written under this run's
+    ``every`` and ``min_count``; otherwise a SystemExit names the key and the path."""
+    entry = ckpt.get("trainer", {}).get("codebook")
+    if entry is None:
+        raise SystemExit(f"exp_params.codebook_restart_every is set, but {path} holds no codebook usage (no trainer['codebook']): "
+                         "it was written by a run without the key; set trainer_params.load_weights_only to start a fresh window "
+                         "from its weights")
+    if int(entry["every"]) != every or int(entry["min_count"]) != min_count:
+        raise SystemExit(f"exp_params.codebook_restart_every / codebook_restart_min_count are {every!r} / {min_count!r}, but {path} "
+                         f"counted its codes under {entry['every']!r} / {entry['min_count']!r}")
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser(description='MI355X runner for the ct-vae models')
     ap.add_argument('--config', '-c', dest="filename", metavar='FILE', default='configs/vae.yaml')
@@ -240,6 +286,7 @@ def main(argv=None):
     with open(args.filename) as f:
         config = yaml.safe_load(f)
     ema_decay, ema_warmup, _ = exp_ema(config['exp_params'])
+    _, restart_every, restart_min_count, _ = exp_codebook(config)
 
     rank =int(os.environ.get("RANK", "0"))
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -273,6 +320,8 @@ def main(argv=None):
         ckpt = torch.load(ckpt_path, map_location="cpu", weights_only=True)
         if ema_decay is not None and not weights_only:
             check_ema_checkpoint(ckpt, ckpt_path, ema_decay, ema_warmup)
+        if restart_every is not None and not weights_only:
+            check_codebook_checkpoint(ckpt, ckpt_path, restart_every, restart_min_count)
         model.load_state_dict({k[6:]: v for k, v in ckpt['state_dict'].items() if k.startswith("model.")}, strict=not weights_only)
     ddp = GradBucketAllReduce(model) if world > 1 else None
     log_dir = os.path.join(config['logging_params'].get('save_dir', 'logs/'), config['logging_params'].get('name', mp['name']))

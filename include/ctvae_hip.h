@@ -726,6 +726,35 @@ int ctvae_adam_flags_window(int* window, int* active, int nb, int mode, void* st
 int ctvae_ema_update(float* ema, const float* p, long n, float one_minus_decay, void* stream);
 int ctvae_buffer_swap(float* a, float* b, long n, void* stream);
 
+/* Codebook usage and dead-code restarts of the vector-quantised models (exp_params.codebook_stats / codebook_restart_every).
+ *   ctvae_vq_usage           counts[c][k] += the number of indices of codebook c equal to k.  `inds` is int64 [B][C][HW] (what
+ *                            ctvae_vq_inds writes), `counts` int64 [C][K], `invalid` one int64 word: an index outside [0, K) adds 1
+ *                            to it and is written nowhere else.  Integer atomics only: exact, independent of the order.  Covered:
+ *                            1 <= K <= 512 and C * K <= 8192; everything else returns the bad-argument code without a launch.
+ *                            Pointers and shape integers only: a captured launch replays correctly.
+ *   ctvae_vq_usage_pass_indices   the indices one turn of that kernel's grid covers (more of them: a grid-stride loop).
+ *   ctvae_vq_pool_fill       pool[0 : rows) = latents[0 : rows) as raw 32-bit words, rows = min(P, R), for NHWC latents [P][D] and a
+ *                            pool [R][D]; rows behind min(P, R) are not touched.  The ranges must not overlap.
+ *   ctvae_vq_usage_pool_fill both of the above in ONE launch (the first workgroups count, the others copy): what a training
+ *                            forward issues, one node of a captured step instead of two.  The same arguments, checks and results.
+ *   ctvae_vq_restart         for every entry i = (c, k, row) of `list` (n entries of three int64 words, on the device) and d < Dc:
+ *                            codebooks[c][k][d] = pool[row][c + d] -- the offset is c, not c * Dc: the slice of the latents codebook
+ *                            c is compared against -- or, with `rows` non-null, = rows[i][d] (`pool` is then not read); exp_avg and
+ *                            exp_avg_sq of the same elements = 0.  codebooks / exp_avg / exp_avg_sq are [C][K][Dc], row < valid_rows
+ *                            <= R, C - 1 + Dc <= D.  No other word is written; an entry outside its ranges is skipped; n = 0
+ *                            launches nothing.
+ *   ctvae_vq_restart_gather  rows[i][d] = pool[row_i][c_i + d]: the first half of a data-parallel restart (gather, broadcast from
+ *                            rank 0, ctvae_vq_restart with `rows`). */
+size_t ctvae_vq_usage_pass_indices(void);
+int ctvae_vq_usage(const long* inds, long* counts, long* invalid, int B, int C, int HW, int K, void* stream);
+int ctvae_vq_pool_fill(const float* latents, float* pool, long P, int D, long R, void* stream);
+int ctvae_vq_usage_pool_fill(const long* inds, long* counts, long* invalid, int B, int C, int HW, int K, const float* latents,
+                             float* pool, long P, int D, long R, void* stream);
+int ctvae_vq_restart(const long* list, int n, const float* pool, int valid_rows, int D, const float* rows, float* codebooks,
+                     float* exp_avg, float* exp_avg_sq, int C, int K, int Dc, void* stream);
+int ctvae_vq_restart_gather(const long* list, int n, const float* pool, int valid_rows, int D, int C, int Dc, float* rows,
+                            void* stream);
+
 /* Gradient tracking: per-parameter norms and 64-bin histograms from the flat gradient buffer (Lightning's track_grad_norm, wandb's
  * watch).  `grads` (n floats) is read only.  A segment is five 64-bit words (base, rows, period, col_lo, width) and names the
  * elements base + r * period + col_lo + c, r < rows, c < width (a contiguous parameter: one row; the heads of a grouped Linear
