@@ -198,6 +198,8 @@ int launch_graph_accumulate(const float* adj, const int* group, const float* mas
                             int* edge_count, double* mask_sum, int* rows, int* mask_rows, int* skipped, hipStream_t st);
 int launch_heatmap_u8(const float* values, int M, int H, int W, float lo, float hi, int cell, int nrow, int pad, int pad_r, int pad_g,
                       int pad_b, const uint8_t* table, int scanlines, uint8_t* out, size_t out_bytes, hipStream_t st);
+int launch_latent_accumulate(const float* mu, long mu_pitch, const float* logvar, long lv_pitch, int B, int L, double* kl_sum,
+                             double* mu_sum, double* sig2_sum, double* cov_sum, int* nonfinite, int* rows, hipStream_t st);
 int launch_loss_forward(const float* r, const float* x, long n, const float* mu, long mu_rs, const float* lv, long lv_rs,
                         int B, int L, float M_N, const float* extra, float* out4, float* ws, size_t ws_bytes,
                         hipStream_t st, float logcosh_alpha, float* g_r = nullptr, float* g_mu = nullptr, float* g_lv = nullptr,
@@ -1100,6 +1102,12 @@ int ctvae_heatmap_u8(const float* values, int M, int H, int W, float lo, float h
                      int pad_g, int pad_b, const uint8_t* table, int scanlines, uint8_t* out, size_t out_bytes, void* stream) {
   return launch_heatmap_u8(values, M, H, W, lo, hi, cell, nrow, padding, pad_r, pad_g, pad_b, table, scanlines, out, out_bytes,
                            (hipStream_t)stream);
+}
+
+int ctvae_latent_accumulate(const float* mu, long mu_pitch, const float* logvar, long logvar_pitch, int B, int L, double* kl_sum,
+                            double* mu_sum, double* sig2_sum, double* cov_sum, int32_t* nonfinite, int32_t* rows, void* stream) {
+  return launch_latent_accumulate(mu, mu_pitch, logvar, logvar_pitch, B, L, kl_sum, mu_sum, sig2_sum, cov_sum, nonfinite, rows,
+                                  (hipStream_t)stream);
 }
 
 size_t ctvae_adam_state_floats(void) { return adam_state_floats(); }

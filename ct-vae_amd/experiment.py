@@ -89,6 +89,16 @@ counters of the skip modes are untouched.  ``state_dict()`` carries ``"codebook"
 restarted, valid_rows}``; a full resume restores it and refuses other ``every`` / ``min_count``.  Refused when the experiment is
 built: either key on a model without such a quantiser, and restarts when ``update_parameters`` leaves the codebooks outside the
 optimizer's slice.  Without the keys there is no buffer, no launch, no log key and no entry.
+
+``exp_params.latent_stats`` (a bool): latent usage of the models with a Gaussian posterior (``BaseVAE.gaussian_posterior``), by
+``latentstats.LatentStats`` on rank 0.  ``_validate`` zeroes it, every ``validation_step`` hands it the batch's ``mu`` / ``log_var``
+views (one ``ctvae_latent_accumulate`` launch, eager like all of validation, no device-to-host copy), and behind the validation
+steps ``write_latent_stats`` makes the one copy and adds ``val_latent_kl_total`` / ``_active_units`` / ``_collapsed`` /
+``_mean_abs_corr`` / ``_gaussian_tc`` / ``_nonfinite`` / ``_rows`` to the epoch record and the JSONL log (what is undefined is left
+out), and with a ``sample_dir`` writes ``Latents/latent_stats_<name>_Epoch_<e>.npz`` and ``Latents/corr_<name>_Epoch_<e>.png``.
+Under ``ema_eval`` the numbers describe the averaged weights; with several ranks they are rank 0's own rows.  It draws nothing and
+writes no model state, so training is bit for bit the same with and without it.  Refused when the experiment is built: the key
+on a model whose hook returns None.  Without the key there is no buffer, no launch, no file and no log key.
 """
 import contextlib
 import json
@@ -101,6 +111,8 @@ import torch
 from . import imagegrid
 from . import kernels as K
 from .ddp import GradBucketAllReduce
+from .latentstats import (LATENT_DIR, LatentStats, has_gaussian_posterior, latent_stats_setting, needs_gaussian_posterior,
+                          record as latent_record, write_files as write_latent_files)
 from .metrics import _eval_mode as eval_mode
 from .optim import (CodebookUsage, ExponentialLR, FlatAdam, GradientTracker, WeightEMA, absent_grad_setting, accumulate_setting,
                     clip_settings, codebook_record, codebook_settings, ema_settings, track_grad_norm_setting, watch_settings,
@@ -277,6 +289,15 @@ class VAEXperiment:
         decay, warmup, self.ema_eval = ema_settings(params.get("ema_decay"), params.get("ema_warmup"), params.get("ema_eval"))
         self.ema = WeightEMA(self.optimizer, decay, warmup) if decay is not None else None
         self._build_codebook_usage(params)
+        # latent usage (latentstats.LatentStats): validated on every rank, built on rank 0 only
+        self.latent_stats = latent_stats_setting(params.get("latent_stats"))
+        self.val_latents = None
+        self._observing_latents = False         # True inside the validation steps of _validate() only
+        if self.latent_stats:
+            if not has_gaussian_posterior(vae_model):
+                raise ValueError(needs_gaussian_posterior(vae_model))
+            if self._rank0():
+                self.val_latents = LatentStats(vae_model.latent_dim, next(vae_model.parameters()).device)
 
     def forward(self, input, **kwargs):
         return self.model(input, **kwargs)
@@ -303,6 +324,8 @@ class VAEXperiment:
         with torch.no_grad():
             results = self.forward(real_img, labels=labels, **kwargs)
             val_loss = self.model.loss_function(*results, M_N=1.0, optimizer_idx=optimizer_idx, batch_idx=batch_idx)
+            if self._observing_latents:        # latent_stats: one launch, nothing comes back to the host before the epoch ends
+                self.val_latents.observe(*self.model.gaussian_posterior(results))
         return self.log_all(val_loss, batch_size=real_img.size(0), validation=True, force=True)
 
     def metric_func(self, x):
@@ -672,6 +695,22 @@ class VAEXperiment:
             self.log_file.flush()
         return rec
 
+    def write_latent_stats(self, latents, epoch: int) -> dict:
+        """What ``latent_stats`` leaves of one validation epoch: the ``val_latent_*`` scalars (``latentstats.summarize``, float64 on
+        the host from one copy of the accumulators; the undefined ones are left out), also as one JSONL line, and with a
+        ``sample_dir`` and at least two rows ``Latents/latent_stats_<name>_Epoch_<e>.npz`` and ``Latents/corr_<name>_Epoch_<e>.png``."""
+        res = latents.result()
+        rec = latent_record(res)
+        if self.sample_dir is not None and "cov" in res:
+            d = os.path.join(self.sample_dir, LATENT_DIR)
+            os.makedirs(d, exist_ok=True)
+            write_latent_files(res, os.path.join(d, f"latent_stats_{self.run_name}_Epoch_{epoch}.npz"),
+                               os.path.join(d, f"corr_{self.run_name}_Epoch_{epoch}.png"))
+        if self.log_file is not None:
+            self.log_file.write(json.dumps({**rec, "step": self.global_step}) + "\n")
+            self.log_file.flush()
+        return rec
+
     def _load_codebook_state(self, entry):
         """Full resume under ``codebook_restart_every``: the window's counts, the restart ordinal and the total come back, so a
         run resumed inside a window continues bit for bit; other ``every`` / ``min_count`` than the checkpoint's are refused."""
@@ -709,6 +748,10 @@ class VAEXperiment:
         if usage is not None:
             usage.zero()
             self.model.vq_layer.usage_observer = usage.observe
+        latents = self.val_latents             # latent_stats: rank 0's own validation rows too
+        if latents is not None:
+            latents.zero()
+            self._observing_latents = True
         try:
             for i, batch in enumerate(val_batches()):
                 r = self.validation_step(batch, i)
@@ -721,11 +764,14 @@ class VAEXperiment:
                 self.model.ct_layer.graph_observer = None
             if usage is not None:
                 self.model.vq_layer.usage_observer = None
+            self._observing_latents = False
         rec.update({k: v / max(cnt, 1) for k, v in sums.items()})
         if stats is not None:
             rec.update(self.write_graphs(stats, epoch))
         if usage is not None:
             rec.update(self.write_codebook_stats(usage))
+        if latents is not None:
+            rec.update(self.write_latent_stats(latents, epoch))
         rec.update(self.validation_metrics(epoch))
         if self.val_sampling and self.sample_dir is not None and test_batches is not None and self._rank0():
             first = next(iter(test_batches()), None)

@@ -2896,3 +2896,49 @@ def grad_segment_hist(table, grads, scale=1.0):
     native.call("ctvae_grad_segment_hist", grads.data_ptr(), table.n, float(scale), table.segments.data_ptr(), table.nseg,
                 table.chunk_seg.data_ptr(), table.chunk_first.data_ptr(), table.nchunks, table.out_range.data_ptr(),
                 table.out_hist.data_ptr())
+
+
+# ---------------------------------------------------------------------------------------------------
+# latent usage of the Gaussian models (csrc/latentstat.hip; latentstats.LatentStats)
+# ---------------------------------------------------------------------------------------------------
+LATENT_MAX_L = 1024                      # what ctvae_latent_accumulate covers: cov_sum is L * L doubles
+LATENT_STATE = (("kl_sum", torch.float64, 1), ("mu_sum", torch.float64, 1), ("sig2_sum", torch.float64, 1),
+                ("cov_sum", torch.float64, 2), ("nonfinite", torch.int32, 1), ("rows", torch.int32, 0))
+
+
+def _latent_rows(t, L):
+    """A [B, L] fp32 tensor as (tensor to keep alive, row pitch in floats): its own memory when the columns are unit-stride and
+    the rows at least L floats apart -- a column half of a [B, 2L] heads tensor, a slice of an expanded view -- else a
+    contiguous copy."""
+    B = t.size(0)
+    if (L > 1 and t.stride(1) != 1) or (B > 1 and t.stride(0) < L):
+        t = t.contiguous()
+    return t, (t.stride(0) if B > 1 else L)
+
+
+def latent_accumulate(mu, log_var, state):
+    """The rows of mu, log_var (fp32 [B, L] device tensors, detached here) added into ``state`` (ctvae_latent_accumulate): a dict
+    of contiguous device tensors ``kl_sum``, ``mu_sum``, ``sig2_sum`` (float64 [L]), ``cov_sum`` (float64 [L, L]), ``nonfinite``
+    (int32 [L]) and ``rows`` (int32 [1]).  One launch, no copy of a unit-stride input, no host synchronisation.  A CPU tensor is
+    a RuntimeError (there is no CPU fallback); a wrong dtype or shape raises a ValueError that names it, before any launch."""
+    what = "latent_accumulate"
+    for name, t in (("mu", mu), ("log_var", log_var)):
+        if not torch.is_tensor(t) or t.dtype != torch.float32 or t.dim() != 2:
+            raise ValueError(f"{what}: {name} must be a torch.float32 [B, L] tensor, got "
+                             f"{getattr(t, 'dtype', type(t).__name__)} {tuple(getattr(t, 'shape', ()))}")
+    if mu.shape != log_var.shape:
+        raise ValueError(f"{what}: mu {tuple(mu.shape)} and log_var {tuple(log_var.shape)} must have one shape")
+    B, L = mu.shape
+    if not 1 <= L <= LATENT_MAX_L:
+        raise ValueError(f"{what}: latent_dim L={L} is not covered: the kernel needs 1 <= L <= {LATENT_MAX_L}")
+    for name, dtype, rank in LATENT_STATE:
+        t = state.get(name)
+        _req_dense(what, name, t, dtype)
+        if tuple(t.shape) != ((1,) if rank == 0 else (L,) * rank):
+            raise ValueError(f"{what}: {name} must be {[1] if rank == 0 else [L] * rank} for L={L}, got {tuple(t.shape)}")
+    _req_cuda(mu, log_var, *(state[name] for name, _, _ in LATENT_STATE))
+    if B == 0:
+        return
+    m, pm = _latent_rows(mu.detach(), L)
+    v, pv = _latent_rows(log_var.detach(), L)
+    native.call("ctvae_latent_accumulate", m.data_ptr(), pm, v.data_ptr(), pv, B, L, *(state[name].data_ptr() for name, _, _ in LATENT_STATE))

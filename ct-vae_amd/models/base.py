@@ -29,6 +29,11 @@ class BaseVAE(FlatParamMixin, nn.Module):
     def generate(self, x: Tensor, **kwargs) -> Tensor:
         raise NotImplementedError
 
+    def gaussian_posterior(self, results: List[Tensor]):
+        """(mu, log_var) of ``forward``'s results as [B, L] views, for the models with a Gaussian posterior (latentstats.py);
+        None for every other model."""
+        return None
+
     @abstractmethod
     def forward(self, *inputs: Tensor) -> Tensor:
         pass

@@ -102,6 +102,9 @@ class BetaTCVAE(BaseVAE):
         z = self.reparameterize(mu, log_var, eps)
         return [self.decode(z), input, mu, log_var, z]
 
+    def gaussian_posterior(self, results: List[Tensor]):
+        return results[2], results[3]
+
     def _log_importance_weights(self, batch_size, dataset_size, device):
         """betatc_vae.py:176-183, as written there (incl. which entries the strided assignments touch)."""
         key = (batch_size, float(dataset_size), device)

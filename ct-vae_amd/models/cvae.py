@@ -103,6 +103,9 @@ class ConditionalVAE(BaseVAE):
         z = self.reparameterize(mu, log_var, eps)
         return [self.decode(torch.cat([z, y], dim=1)), input, mu, log_var]
 
+    def gaussian_posterior(self, results: List[Tensor]):
+        return results[2], results[3]
+
     def loss_function(self, *args, **kwargs) -> dict:
         """MSE + M_N * KL (cvae.py:132-146); 'KLD' carries the reference's flipped sign."""
         recons, input, mu, log_var = args[0], args[1], args[2], args[3]

@@ -99,6 +99,10 @@ class JointVAE(BaseVAE):
         z = self.reparameterize(mu, log_var, q, e=eps, u=u)
         return [self.decode(z), input, q, mu, log_var]
 
+    def gaussian_posterior(self, results: List[Tensor]):
+        """The Gaussian part of the joint posterior; the categorical code is not covered."""
+        return results[3], results[4]
+
     def loss_function(self, *args, **kwargs) -> dict:
         recons, input, q, mu, log_var = args[0], args[1], args[2], args[3], args[4]
         kld_weight = kwargs['M_N']

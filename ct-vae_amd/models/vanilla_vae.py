@@ -166,6 +166,13 @@ class VanillaVAE(BaseVAE):
         out = K.VAELoss.apply(K.to_nhwc(recons), self._cached_nhwc(input), mu, log_var, None, kld_weight)
         return {'loss': out[0], 'Reconstruction_Loss': out[1].detach(), 'KLD': out[3].detach()}
 
+    def gaussian_posterior(self, results: List[Tensor]):
+        """results[2], results[3] as [B, L] views: index 0 on every middle axis (IWAE / MIWAE expand them to [B, (M,) S, L])."""
+        mu, log_var = results[2], results[3]
+        while mu.dim() > 2:
+            mu, log_var = mu[:, 0], log_var[:, 0]
+        return mu, log_var
+
     def sample(self, num_samples: int, current_device: int, **kwargs) -> Tensor:
         z = torch.randn(num_samples, self.latent_dim).to(current_device)
         return self.decode(z)

@@ -103,6 +103,9 @@ class InfoVAE(VanillaVAE):
         z = self.reparameterize(mu, log_var, eps)
         return [self.decode(z), input, z, mu, log_var]
 
+    def gaussian_posterior(self, results: List[Tensor]):
+        return results[3], results[4]
+
     def compute_mmd(self, z: Tensor, prior_z: Tensor = None) -> Tensor:
         return _mmd(z, self.kernel_type, self.z_var, 1.0, 1.0, 1.0, prior_z)[0]
 

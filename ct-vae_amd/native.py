@@ -111,6 +111,7 @@ SIGNATURES = {
     "ctvae_action_hits": [_fp, _fp, _i, _i, _fp, _vp],
     "ctvae_graph_accumulate": [_fp, _fp, _fp, _f, _i, _i, _i, _fp, _fp, _fp, _fp, _fp, _fp, _vp],
     "ctvae_heatmap_u8": [_fp, _i, _i, _i, _f, _f, _i, _i, _i, _i, _i, _i, _fp, _i, _fp, _sz, _vp],
+    "ctvae_latent_accumulate": [_fp, _l, _fp, _l, _i, _i, _fp, _fp, _fp, _fp, _fp, _fp, _vp],
     "ctvae_adam_step": [_fp, _fp, _fp, _fp, _fp, _l, _f, _vp],
     "ctvae_adam_step_clipped": [_fp, _fp, _fp, _fp, _fp, _l, _f, _i, _f, _fp, _fp, _vp],
     "ctvae_adam_mark_members": [_fp, _i, _fp, _i, _vp],

@@ -41,6 +41,12 @@ encoder outputs of the last batch, zeroing their Adam moments (experiment.py, op
 gains ``trainer['codebook']``; a full resume under the key continues the window bit for bit and refuses other ``every`` /
 ``min_count``; ``load_weights_only`` starts a fresh window; a run without the key ignores the entry.  Restarts are refused when
 ``update_parameters`` leaves the codebooks outside the optimizer's slice.
+``exp_params.latent_stats: true`` adds the latent usage of a model with a Gaussian posterior to every validation epoch:
+``val_latent_kl_total`` / ``_active_units`` / ``_collapsed`` / ``_mean_abs_corr`` / ``_gaussian_tc`` / ``_nonfinite`` / ``_rows`` in the
+epoch records and ``metrics_rank0.jsonl``, and ``Latents/latent_stats_<name>_Epoch_<e>.npz`` (per-dimension KL, mean, variance and
+covariance of the posterior means) with ``Latents/corr_<name>_Epoch_<e>.png`` in the log directory (experiment.py,
+latentstats.py); ``python -m ctvae_amd.latent_stats`` does the same for a checkpoint and adds the traversal picture.  Anything but
+a bool, and the key on a model without such a posterior, is a SystemExit that names it.
 """
 import argparse
 import json
@@ -264,6 +270,21 @@ def exp_codebook(config):
     return stats, every, min_count, pool
 
 
+def exp_latent_stats(config) -> bool:
+    """``exp_params.latent_stats`` as a bool (absent: False).  Anything but a bool, and the key on a model without a Gaussian
+    posterior, are a SystemExit that names the key."""
+    from . import latentstats
+    try:
+        on = latentstats.latent_stats_setting(config['exp_params'].get('latent_stats'))
+    except ValueError as e:
+        raise SystemExit(f"exp_params.{e}")
+    name = config['model_params'].get('name')
+    cls = vae_models.get(name)
+    if on and (cls is None or not latentstats.has_gaussian_posterior(cls)):
+        raise SystemExit(f"exp_params.{latentstats.needs_gaussian_posterior(cls, name=repr(name))} (model_params.name)")
+    return on
+
+
 def check_codebook_checkpoint(ckpt, path, every, min_count):
     """Full resume of a run that restarts dead codes: the checkpoint must hold ``trainer['codebook']``, written under this run's
     ``every`` and ``min_count``; otherwise a SystemExit names the key and the path."""
@@ -287,6 +308,7 @@ def main(argv=None):
         config = yaml.safe_load(f)
     ema_decay, ema_warmup, _ = exp_ema(config['exp_params'])
     _, restart_every, restart_min_count, _ = exp_codebook(config)
+    exp_latent_stats(config)                 # refused here, before a device is touched; VAEXperiment reads the key itself
 
     rank =int(os.environ.get("RANK", "0"))
     world = int(os.environ.get("WORLD_SIZE", "1"))

@@ -599,6 +599,24 @@ int ctvae_graph_accumulate(const float* adj, const int32_t* group, const float* 
                            double* adj_sum, int32_t* edge_count, double* mask_sum, int32_t* rows, int32_t* mask_rows,
                            int32_t* skipped, void* stream);
 
+/* Latent usage of the Gaussian models (latentstats.py: LatentStats).  One batch of posterior parameters -- mu and logvar, fp32
+ * [B][L], row r of each starting at mu + r * mu_pitch resp. logvar + r * logvar_pitch (pitches in floats, so the two may be the
+ * column halves of one [B][2L] tensor) -- is ADDED into accumulators (device memory, zero before the first call):
+ *   kl_sum [L] double       sum over rows of 0.5 * (((m*m + s2) - lv) - 1), m = mu, lv = logvar, s2 = exp(lv), all in double
+ *   mu_sum [L] double       sum of m
+ *   sig2_sum [L] double     sum of s2
+ *   cov_sum [L][L] double   sum of m_i * m_j (the whole matrix; it is symmetric to the bit)
+ *   nonfinite [L] int32     elements whose mu or logvar is NaN or +-inf (they still go into the sums)
+ *   rows [1] int32          rows
+ * Every element ends up as if the rows had been added one at a time in ascending row order onto what earlier calls left: one
+ * owner per element, no atomics, so the result is bit-identical however the rows are split into calls and from run to run.  The
+ * product of two fp32 values is exact in double: mu_sum and cov_sum equal a float64 loop on the host bit for bit; kl_sum and
+ * sig2_sum differ from one by the two double exp implementations only.  One launch, no host synchronisation.  L in 1 .. 1024
+ * (cov_sum is L * L doubles); B == 0 is a successful no-op that touches nothing; B < 0, another L, a pitch below L or a NULL
+ * pointer returns -22 and launches nothing. */
+int ctvae_latent_accumulate(const float* mu, long mu_pitch, const float* logvar, long logvar_pitch, int B, int L, double* kl_sum,
+                            double* mu_sum, double* sig2_sum, double* cov_sum, int32_t* nonfinite, int32_t* rows, void* stream);
+
 /* values [M][H][W] f32 (contiguous) as a colour-mapped, tiled sheet (causalgraph.py: heatmap_u8): every value becomes cell x cell
  * pixels of colour table[floor(t*255 + 0.5)] with t = (clamp(v, lo, hi) - lo) / (hi - lo), every operation rounded to f32 on its
  * own (ctvae_image_grid_u8's byte conversion); NaN takes entry 0, +-inf clamp.  table: 256 x RGB bytes in HOST memory, read

@@ -1,0 +1,307 @@
+"""GPU: the latent statistics (``exp_params.latent_stats``) through the training harness, and the tool on a checkpoint:
+latentstats.LatentStats on csrc/latentstat.hip, fed by ``validation_step`` with ``BaseVAE.gaussian_posterior``.
+
+VanillaVAE (latent_dim 128) at B = 4, BetaTCVAE (latent_dim 10) at B = 8, IWAE at B = 4, on ``filler.synthetic_batch`` -- what
+``run.SyntheticData`` hands out.  Two references:
+* the very tensors the harness handed to the statistics (a spy on ``observe``), through ``latent_checks.ref_accumulate``: the sums
+  of mu are bit-identical, so everything derived from them alone is EQUAL; what goes through ``exp`` lies within ``kl_bound``;
+* ``encode()`` of the validation batches, gathered here.  ``forward`` and ``encode`` reach mu / log_var through different launches
+  (the latent node sums the heads' split-K slices itself), so these agree to the project's fp32 parity tolerance, 1e-4 relative
+  -- which is also the bound against ``-val_KLD``, the fp32 loss kernel being the looser side there."""
+import io
+import json
+import os
+import struct
+
+import numpy as np
+import pytest
+import torch
+import yaml
+
+from ctvae_amd import filler
+from tests import helpers as H
+from tests import latent_checks as C
+from tests.test_grad_accum_gpu import B, EXP, _assert_same, _batches, _snapshot, _vanilla
+
+pytestmark = pytest.mark.gpu
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+RTOL = 1e-4
+SCALARS = ("kl_total", "active_units", "collapsed", "mean_abs_corr", "gaussian_tc", "nonfinite", "rows")
+
+
+@pytest.fixture(scope="module")
+def dev():
+    if not torch.cuda.is_available():
+        pytest.skip("needs a GPU")
+    return torch.device("cuda", 0)
+
+
+def _epochs(batches, per_epoch):
+    calls = [0]
+
+    def train():
+        lo = calls[0] * per_epoch
+        calls[0] += 1
+        return iter(batches[lo:lo + per_epoch])
+    return train
+
+
+def _spy(exp, seen):
+    inner = exp.val_latents.observe
+
+    def observe(mu, log_var):
+        seen.append((mu.detach().clone(), log_var.detach().clone(), tuple(mu.stride())))
+        inner(mu, log_var)
+    exp.val_latents.observe = observe
+
+
+def _ref_of(pairs, L):
+    st = C.new_state(L)
+    for mu, lv in pairs:
+        C.ref_accumulate(st, mu.float().cpu().numpy(), lv.float().cpu().numpy())
+    return st
+
+
+def _encoded(model, val):
+    """(mu, log_var) of every validation batch by ``encode()``, in eval mode, with the weights the model holds now."""
+    from ctvae_amd.metrics import _eval_mode
+    with _eval_mode(model):
+        return [tuple(t.clone() for t in model.encode(b[0])[:2]) for b in val]
+
+
+def _png_size(path):
+    data = open(path, "rb").read()
+    assert data[:8] == b"\x89PNG\r\n\x1a\n" and data[12:16] == b"IHDR"
+    return struct.unpack(">II", data[16:24])          # (width, height)
+
+
+def _lines(log, key):
+    return [r for r in map(json.loads, log.getvalue().splitlines()) if key in r]
+
+
+ALWAYS = {"val_latent_" + k for k in ("kl_total", "active_units", "collapsed", "nonfinite", "rows")}
+
+
+def _assert_record_is(rec, res, exact=True):
+    """The record's scalars against a ``summarize`` result.  ``exact``: from bit-identical mu sums, so the same keys and equal
+    values; the KL lies within the exp bound, a few 2^-53 of sums of O(1) terms, which 1e-12 relative covers with digits to
+    spare.  Otherwise the fp32 parity tolerance on the KL and the mean correlation; the counts of active and collapsed units
+    sit on thresholds and ``gaussian_tc`` amplifies an input difference by the covariance's condition number, so those three
+    are compared only where the inputs are the same bits."""
+    from ctvae_amd import latentstats as S
+    want = S.record(res)
+    assert ALWAYS <= set(rec) and set(rec) <= {"val_latent_" + k for k in SCALARS}
+    if exact:
+        assert sorted(rec) == sorted(want), (sorted(rec), sorted(want))
+    for k in ("val_latent_rows", "val_latent_nonfinite"):
+        assert rec[k] == want[k], (k, rec[k], want[k])
+    assert abs(rec["val_latent_kl_total"] - want["val_latent_kl_total"]) <= (1e-12 if exact else RTOL) * want["val_latent_kl_total"]
+    if exact:
+        for k in set(want) - {"val_latent_kl_total"}:
+            assert rec[k] == want[k], (k, rec[k], want[k])
+    elif "val_latent_mean_abs_corr" in rec and "val_latent_mean_abs_corr" in want:
+        assert abs(rec["val_latent_mean_abs_corr"] - want["val_latent_mean_abs_corr"]) <= RTOL
+
+
+# ---- 1. VanillaVAE: the record, the log, the files -----------------------------------------------------------
+def test_vanilla_record_log_and_files(dev, tmp_path):
+    from ctvae_amd import imagegrid, latentstats as S
+    from ctvae_amd.experiment import VAEXperiment
+    train, val = _batches(dev, 6), _batches(dev, 3, seed=4900)
+    log, seen = io.StringIO(), []
+    exp = VAEXperiment(_vanilla(dev), dict(EXP, latent_stats=True), log_file=log, sample_dir=str(tmp_path), run_name="run")
+    _spy(exp, seen)
+    hist = exp.fit(_epochs(train, 3), lambda: iter(val), max_epochs=2)
+    assert len(seen) == 6 and all(tuple(mu.shape) == (B, 128) for mu, _, _ in seen)
+    assert seen[0][2] == (256, 1), "mu is handed over as a column half of the [B, 2L] heads tensor, not as a copy"
+    rec = {k: v for k, v in hist[1].items() if k.startswith("val_latent_")}
+    print(rec, "val_KLD", hist[1]["val_KLD"])
+    assert ALWAYS <= set(rec) and rec["val_latent_rows"] == 3 * B and rec["val_latent_nonfinite"] == 0
+    assert "val_latent_gaussian_tc" not in rec               # 12 rows cannot give 128 dimensions a regular covariance
+    lines = _lines(log, "val_latent_kl_total")
+    assert len(lines) == 2 and {k: v for k, v in lines[1].items() if k != "step"} == rec and lines[1]["step"] == 6
+    # equal-sized validation batches: the mean of the batches' KLD is the KL per row, with the reference's flipped sign
+    assert abs(rec["val_latent_kl_total"] + hist[1]["val_KLD"]) <= RTOL * abs(hist[1]["val_KLD"])
+    # against the tensors that were handed over (epoch 1: the last three), and against encode() with the final weights
+    ref = S.summarize(_ref_of([p[:2] for p in seen[3:]], 128))
+    _assert_record_is(rec, ref, exact=True)
+    enc = S.summarize(_ref_of(_encoded(exp.model, val), 128))
+    _assert_record_is(rec, enc, exact=False)
+    for e in (0, 1):
+        npz = np.load(tmp_path / "Latents" / f"latent_stats_run_Epoch_{e}.npz")
+        assert sorted(npz.files) == ["cov", "kl", "mu_mean", "mu_var", "rows", "sigma2_mean"]
+        assert npz["cov"].shape == (128, 128) and npz["kl"].shape == (128,) and npz["rows"].tolist() == [3 * B]
+        w, h = _png_size(tmp_path / "Latents" / f"corr_run_Epoch_{e}.png")
+        _, _, Hg, Wg = imagegrid.grid_geometry(1, 128 * 4, 128 * 4, 8, 2)
+        assert (w, h) == (Wg, Hg)
+    npz = np.load(tmp_path / "Latents" / "latent_stats_run_Epoch_1.npz")
+    assert np.array_equal(npz["cov"], ref["cov"]) and np.array_equal(npz["mu_mean"], ref["mu_mean"])
+    scale = np.abs(enc["cov"]).max()
+    assert np.abs(npz["cov"] - enc["cov"]).max() <= RTOL * scale and np.abs(npz["kl"] - enc["kl"]).max() <= RTOL * enc["kl"].max()
+    assert abs(npz["kl"].sum() - rec["val_latent_kl_total"]) <= 1e-12 * rec["val_latent_kl_total"]
+
+
+# ---- 2. training does not notice ---------------------------------------------------------------------------
+@pytest.mark.parametrize("hipgraph", [True, False])
+def test_training_is_bit_for_bit_the_same(dev, tmp_path, hipgraph):
+    from ctvae_amd.experiment import VAEXperiment
+    train, val = _batches(dev, 6), _batches(dev, 2, seed=4900)
+    finals, rngs = {}, {}
+    for name, extra in (("plain", {}), ("stats", {"latent_stats": True})):
+        log = io.StringIO()
+        exp = VAEXperiment(_vanilla(dev), dict(EXP, hipgraph=hipgraph, **extra), log_file=log, sample_dir=str(tmp_path / name),
+                           run_name="run")
+        torch.manual_seed(5)
+        hist = exp.fit(_epochs(train, 3), lambda: iter(val), max_epochs=2)
+        assert exp.global_step == 6
+        finals[name] = _snapshot(exp)
+        rngs[name] = (exp.model._rng_state.clone(), torch.get_rng_state(), torch.cuda.get_rng_state(dev))
+        if name == "plain":            # no buffer, no file, no key
+            assert exp.val_latents is None and not (tmp_path / name).exists()
+            assert not any("latent" in k for k in hist[1]) and not _lines(log, "val_latent_rows")
+        else:
+            assert hist[1]["val_latent_rows"] == 2 * B and (tmp_path / name / "Latents").is_dir()
+    _assert_same(finals["plain"], finals["stats"], "with and without latent_stats")
+    for a, b in zip(rngs["plain"], rngs["stats"]):
+        assert torch.equal(a, b)
+
+
+# ---- 3. BetaTCVAE ------------------------------------------------------------------------------------------
+def _betatc(dev):
+    from ctvae_amd.models import vae_models
+    m = vae_models["BetaTCVAE"](**H.BETATC_CFG)
+    m.load_state_dict(filler.fill_state(H.betatc_specs(), 1401))
+    return m.to(dev).train()
+
+
+def test_betatc_statistics_and_traversal(dev, tmp_path):
+    from ctvae_amd import latentstats as S
+    from ctvae_amd.experiment import VAEXperiment
+    bs = 8
+    mk = lambda n, seed: [(filler.synthetic_batch(seed + i, bs)[0].to(dev), torch.zeros(bs, device=dev)) for i in range(n)]
+    train, val = mk(2, 5100), mk(2, 5900)
+    log, seen = io.StringIO(), []
+    exp = VAEXperiment(_betatc(dev), dict(EXP, latent_stats=True), log_file=log)       # no sample_dir: numbers only
+    _spy(exp, seen)
+    hist = exp.fit(lambda: iter(train), lambda: iter(val), max_epochs=1)
+    rec = {k: v for k, v in hist[0].items() if k.startswith("val_latent_")}
+    print(rec)
+    assert rec["val_latent_rows"] == 2 * bs and len(seen) == 2 and tuple(seen[0][0].shape) == (bs, 10)
+    _assert_record_is(rec, S.summarize(_ref_of([p[:2] for p in seen], 10)), exact=True)
+    _assert_record_is(rec, S.summarize(_ref_of(_encoded(exp.model, val), 10)), exact=False)
+    assert _lines(log, "val_latent_rows")[0]["val_latent_rows"] == 2 * bs
+    # the traversal: 3 dimensions x 100 values = 300 rows, decoded in two calls; nothing of the run moves
+    model = exp.model
+    calls, inner = [], model.decode
+    model.decode = lambda z: (calls.append(z.size(0)), inner(z))[1]
+    before = (model.training, torch.get_rng_state(), torch.cuda.get_rng_state(dev), model.flat_params.clone())
+    dims = S.rank_dims(S.summarize(_ref_of([p[:2] for p in seen], 10))["kl"], 3)
+    shape = S.save_traversal(model, val[0][0][1], dims, np.linspace(-3, 3, 100), str(tmp_path / "t.png"))
+    del model.decode
+    assert shape == (3, 100) and calls == [256, 44]
+    assert _png_size(tmp_path / "t.png") == (100 * 66 + 2, 3 * 66 + 2)
+    assert model.training is before[0] and torch.equal(torch.get_rng_state(), before[1])
+    assert torch.equal(torch.cuda.get_rng_state(dev), before[2]) and torch.equal(model.flat_params, before[3])
+
+
+# ---- 4. ema_eval -------------------------------------------------------------------------------------------
+def test_ema_eval_describes_the_averaged_weights(dev):
+    from ctvae_amd import latentstats as S
+    from ctvae_amd.experiment import VAEXperiment
+    train, val = _batches(dev, 3), _batches(dev, 2, seed=4900)
+    got, want = {}, {}
+    for ema_eval in (True, False):
+        extra = {} if ema_eval else {"ema_eval": False}
+        exp = VAEXperiment(_vanilla(dev), dict(EXP, LR=1e-2, hipgraph=False, ema_decay=0.5, latent_stats=True, **extra))
+        exp.fit(lambda: iter(train), None, max_epochs=1)
+        got[ema_eval] = exp.fit(lambda: iter([]), lambda: iter(val), max_epochs=1)[0]["val_latent_kl_total"]
+        with exp.ema_weights() if ema_eval else torch.no_grad():
+            want[ema_eval] = S.summarize(_ref_of(_encoded(exp.model, val), 128))["kl_total"]
+        assert not exp.ema.swapped
+    print(got, want)
+    assert abs(want[True] - want[False]) > 10 * RTOL * want[False], "the averaged and the live weights give the same KL"
+    for k in (True, False):
+        assert abs(got[k] - want[k]) <= RTOL * want[k]
+
+
+# ---- 5. IWAE: [B, L] statistics ----------------------------------------------------------------------------
+def test_iwae_counts_images_not_samples(dev):
+    from ctvae_amd import latentstats as S
+    from ctvae_amd.experiment import VAEXperiment
+    from ctvae_amd.models import vae_models
+    name, cfg, lead = H.IW_CASES["iwae"]
+    m = vae_models[name](**cfg)
+    m.load_state_dict(filler.fill_state(H.vanilla_specs(), 1266))
+    m = m.to(dev).train()
+    val = _batches(dev, 2, seed=4900)
+    seen = []
+    exp = VAEXperiment(m, dict(EXP, latent_stats=True))
+    _spy(exp, seen)
+    rec = exp.fit(lambda: iter([]), lambda: iter(val), max_epochs=1)[0]
+    assert rec["val_latent_rows"] == 2 * B and all(tuple(mu.shape) == (B, 128) for mu, _, _ in seen) and lead == (5,)
+    _assert_record_is({k: v for k, v in rec.items() if k.startswith("val_latent_")},
+                      S.summarize(_ref_of(_encoded(m, val), 128)), exact=False)
+
+
+# ---- 6. the tool -------------------------------------------------------------------------------------------
+def _tool_cfg(tmp_path, name, model=None):
+    cfg = yaml.safe_load(open(os.path.join(ROOT, "configs", name)))
+    cfg["logging_params"]["save_dir"] = str(tmp_path / "logs")
+    cfg["data_params"]["train_batch_size"] = cfg["data_params"]["val_batch_size"] = 4
+    cfg["model_params"].update(model or {})
+    p = tmp_path / name
+    p.write_text(yaml.safe_dump(cfg))
+    return str(p), cfg
+
+
+def _save(model, path, ema=None):
+    state = {"state_dict": {"model." + k: v.detach().cpu().contiguous() for k, v in model.state_dict().items()}, "epoch": 0}
+    if ema is not None:
+        state["ema_state_dict"] = {"model." + k: v for k, v in ema.items()}
+    torch.save(state, path)
+
+
+def test_tool_writes_its_four_files(dev, tmp_path):
+    from ctvae_amd import latent_stats
+    from ctvae_amd.experiment import VAEXperiment
+    exp = VAEXperiment(_vanilla(dev), dict(EXP, LR=1e-2, hipgraph=False, ema_decay=0.5))
+    exp.fit(lambda: iter(_batches(dev, 3)), None, max_epochs=1)
+    plain, both = tmp_path / "plain.ckpt", tmp_path / "both.ckpt"
+    _save(exp.model, plain)
+    _save(exp.model, both, ema=exp.ema_model_state_dict())
+    cfg_path, cfg = _tool_cfg(tmp_path, "vae.yaml")
+    with pytest.raises(SystemExit, match="--ema.*plain.ckpt holds no ema_state_dict"):
+        latent_stats.main(["-c", cfg_path, "--checkpoint", str(plain), "--ema"])
+    assert not (tmp_path / "logs").exists()
+    out = tmp_path / "out"
+    summary = latent_stats.main(["-c", cfg_path, "--checkpoint", str(both), "--out", str(out), "--traverse", "3", "--steps", "5"])
+    assert sorted(os.listdir(out)) == sorted(latent_stats.FILES)
+    on_disk = json.load(open(out / "latent_stats.json"))
+    assert on_disk["rows"] == 8 * 4 and len(on_disk["kl"]) == 128 and sorted(on_disk["ranked_dims"]) == list(range(128))
+    kl = np.asarray(on_disk["kl"])
+    assert all(kl[a] >= kl[b] for a, b in zip(on_disk["ranked_dims"][:-1], on_disk["ranked_dims"][1:]))
+    assert summary["traversal_dims"] == on_disk["ranked_dims"][:3] and abs(on_disk["kl_total"] - kl.sum()) <= 1e-12 * kl.sum()
+    assert _png_size(out / "traversal.png") == (5 * 66 + 2, 3 * 66 + 2)
+    npz = np.load(out / "latent_stats.npz")
+    assert np.array_equal(npz["kl"], kl) and npz["cov"].shape == (128, 128) and npz["rows"].tolist() == [32]
+    assert _png_size(out / "latent_corr.png")[0] == 128 * 4 + 4
+    # default output directory, the averaged weights, no traversal: three files and other numbers
+    ema = latent_stats.main(["-c", cfg_path, "--checkpoint", str(both), "--ema", "--traverse", "0"])
+    d = tmp_path / "logs" / cfg["logging_params"]["name"] / "latent_stats"
+    assert sorted(os.listdir(d)) == sorted(latent_stats.FILES[:3]) and ema["kl_total"] != summary["kl_total"]
+
+
+def test_tool_refuses_a_traversal_of_a_conditional_model_after_the_statistics(dev, tmp_path):
+    from ctvae_amd import latent_stats
+    from ctvae_amd.models import vae_models
+    cfg_path, cfg = _tool_cfg(tmp_path, "cvae.yaml", model={"num_classes": 1, "latent_dim": 16})
+    torch.manual_seed(9)
+    m = vae_models["ConditionalVAE"](**cfg["model_params"])
+    ckpt = tmp_path / "cvae.ckpt"
+    _save(m, ckpt)
+    out = tmp_path / "out"
+    with pytest.raises(SystemExit, match="--traverse.*ConditionalVAE"):
+        latent_stats.main(["-c", cfg_path, "--checkpoint", str(ckpt), "--out", str(out), "--traverse", "2"])
+    assert sorted(os.listdir(out)) == sorted(latent_stats.FILES[:3])
+    on_disk = json.load(open(out / "latent_stats.json"))
+    assert on_disk["rows"] == 32 and len(on_disk["kl"]) == 16 and on_disk["nonfinite"] == 0
