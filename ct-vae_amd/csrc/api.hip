@@ -200,6 +200,9 @@ int launch_heatmap_u8(const float* values, int M, int H, int W, float lo, float 
                       int pad_b, const uint8_t* table, int scanlines, uint8_t* out, size_t out_bytes, hipStream_t st);
 int launch_latent_accumulate(const float* mu, long mu_pitch, const float* logvar, long lv_pitch, int B, int L, double* kl_sum,
                              double* mu_sum, double* sig2_sum, double* cov_sum, int* nonfinite, int* rows, hipStream_t st);
+size_t freebits_workspace_bytes(int L);
+int launch_freebits_kl(const float* mu, long mu_pitch, const float* lv, long lv_pitch, int B, int L, const float* w_dev, float scale,
+                       float lambda, float* out4, float* g_mu, float* g_lv, float* ws, size_t ws_bytes, hipStream_t st);
 int launch_loss_forward(const float* r, const float* x, long n, const float* mu, long mu_rs, const float* lv, long lv_rs,
                         int B, int L, float M_N, const float* extra, float* out4, float* ws, size_t ws_bytes,
                         hipStream_t st, float logcosh_alpha, float* g_r = nullptr, float* g_mu = nullptr, float* g_lv = nullptr,
@@ -1108,6 +1111,15 @@ int ctvae_latent_accumulate(const float* mu, long mu_pitch, const float* logvar,
                             double* mu_sum, double* sig2_sum, double* cov_sum, int32_t* nonfinite, int32_t* rows, void* stream) {
   return launch_latent_accumulate(mu, mu_pitch, logvar, logvar_pitch, B, L, kl_sum, mu_sum, sig2_sum, cov_sum, nonfinite, rows,
                                   (hipStream_t)stream);
+}
+
+size_t ctvae_freebits_workspace_bytes(int L) { return freebits_workspace_bytes(L); }
+
+int ctvae_freebits_kl_forward_grad(const float* mu, long mu_pitch, const float* logvar, long logvar_pitch, int B, int L,
+                                   const float* w_dev, float scale, float free_bits, float* out, float* g_mu, float* g_logvar,
+                                   float* ws, size_t ws_bytes, void* stream) {
+  return launch_freebits_kl(mu, mu_pitch, logvar, logvar_pitch, B, L, w_dev, scale, free_bits, out, g_mu, g_logvar, ws, ws_bytes,
+                            (hipStream_t)stream);
 }
 
 size_t ctvae_adam_state_floats(void) { return adam_state_floats(); }

@@ -99,6 +99,19 @@ out), and with a ``sample_dir`` writes ``Latents/latent_stats_<name>_Epoch_<e>.n
 Under ``ema_eval`` the numbers describe the averaged weights; with several ranks they are rank 0's own rows.  It draws nothing and
 writes no model state, so training is bit for bit the same with and without it.  Refused when the experiment is built: the key
 on a model whose hook returns None.  Without the key there is no buffer, no launch, no file and no log key.
+
+``exp_params.kld_schedule`` (a mapping: linear warm-up or cyclical annealing of the KL weight) and ``exp_params.kld_free_bits`` (a
+float >= 0, nats per latent dimension): ``klcontrol.KLControl`` (its module docstring has the definitions), on the models whose
+training loss is recon + c * M_N * KL.  The run owns one persistent 1-element device tensor; ``write_kl_weight()`` puts
+w(``global_step``) into it in front of every training step -- eagerly, also in front of a replay, one fill and only when the value
+changed -- and the step hands ``loss_function`` ``M_N=<that tensor>`` and ``free_bits=lambda``: the loss launch
+(``kernels.FreeBitsKL``) reads the weight from device memory, so a captured step follows the schedule (a by-value ``M_N`` is
+frozen at capture).  Every micro-batch of an accumulation window uses the window's weight; every rank computes the same weight
+from ``global_step``, the batch mean under the floor is over the rank's own rows, and no collective is added.  Training records
+gain ``kld_weight`` (the host's value, no copy), ``KLD_free_bits`` and ``KLD_floored_dims``; validation (``M_N = 1.0``) is untouched.
+``state_dict()`` carries ``"kl": {schedule, free_bits}``; a full resume under other values is refused by name, the weight itself
+needs no state.  Refused when the experiment is built: either key on another model.  Without the keys there is no buffer, no
+launch, no log key and no entry.
 """
 import contextlib
 import json
@@ -111,6 +124,7 @@ import torch
 from . import imagegrid
 from . import kernels as K
 from .ddp import GradBucketAllReduce
+from .klcontrol import KLControl, kl_settings, needs_served_model, serves as kl_serves
 from .latentstats import (LATENT_DIR, LatentStats, has_gaussian_posterior, latent_stats_setting, needs_gaussian_posterior,
                           record as latent_record, write_files as write_latent_files)
 from .metrics import _eval_mode as eval_mode
@@ -162,7 +176,7 @@ class _GraphedTrainStep:
         opts = {**self.static, **self.const}
         labels = opts.pop("labels", None)         # ConditionalVAE reads them (cvae.py:123); a static buffer like every tensor option
         results = exp.forward(self.x, labels=labels, **opts)
-        losses = exp.model.loss_function(*results, M_N=exp.params['kld_weight'], optimizer_idx=0, batch_idx=0)
+        losses = exp.model.loss_function(*results, **exp.loss_options(), optimizer_idx=0, batch_idx=0)
         K.backward(losses['loss'])
         # inside the capture: the fills of unwritten blocks AND the copies of autograd-produced gradients (CT layer: a_dense, mask,
         # positional encoding, the GATv2 vectors) into the flat buffer belong to the replayed step.  Left to ddp.all_reduce() /
@@ -195,6 +209,7 @@ class _GraphedTrainStep:
         K.stage_batch(self.x, real_img)
         for k, t in self.static.items():
             t.copy_(kwargs[k], non_blocking=True)
+        exp.write_kl_weight()              # eager, in front of the capture and of every replay: the body reads the device scalar
         if self.graph is None and self.seen >= self.WARM:
             torch.cuda.synchronize()
             g = torch.cuda.CUDAGraph()
@@ -298,6 +313,15 @@ class VAEXperiment:
                 raise ValueError(needs_gaussian_posterior(vae_model))
             if self._rank0():
                 self.val_latents = LatentStats(vae_model.latent_dim, next(vae_model.parameters()).device)
+        # KL weight schedule / free bits (klcontrol.KLControl): on every rank, the same weight from global_step
+        schedule, free_bits = kl_settings(params)
+        self.kl = None
+        if schedule is not None or free_bits is not None:
+            if not kl_serves(vae_model):
+                raise ValueError(needs_served_model("kld_schedule" if schedule is not None else "kld_free_bits",
+                                                    type(vae_model).__name__ + (f" with loss_type {vae_model.loss_type!r}"
+                                                                                if hasattr(vae_model, "loss_type") else "")))
+            self.kl = KLControl(schedule, free_bits, params['kld_weight'], next(vae_model.parameters()).device)
 
     def forward(self, input, **kwargs):
         return self.model(input, **kwargs)
@@ -312,11 +336,25 @@ class VAEXperiment:
         real_img, labels, kwargs = self._unpack(batch)
         self.curr_device = real_img.device
         results = self.forward(real_img, labels=labels, **kwargs)
-        train_loss = self.model.loss_function(*results, M_N=self.params['kld_weight'], optimizer_idx=optimizer_idx,
-                                              batch_idx=batch_idx)
+        self.write_kl_weight()
+        train_loss = self.model.loss_function(*results, **self.loss_options(), optimizer_idx=optimizer_idx, batch_idx=batch_idx)
         if self._log_train:
             self.log_all(train_loss, batch_size=real_img.size(0), validation=False)
         return train_loss['loss']
+
+    # -- KL weight schedule and free bits (exp_params.kld_schedule / kld_free_bits; klcontrol.KLControl) --------------
+    def write_kl_weight(self):
+        """Called eagerly in front of every training step, also in front of a captured step's replay: w(``global_step``) into the
+        device scalar, one fill and only when the value differs from the last one written.  Nothing without the keys."""
+        if self.kl is not None:
+            self.kl.write(self.global_step)
+
+    def loss_options(self):
+        """What a training step hands ``loss_function`` for the KL weight: the float ``kld_weight``, or under the keys the device
+        scalar and the floor."""
+        if self.kl is None:
+            return {"M_N": self.params['kld_weight']}
+        return {"M_N": self.kl.tensor, "free_bits": self.kl.floor}
 
     def validation_step(self, batch, batch_idx, optimizer_idx=0):
         real_img, labels, kwargs = self._unpack(batch)
@@ -425,6 +463,8 @@ class VAEXperiment:
         keys = sorted(scal)
         vals = torch.stack([scal[k].detach().float().reshape(()) for k in keys]).cpu().tolist() if keys else []
         rec = dict(zip(keys, vals))
+        if self.kl is not None and not validation:
+            rec["kld_weight"] = self.kl.weight(self.global_step)      # the host's value of the step that ran: no copy
         rec["step"] = self.global_step
         if self.log_file is not None:
             self.log_file.write(json.dumps(rec) + "\n")
@@ -475,10 +515,16 @@ class VAEXperiment:
                               "pool": int(cb.pool.size(0)), "counts": cb.read()[0].clone(), "ordinal": int(self.codebook_ordinal),
                               "restarted": int(self.codebook_restarted),
                               "valid_rows": -1 if cb.valid_rows is None else int(cb.valid_rows)}
+        if self.kl is not None:            # (the weight itself is a function of global_step)
+            sd["kl"] = self.kl.state_dict()
         return sd
 
     def load_state_dict(self, sd):
         """Inverse of state_dict(), in place (captured steps, if any, keep pointing at the same buffers)."""
+        if self.kl is not None:            # (a run without the keys ignores the entry)
+            why = self.kl.mismatch(sd.get("kl"))
+            if why is not None:
+                raise RuntimeError(f"{why} (exp_params.kld_schedule / kld_free_bits differ)")
         o = sd["optimizer"]
         if [int(self.optimizer.slice.start or 0), int(self.optimizer.slice.stop)] != [int(v) for v in o["slice"]]:
             raise RuntimeError("checkpoint optimizes another parameter range than this run (update_parameters differs)")

@@ -1291,6 +1291,62 @@ class VAELoss(Function):
         return g_r, None, g_mu, g_lv, g_extra, None, None
 
 
+FREE_BITS_MAX_L = 1024                  # what ctvae_freebits_kl_forward_grad covers
+
+
+class FreeBitsKL(Function):
+    """out = [w * sum_d f_d, sum_d m_d, sum_d f_d, #floored]: the Gaussian KL term with free bits (Kingma et al. 2016, eq. 15) and
+    a weight read from device memory (csrc/klfloor.hip).  m_d is the batch mean of dimension d's KL, f_d = m_d
+    where m_d > free_bits (or is not finite), else free_bits; w = scale * w_dev[0].  ``w_dev`` is a 1-element
+    fp32 device tensor whose ADDRESS the launch takes: a captured launch reads the value it holds at replay.  Only out[0] carries
+    gradient, to mu and log_var; the gradients for a unit upstream gradient come out of the forward launch."""
+
+    @staticmethod
+    def forward(ctx, mu, log_var, w_dev, scale, free_bits):
+        _req_cuda(mu, log_var, w_dev)
+        if mu.dim() != 2 or mu.shape != log_var.shape or mu.dtype != torch.float32 or log_var.dtype != torch.float32:
+            raise RuntimeError(f"free_bits_kl: mu / log_var must be fp32 [B, L] of one shape, got {tuple(mu.shape)} {mu.dtype}, "
+                               f"{tuple(log_var.shape)} {log_var.dtype}")
+        if w_dev.dtype != torch.float32 or w_dev.numel() != 1:
+            raise RuntimeError("free_bits_kl: the weight is one fp32 element on the device")
+        B, L = mu.shape
+        if B < 1 or not 1 <= L <= FREE_BITS_MAX_L:
+            raise RuntimeError(f"free_bits_kl: B >= 1 and 1 <= L <= {FREE_BITS_MAX_L}, got B = {B}, L = {L}")
+        mu_, mrs = _rows(mu)
+        lv_, lrs = _rows(log_var)
+        out = torch.empty(4, dtype=torch.float32, device=mu.device)
+        want = ctx.needs_input_grad[0] or ctx.needs_input_grad[1]
+        pre = (torch.empty((B, L), dtype=torch.float32, device=mu.device),
+               torch.empty((B, L), dtype=torch.float32, device=mu.device)) if want else None
+        ws = native.workspace(mu.device)
+        native.call("ctvae_freebits_kl_forward_grad", mu_.data_ptr(), mrs, lv_.data_ptr(), lrs, B, L, w_dev.data_ptr(), float(scale),
+                    float(free_bits), out.data_ptr(), native.ptr(pre[0]) if want else None, native.ptr(pre[1]) if want else None,
+                    ws.data_ptr(), ws.numel() * 4)
+        ctx.pre = pre
+        return _scalar_outputs(ctx, out)
+
+    @staticmethod
+    def backward(ctx, g, *_unused):
+        if g is None or ctx.pre is None:
+            return (None,) * 5
+        g_mu, g_lv = ctx.pre
+        if not _is_cached_root(g):                    # the rare path: an upstream gradient other than kernels.backward's one
+            g_mu, g_lv = g_mu * g, g_lv * g
+        return g_mu, g_lv, None, None, None
+
+
+def free_bits_term(mu, log_var, kwargs, scale=1.0):
+    """The KL side of a served model's ``loss_function`` under ``kld_schedule`` / ``kld_free_bits``: FreeBitsKL's four scalars
+    when ``kwargs['M_N']`` is a device tensor or ``kwargs`` has ``free_bits``; None for a float ``M_N`` alone (the caller then runs
+    exactly what it ran before).  scale: the model's host constant in front of M_N * KL."""
+    M_N, has_floor = kwargs['M_N'], 'free_bits' in kwargs
+    if not torch.is_tensor(M_N):
+        if not has_floor:
+            return None
+        M_N = torch.full((1,), float(M_N), dtype=torch.float32, device=mu.device)
+    return FreeBitsKL.apply(mu, log_var, M_N, scale, kwargs['free_bits'] if has_floor else 0.0)
+
+
 class GumbelSoftmax(Function):
     """s = softmax((z + g)/temp, dim=-1), g = -log(-log(u + eps) + eps): CategoricalVAE.reparameterize
     (cat_vae.py:118-132) with the uniform draws injectable.  z, u: [..., Q]."""

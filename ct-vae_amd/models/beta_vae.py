@@ -32,9 +32,15 @@ class BetaVAE(VanillaVAE):
         kld_weight = kwargs['M_N']
         r, x = K.to_nhwc(recons), self._cached_nhwc(input)
         if self.loss_type == 'H':
+            kl = K.free_bits_term(mu, log_var, kwargs, scale=self.beta)      # kld_schedule / kld_free_bits (klcontrol.py)
+            if kl is not None:
+                out = K.VAELoss.apply(r, x, None, None, kl[0].reshape(1), 0.0)
+                return {'loss': out[0], 'Reconstruction_Loss': out[1], 'KLD': kl[1], 'KLD_free_bits': kl[2], 'KLD_floored_dims': kl[3]}
             out = K.VAELoss.apply(r, x, mu, log_var, None, self.beta * kld_weight)
             return {'loss': out[0], 'Reconstruction_Loss': out[1], 'KLD': out[2]}
         if self.loss_type == 'B':
+            if torch.is_tensor(kld_weight) or 'free_bits' in kwargs:
+                raise ValueError("BetaVAE loss_type 'B' is not served by kld_schedule / kld_free_bits (klcontrol.py)")
             # |kld - C| needs the sign of a device value: the loss kernel runs once for the reconstruction term (weight 0
             # on the KL) and once for the KL term alone (reconstruction detached), the scalar glue stays on the device
             mse = K.VAELoss.apply(r, x, mu, log_var, None, 0.0)

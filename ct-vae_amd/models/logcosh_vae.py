@@ -19,6 +19,12 @@ class LogCoshVAE(VanillaVAE):
 
     def loss_function(self, *args, **kwargs) -> dict:
         recons, input, mu, log_var = args[0], args[1], args[2], args[3]
+        kl = K.free_bits_term(mu, log_var, kwargs, scale=self.beta)          # kld_schedule / kld_free_bits (klcontrol.py)
+        if kl is not None:
+            # the log-cosh launch pair takes no extra term: the reconstruction term alone (mu = NULL), one add for the sum
+            out = K.VAELoss.apply(K.to_nhwc(recons), self._cached_nhwc(input), None, None, None, 0.0, float(self.alpha))
+            return {'loss': out[0] + kl[0], 'Reconstruction_Loss': out[1], 'KLD': -kl[1], 'KLD_free_bits': kl[2],
+                    'KLD_floored_dims': kl[3]}
         out = K.VAELoss.apply(K.to_nhwc(recons), self._cached_nhwc(input), mu, log_var, None, self.beta * kwargs['M_N'],
                               float(self.alpha))
         return {'loss': out[0], 'Reconstruction_Loss': out[1], 'KLD': out[3]}

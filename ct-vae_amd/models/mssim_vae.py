@@ -25,6 +25,10 @@ class MSSIMVAE(VanillaVAE):
         recons, input, mu, log_var = args[0], args[1], args[2], args[3]
         kld_weight = kwargs['M_N']
         recons_loss = K.MSSIMLoss.apply(K.to_nhwc(recons), self._cached_nhwc(input))
+        kl = K.free_bits_term(mu, log_var, kwargs)          # kld_schedule / kld_free_bits (klcontrol.py); None: a float M_N alone
+        if kl is not None:
+            return {'loss': recons_loss + kl[0], 'Reconstruction_Loss': recons_loss.detach(), 'KLD': -kl[1], 'KLD_free_bits': kl[2],
+                    'KLD_floored_dims': kl[3]}
         kld = K.GaussKL.apply(mu, log_var)
         loss = recons_loss + kld_weight * kld
         return {'loss': loss, 'Reconstruction_Loss': recons_loss.detach(), 'KLD': -kld.detach()}

@@ -163,6 +163,11 @@ class VanillaVAE(BaseVAE):
         """MSE + M_N*KL (vanilla_vae.py:124-146); 'KLD' carries the reference's flipped sign."""
         recons, input, mu, log_var = args[0], args[1], args[2], args[3]
         kld_weight = kwargs['M_N']
+        kl = K.free_bits_term(mu, log_var, kwargs)          # kld_schedule / kld_free_bits (klcontrol.py); None: a float M_N alone
+        if kl is not None:
+            out = K.VAELoss.apply(K.to_nhwc(recons), self._cached_nhwc(input), None, None, kl[0].reshape(1), 0.0)
+            return {'loss': out[0], 'Reconstruction_Loss': out[1].detach(), 'KLD': -kl[1], 'KLD_free_bits': kl[2],
+                    'KLD_floored_dims': kl[3]}
         out = K.VAELoss.apply(K.to_nhwc(recons), self._cached_nhwc(input), mu, log_var, None, kld_weight)
         return {'loss': out[0], 'Reconstruction_Loss': out[1].detach(), 'KLD': out[3].detach()}
 

@@ -112,6 +112,7 @@ SIGNATURES = {
     "ctvae_graph_accumulate": [_fp, _fp, _fp, _f, _i, _i, _i, _fp, _fp, _fp, _fp, _fp, _fp, _vp],
     "ctvae_heatmap_u8": [_fp, _i, _i, _i, _f, _f, _i, _i, _i, _i, _i, _i, _fp, _i, _fp, _sz, _vp],
     "ctvae_latent_accumulate": [_fp, _l, _fp, _l, _i, _i, _fp, _fp, _fp, _fp, _fp, _fp, _vp],
+    "ctvae_freebits_kl_forward_grad": [_fp, _l, _fp, _l, _i, _i, _fp, _f, _f, _fp, _fp, _fp, _fp, _sz, _vp],
     "ctvae_adam_step": [_fp, _fp, _fp, _fp, _fp, _l, _f, _vp],
     "ctvae_adam_step_clipped": [_fp, _fp, _fp, _fp, _fp, _l, _f, _i, _f, _fp, _fp, _vp],
     "ctvae_adam_mark_members": [_fp, _i, _fp, _i, _vp],
@@ -156,6 +157,7 @@ _RESTYPES = {
     "ctvae_vq_usage_pass_indices": _c.c_size_t,
     "ctvae_grad_segment_chunk_floats": _c.c_size_t,
     "ctvae_mssim_part_floats": _c.c_size_t,
+    "ctvae_freebits_workspace_bytes": _c.c_size_t,
     "ctvae_glinear_wgrad_ws_bytes": _c.c_size_t,
     "ctvae_conv_input_transform_supported": _c.c_int,
     "ctvae_conv_wgrad_bn_apply_supported": _c.c_int,
@@ -198,6 +200,7 @@ def load():
                        "ctvae_conv_bn_act_apply_is_separate": [_c.c_int] * 10 + [_c.c_size_t],
                        "ctvae_winograd_enable": [_c.c_int],
                        "ctvae_dip_state_floats": [_c.c_int, _c.c_int],
+                       "ctvae_freebits_workspace_bytes": [_c.c_int],
                        "ctvae_glinear_wgrad_ws_bytes": [_c.c_int] * 5,
                        "ctvae_conv_wino_filter_floats": [_c.c_int] * 10 + [_c.c_size_t],
                        "ctvae_conv_input_transform_supported": [_c.c_int] * 10,

@@ -47,6 +47,15 @@ epoch records and ``metrics_rank0.jsonl``, and ``Latents/latent_stats_<name>_Epo
 covariance of the posterior means) with ``Latents/corr_<name>_Epoch_<e>.png`` in the log directory (experiment.py,
 latentstats.py); ``python -m ctvae_amd.latent_stats`` does the same for a checkpoint and adds the traversal picture.  Anything but
 a bool, and the key on a model without such a posterior, is a SystemExit that names it.
+``exp_params.kld_schedule`` anneals the KL weight over the optimizer steps s -- ``{type: linear, warmup_steps: N, start: a}``:
+``kld_weight * (a + (1 - a) * min(1, s / N))``; ``{type: cyclical, cycle_steps: M, ratio: r, cycles: n}``: ``kld_weight * min(1,
+((s mod M) / M) / r)``, constant ``kld_weight`` from step n * M on (``cycles`` absent: for ever) -- and ``exp_params.kld_free_bits:
+lambda`` (nats per latent dimension, >= 0) floors the batch-mean KL of every dimension at lambda, switching off the KL gradient
+of the dimensions under it (klcontrol.py, experiment.py).  They serve VanillaVAE and its aliases, TwoStageVAE, ConditionalVAE,
+MSSIMVAE, LogCoshVAE and BetaVAE with ``loss_type: 'H'``; the training records gain ``kld_weight``, ``KLD_free_bits`` and
+``KLD_floored_dims``, validation is unchanged, and the checkpoint gains ``trainer['kl']``: a full resume under other settings is
+refused, ``load_weights_only`` starts the schedule at step 0, a run without the keys ignores the entry.  A refused value or model
+is a SystemExit that names ``exp_params.kld_schedule`` or ``exp_params.kld_free_bits``.
 """
 import argparse
 import json
@@ -285,6 +294,38 @@ def exp_latent_stats(config) -> bool:
     return on
 
 
+def exp_kl(config):
+    """``exp_params.kld_schedule`` / ``kld_free_bits`` as ``(schedule, free_bits)`` (both None: off).  A refused value, and either key
+    on a model whose loss is not recon + c * M_N * KL (BetaVAE's default ``loss_type: 'B'`` among them), are a SystemExit that
+    names the key."""
+    from . import klcontrol
+    ep = config['exp_params']
+    try:
+        schedule, free_bits = klcontrol.kl_settings(ep)
+    except ValueError as e:
+        raise SystemExit(f"exp_params.{e}")
+    if schedule is None and free_bits is None:
+        return None, None
+    mp = config['model_params']
+    name = mp.get('name')
+    cls = vae_models.get(name)
+    if cls is None or not klcontrol.serves(cls, loss_type=mp.get('loss_type', 'B')):
+        key = 'kld_schedule' if schedule is not None else 'kld_free_bits'
+        what = repr(name) + (f" with loss_type {mp.get('loss_type', 'B')!r}" if cls is not None and cls.__name__ == "BetaVAE" else "")
+        raise SystemExit(f"exp_params.{klcontrol.needs_served_model(key, what)} (model_params.name)")
+    return schedule, free_bits
+
+
+def check_kl_checkpoint(ckpt, path, schedule, free_bits):
+    """Full resume of a run under ``kld_schedule`` / ``kld_free_bits``: the checkpoint must hold ``trainer['kl']``, written under the
+    same settings; otherwise a SystemExit names the key and the path."""
+    from . import klcontrol
+    why = klcontrol.KLControl(schedule, free_bits, 0.0, "cpu").mismatch(ckpt.get("trainer", {}).get("kl"))
+    if why is not None:
+        raise SystemExit(f"exp_params.kld_schedule / kld_free_bits: {why} ({path}); set trainer_params.load_weights_only to start at "
+                         "step 0 from its weights")
+
+
 def check_codebook_checkpoint(ckpt, path, every, min_count):
     """Full resume of a run that restarts dead codes: the checkpoint must hold ``trainer['codebook']``, written under this run's
     ``every`` and ``min_count``; otherwise a SystemExit names the key and the path."""
@@ -309,6 +350,7 @@ def main(argv=None):
     ema_decay, ema_warmup, _ = exp_ema(config['exp_params'])
     _, restart_every, restart_min_count, _ = exp_codebook(config)
     exp_latent_stats(config)                 # refused here, before a device is touched; VAEXperiment reads the key itself
+    kl_schedule, kl_free_bits = exp_kl(config)             # likewise
 
     rank =int(os.environ.get("RANK", "0"))
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -344,6 +386,8 @@ def main(argv=None):
             check_ema_checkpoint(ckpt, ckpt_path, ema_decay, ema_warmup)
         if restart_every is not None and not weights_only:
             check_codebook_checkpoint(ckpt, ckpt_path, restart_every, restart_min_count)
+        if (kl_schedule is not None or kl_free_bits is not None) and not weights_only:
+            check_kl_checkpoint(ckpt, ckpt_path, kl_schedule, kl_free_bits)
         model.load_state_dict({k[6:]: v for k, v in ckpt['state_dict'].items() if k.startswith("model.")}, strict=not weights_only)
     ddp = GradBucketAllReduce(model) if world > 1 else None
     log_dir = os.path.join(config['logging_params'].get('save_dir', 'logs/'), config['logging_params'].get('name', mp['name']))

@@ -617,6 +617,23 @@ int ctvae_graph_accumulate(const float* adj, const int32_t* group, const float* 
 int ctvae_latent_accumulate(const float* mu, long mu_pitch, const float* logvar, long logvar_pitch, int B, int L, double* kl_sum,
                             double* mu_sum, double* sig2_sum, double* cov_sum, int32_t* nonfinite, int32_t* rows, void* stream);
 
+/* The Gaussian KL term with free bits and a weight that lives in device memory (exp_params.kld_free_bits / kld_schedule;
+ * klcontrol.py, kernels.FreeBitsKL).  mu and logvar are fp32 [B][L] with a row pitch each, as for ctvae_latent_accumulate.
+ *   t_bd = 1 + lv - m^2 - e^lv in fp32 (ctvae_loss_forward's expression);  m_d = -0.5 * (sum_b t_bd) / B, the sum in double with
+ *   the rows in ascending order;  a_d = 1 if m_d > free_bits or m_d is not finite, else 0;  f_d = a_d ? m_d : free_bits;
+ *   w = scale * w_dev[0] -- w_dev is DEVICE memory, read by the launch, so a captured launch follows the value it holds at replay.
+ *   out[0] = w * sum_d f_d, out[1] = sum_d m_d (ctvae_loss_forward's kld), out[2] = sum_d f_d, out[3] = the number of d with a_d = 0
+ *   g_mu, g_logvar (dense [B][L]; both NULL: not wanted): the gradients of out[0] for a unit upstream gradient,
+ *   a_d * (w / B) * m  resp.  a_d * (w / B) * 0.5 * (e^lv - 1) -- ctvae_loss_forward_grad's expressions -- and exactly 0.0f where a_d = 0.
+ * One owner thread per column and a fixed reduction tree over the columns: no atomics, the same bits from run to run and
+ * between an eager and a captured launch.  One launch for L <= 128, two (the second of one workgroup) above; L in 1 .. 1024,
+ * B >= 1, free_bits finite and >= 0.  ws: ctvae_freebits_workspace_bytes(L) bytes of scratch, 8-byte aligned (0: may be NULL).
+ * Anything else returns -22 (-12: the workspace) and launches nothing. */
+size_t ctvae_freebits_workspace_bytes(int L);
+int ctvae_freebits_kl_forward_grad(const float* mu, long mu_pitch, const float* logvar, long logvar_pitch, int B, int L,
+                                   const float* w_dev, float scale, float free_bits, float* out, float* g_mu, float* g_logvar,
+                                   float* ws, size_t ws_bytes, void* stream);
+
 /* values [M][H][W] f32 (contiguous) as a colour-mapped, tiled sheet (causalgraph.py: heatmap_u8): every value becomes cell x cell
  * pixels of colour table[floor(t*255 + 0.5)] with t = (clamp(v, lo, hi) - lo) / (hi - lo), every operation rounded to f32 on its
  * own (ctvae_image_grid_u8's byte conversion); NaN takes entry 0, +-inf clamp.  table: 256 x RGB bytes in HOST memory, read
