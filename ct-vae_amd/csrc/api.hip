@@ -217,6 +217,13 @@ int launch_kl_backward(const float* mu, long mu_rs, const float* lv, long lv_rs,
 int launch_vq_inds(const float* lat, const float* cb, long long* inds, int B, int HW, int D, int K, int C, hipStream_t st);
 int launch_vq_lookup(const float* lat, const float* cb, const long long* inds, float* out, float* vq_loss, float beta, int B,
                      int HW, int D, int K, int C, float* ws, size_t ws_bytes, hipStream_t st);
+int launch_vq_lookup_commit(const float* lat, const float* cb, const long long* inds, float* out, float* vq_loss, float beta, int B,
+                            int HW, int D, int K, int C, float* ws, size_t ws_bytes, hipStream_t st);
+int vq_ema_supported(int K, int C, int Dc);
+int launch_vq_ema_stats(const float* lat, const long* inds, long* acc_n, float* acc_s, long* invalid, int B, int HW, int D, int K,
+                        int C, float* ws, size_t ws_bytes, hipStream_t st);
+int launch_vq_ema_update(float* cb, float* N, float* M, long* acc_n, float* acc_s, int C, int K, int Dc, float decay, float eps,
+                         hipStream_t st);
 int launch_vq_backward(const float* gq, const float* gvq, const float* lat, const float* cb, const long long* inds,
                        float* glat, float* dcb, int accumulate, float beta, int B, int HW, int D, int K, int C, float* ws, size_t ws_bytes,
                        hipStream_t st);
@@ -1223,6 +1230,25 @@ int ctvae_vq_restart(const long* list, int n, const float* pool, int valid_rows,
 int ctvae_vq_restart_gather(const long* list, int n, const float* pool, int valid_rows, int D, int C, int Dc, float* rows,
                             void* stream) {
   return launch_vq_restart_gather(list, n, pool, valid_rows, D, C, Dc, rows, (hipStream_t)stream);
+}
+
+int ctvae_vq_lookup_commit(const float* latents, const float* codebooks, const int64_t* inds, float* quantized, float* vq_loss,
+                           float beta, int B, int HW, int D, int K, int C, float* ws, size_t ws_bytes, void* stream) {
+  if (!latents || !codebooks || !inds || !quantized || !vq_loss || !ws || C <= 0) return kErrBadArg;
+  return launch_vq_lookup_commit(latents, codebooks, (const long long*)inds, quantized, vq_loss, beta, B, HW, D, K, C, ws, ws_bytes,
+                                 (hipStream_t)stream);
+}
+
+int ctvae_vq_ema_supported(int K, int C, int Dc) { return vq_ema_supported(K, C, Dc); }
+
+int ctvae_vq_ema_stats(const float* latents, const long* inds, long* acc_n, float* acc_s, long* invalid, int B, int HW, int D, int K,
+                       int C, float* ws, size_t ws_bytes, void* stream) {
+  return launch_vq_ema_stats(latents, inds, acc_n, acc_s, invalid, B, HW, D, K, C, ws, ws_bytes, (hipStream_t)stream);
+}
+
+int ctvae_vq_ema_update(float* codebooks, float* N, float* M, long* acc_n, float* acc_s, int C, int K, int Dc, float decay, float eps,
+                        void* stream) {
+  return launch_vq_ema_update(codebooks, N, M, acc_n, acc_s, C, K, Dc, decay, eps, (hipStream_t)stream);
 }
 
 size_t ctvae_grad_segment_chunk_floats(void) { return grad_segment_chunk_floats(); }

@@ -214,6 +214,31 @@ __global__ __launch_bounds__(64) void vq_loss_finish_kernel(const float* __restr
   if (threadIdx.x == 0) out[0] = total;
 }
 
+// the EMA-codebook form (csrc/vqema.hip; exp_params.codebook_ema_decay): vq_loss = sum_i mse_i*beta, the commitment term alone --
+// the codebook is not trained through the loss.  The same partials, the same sums, one term less per codebook.
+__global__ __launch_bounds__(64) void vq_loss_finish_commit_kernel(const float* __restrict__ part, int nblocks, int C, double inv_n,
+                                                                   float beta, float* __restrict__ out) {
+  float total = 0.f;
+  for (int i = 0; i < C; ++i) {
+    double s = 0.0;
+    for (int b0 = 0; b0 < nblocks; b0 += 8 * 64) {
+      float t[8];
+#pragma unroll
+      for (int u = 0; u < 8; ++u) {
+        const int b = b0 + threadIdx.x + 64 * u;
+        const float v = part[(size_t)(b < nblocks ? b : nblocks - 1) * C + i];
+        t[u] = b < nblocks ? v : 0.f;
+      }
+#pragma unroll
+      for (int u = 0; u < 8; ++u) s += (double)t[u];
+    }
+    s = wave_sum_d(s);
+    const float mse = (float)(s * inv_n);
+    total = total + mse * beta;
+  }
+  if (threadIdx.x == 0) out[0] = total;
+}
+
 // g_lat[p][j] = sum_{i: 0<=j-i<Dc} ( g_q[p][i*Dc + j-i] + g_vq*beta*2*(x_j - E_i[idx][j-i])/(P*Dc) )
 __global__ __launch_bounds__(256) void vq_bwd_latents_kernel(const float* __restrict__ gq, const float* __restrict__ gvq,
                                                              const float* __restrict__ lat, const float* __restrict__ cb,
@@ -473,6 +498,22 @@ int launch_vq_lookup(const float* lat, const float* cb, const long long* inds, f
   hipLaunchKernelGGL(vq_lookup_kernel, dim3((unsigned)blocks), dim3(256), 0, st, lat, cb, inds, out, ws, P, D, K, Dc, C, HW);
   CTVAE_LAUNCH_CHECK();
   hipLaunchKernelGGL(vq_loss_finish_kernel, dim3(1), dim3(64), 0, st, ws, (int)blocks, C, 1.0 / ((double)P * Dc), beta, vq_loss);
+  CTVAE_LAUNCH_CHECK();
+  return 0;
+}
+
+int launch_vq_lookup_commit(const float* lat, const float* cb, const long long* inds, float* out, float* vq_loss, float beta, int B,
+                            int HW, int D, int K, int C, float* ws, size_t ws_bytes, hipStream_t st) {
+  if (D % C != 0 || C > 8) return kErrBadArg;
+  if (ws_bytes / sizeof(float) < vq_workspace_floats(C)) return kErrWorkspace;
+  const int Dc = D / C, P = B * HW;
+  long blocks = ((long)P * D + 255) / 256;
+  if (blocks > 1024) blocks = 1024;
+  ProfScope ps("vq_lookup+loss_finish_commit", st, 0.0, 8.0 * (double)P * D + 8.0 * (double)P * C + 4.0 * (double)K * D);
+  hipLaunchKernelGGL(vq_lookup_kernel, dim3((unsigned)blocks), dim3(256), 0, st, lat, cb, inds, out, ws, P, D, K, Dc, C, HW);
+  CTVAE_LAUNCH_CHECK();
+  hipLaunchKernelGGL(vq_loss_finish_commit_kernel, dim3(1), dim3(64), 0, st, ws, (int)blocks, C, 1.0 / ((double)P * Dc), beta,
+                     vq_loss);
   CTVAE_LAUNCH_CHECK();
   return 0;
 }

@@ -13,6 +13,16 @@ import torch
 import torch.distributed as dist
 
 
+def codebook_ema_reduce(words, sums, all_reduce_sum):
+    """The reduce plumbing of ``GradBucketAllReduce.all_reduce_codebook_ema`` on any tensors (host tensors under gloo): pack the
+    int64 ``words`` and the fp32 ``sums`` into one float64 buffer, hand it to ``all_reduce_sum`` (in place), unpack in place."""
+    nw = words.numel()
+    buf = torch.cat([words.reshape(-1).to(torch.float64), sums.reshape(-1).to(torch.float64)])
+    all_reduce_sum(buf)
+    words.copy_(buf[:nw].to(torch.int64).view_as(words))
+    sums.copy_(buf[nw:].to(torch.float32).view_as(sums))
+
+
 class GradBucketAllReduce:
     def __init__(self, model, process_group=None, bucket_bytes=32 << 20, broadcast_from=0, force=False):
         """force: issue the collectives even in a 1-rank group (rehearsal of the N>1 call pattern on one GPU)."""
@@ -103,6 +113,14 @@ class GradBucketAllReduce:
         when no rank chose it often enough.  One small collective per restart, stream-ordered."""
         if self.active:
             dist.all_reduce(counts, op=dist.ReduceOp.SUM, group=self.pg)
+
+    def all_reduce_codebook_ema(self, words, sums):
+        """ONE SUM all-reduce, in place, of the window accumulators of ``optim.CodebookEMA``: the int64 counts and the fp32
+        sums travel as one float64 buffer -- integers below 2^53 and fp32 values are exact in it, the
+        ranks' shares are added in float64 and the sums rounded back to fp32 once, so every rank ends with the same bits (and a
+        group of one rank with the bits it had)."""
+        if self.active:
+            codebook_ema_reduce(words, sums, lambda t: dist.all_reduce(t, op=dist.ReduceOp.SUM, group=self.pg))
 
     def broadcast_rows(self, rows, src=0):
         """Rank ``src``'s gathered restart rows to every rank, in place: the pools differ from rank to rank, the restarted codes

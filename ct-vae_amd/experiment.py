@@ -90,6 +90,21 @@ restarted, valid_rows}``; a full resume restores it and refuses other ``every`` 
 built: either key on a model without such a quantiser, and restarts when ``update_parameters`` leaves the codebooks outside the
 optimizer's slice.  Without the keys there is no buffer, no launch, no log key and no entry.
 
+``exp_params.codebook_ema_decay`` (a float, 0 < g < 1; absent: off) with ``codebook_ema_eps`` (default 1e-5): EMA codebooks (van den
+Oord et al. 2017, appendix A.1) for the models with a ``vq_layer`` quantiser, by ``optim.CodebookEMA``.  With the key the
+quantiser's ``ema`` is set for good -- ``VQ_Loss`` is the commitment term alone, beta / (1 + beta) of the value without the key, in
+training and validation records alike, and no codebook gradient is formed: the codebooks' block of the flat gradient buffer is an
+absent block -- and ``CodebookEMA.observe`` is its ``ema_observer`` around the training batches of ``fit()`` only
+(``_counting_training_codes``): one statistics call per index search, part of the forward, inside the captured body when the step
+is captured.  ``codebook_update()`` runs eagerly behind every optimizer step, once per window under ``accumulate_grad_batches``,
+in the order ``track_gradients()``, ``codebook_update()``, ``ema_update()`` (the weight average sees the codebook the step ends
+with), ``codebook_restart()`` (a restarted code gets N = 1, M = its row).  Under DDP the window accumulators are SUM-reduced first:
+one small collective per optimizer step, none inside a window, and all ranks hold the same N, M and codebooks.  Records on
+logging steps: ``codebook_ema_min_cluster[_<i>]`` / ``codebook_ema_max_cluster[_<i>]``.  ``state_dict()`` carries ``"codebook_ema":
+{decay, eps, N, M, acc_n, acc_s, invalid}``; a full resume restores it and refuses another decay or eps, or a checkpoint
+without the entry.  Refused when the experiment is built: the key on another model, and the key when ``update_parameters`` leaves
+the codebooks outside the optimizer's slice.  Without the key there is no buffer, no launch, no log key and no entry.
+
 ``exp_params.latent_stats`` (a bool): latent usage of the models with a Gaussian posterior (``BaseVAE.gaussian_posterior``), by
 ``latentstats.LatentStats`` on rank 0.  ``_validate`` zeroes it, every ``validation_step`` hands it the batch's ``mu`` / ``log_var``
 views (one ``ctvae_latent_accumulate`` launch, eager like all of validation, no device-to-host copy), and behind the validation
@@ -128,9 +143,9 @@ from .klcontrol import KLControl, kl_settings, needs_served_model, serves as kl_
 from .latentstats import (LATENT_DIR, LatentStats, has_gaussian_posterior, latent_stats_setting, needs_gaussian_posterior,
                           record as latent_record, write_files as write_latent_files)
 from .metrics import _eval_mode as eval_mode
-from .optim import (CodebookUsage, ExponentialLR, FlatAdam, GradientTracker, WeightEMA, absent_grad_setting, accumulate_setting,
-                    clip_settings, codebook_record, codebook_settings, ema_settings, track_grad_norm_setting, watch_settings,
-                    with_window_ends)
+from .optim import (CodebookEMA, CodebookUsage, ExponentialLR, FlatAdam, GradientTracker, WeightEMA, absent_grad_setting,
+                    accumulate_setting, clip_settings, codebook_ema_serves, codebook_ema_settings, codebook_record,
+                    codebook_settings, ema_settings, track_grad_norm_setting, watch_settings, with_window_ends)
 
 
 def _graph_key(real_img, kwargs):
@@ -230,6 +245,7 @@ class _GraphedTrainStep:
             exp.ddp_step(self.pattern)
         if ends_window:
             exp.track_gradients()          # eager, behind the replay: the flat buffer holds the gradient that was just stepped
+            exp.codebook_update()          # eager too (decay and eps are by-value arguments), in front of the weight average
             exp.ema_update()               # eager too: the decay is a by-value argument that a captured launch would freeze
             exp.codebook_restart()         # eager too: the dead list is formed on the host
             exp.global_step += 1
@@ -304,6 +320,7 @@ class VAEXperiment:
         decay, warmup, self.ema_eval = ema_settings(params.get("ema_decay"), params.get("ema_warmup"), params.get("ema_eval"))
         self.ema = WeightEMA(self.optimizer, decay, warmup) if decay is not None else None
         self._build_codebook_usage(params)
+        self._build_codebook_ema(params)
         # latent usage (latentstats.LatentStats): validated on every rank, built on rank 0 only
         self.latent_stats = latent_stats_setting(params.get("latent_stats"))
         self.val_latents = None
@@ -517,6 +534,8 @@ class VAEXperiment:
                               "valid_rows": -1 if cb.valid_rows is None else int(cb.valid_rows)}
         if self.kl is not None:            # (the weight itself is a function of global_step)
             sd["kl"] = self.kl.state_dict()
+        if self.codebook_ema is not None:
+            sd["codebook_ema"] = self.codebook_ema.state_dict()
         return sd
 
     def load_state_dict(self, sd):
@@ -549,6 +568,14 @@ class VAEXperiment:
             self.ema.load_state_dict(sd["ema"])
         if self.codebook is not None:      # (a run without the key ignores the entry)
             self._load_codebook_state(sd.get("codebook"))
+        if self.codebook_ema is not None:  # (likewise)
+            if "codebook_ema" not in sd:
+                raise RuntimeError("checkpoint holds no codebook average (trainer['codebook_ema']), this run keeps one "
+                                   "(exp_params.codebook_ema_decay)")
+            self.codebook_ema.load_state_dict(sd["codebook_ema"])
+            if not self._rank0():          # (the accumulators are rank 0's own rows; the other ranks' share of the window starts over)
+                self.codebook_ema.words.zero_()
+                self.codebook_ema.acc_s.zero_()
         K.bump_param_epoch()
 
     def ddp_step(self, pattern=None):
@@ -594,6 +621,7 @@ class VAEXperiment:
         else:
             self.optimizer.step()
         self.track_gradients()
+        self.codebook_update()
         self.ema_update()
         self.codebook_restart()
         self.global_step += 1
@@ -688,19 +716,71 @@ class VAEXperiment:
         if stats and self._rank0():
             self.val_codebook = CodebookUsage(vq)
 
+    # -- EMA codebooks (exp_params.codebook_ema_decay / codebook_ema_eps; optim.CodebookEMA) ---------------------------
+    def _build_codebook_ema(self, params):
+        """``codebook_ema`` (on every rank), or None without the key.  Refused by name: a bad value, the key on a model without
+        a ``vq_layer`` quantiser, and the key when ``update_parameters`` leaves the codebooks outside the optimizer's slice -- the
+        user asked for those weights to stand still, the condition under which restarts are refused.  With the key the
+        quantiser's ``ema`` is set for good: the commitment-only loss is a property of the run, validation included."""
+        decay, eps = codebook_ema_settings(params.get("codebook_ema_decay"), params.get("codebook_ema_eps"))
+        self.codebook_ema = None
+        self.last_codebook_ema = None           # the cluster-size record of the last logging step (also without a log file)
+        if decay is None:
+            return
+        if not codebook_ema_serves(self.model):
+            raise ValueError(f"codebook_ema_decay needs a model with a vq_layer quantiser (MCQVAE, VQVAE, CTMCQVAE), got "
+                             f"{type(self.model).__name__}")
+        vq = self.model.vq_layer
+        ema = CodebookEMA(vq, decay, eps)
+        cb = ema.codebooks()
+        lo = (cb.data_ptr() - self.model.flat_params.data_ptr()) // 4 - int(self.optimizer.slice.start or 0)
+        if not (0 <= lo and lo + cb.numel() <= self.model.flat_params[self.optimizer.slice].numel()):
+            raise ValueError(f"codebook_ema_decay cannot move codebooks the optimizer does not step: update_parameters="
+                             f"{params.get('update_parameters')!r} leaves the codebooks outside the optimizer's slice")
+        self.codebook_ema = vq.ema = ema
+
+    def codebook_update(self):
+        """Called eagerly right behind an optimizer step and ``track_gradients()``, in front of ``ema_update()`` -- the weight
+        average sees the codebook the step ends with -- and never inside a capture: [DDP: one SUM all-reduce of the window
+        accumulators,] one ``ctvae_vq_ema_update`` launch, a parameter-epoch bump.  On the steps that log training scalars one
+        JSONL line ``{"codebook_ema_min_cluster_<i>": min_k N, "codebook_ema_max_cluster_<i>": max_k N, ...,
+        "codebook_ema_min_cluster": ..., "codebook_ema_max_cluster": ..., "step": s}`` (rank 0, one device-to-host copy).
+        Nothing without ``codebook_ema_decay``."""
+        ema = self.codebook_ema
+        if ema is None:
+            return
+        ddp = self.ddp if self.ddp is not None and getattr(self.ddp, "active", False) else None
+        ema.update(reduce=ddp.all_reduce_codebook_ema if ddp is not None else None)
+        if self.global_step % self.log_every == 0 and self._rank0():
+            lo, hi = ema.cluster_sizes()
+            rec = {}
+            for i in range(ema.C):
+                rec[f"codebook_ema_min_cluster_{i}"], rec[f"codebook_ema_max_cluster_{i}"] = lo[i], hi[i]
+            rec["codebook_ema_min_cluster"], rec["codebook_ema_max_cluster"] = min(lo), max(hi)
+            rec["step"] = self.global_step
+            self.last_codebook_ema = rec
+            if self.log_file is not None:
+                self.log_file.write(json.dumps(rec) + "\n")
+                self.log_file.flush()
+
     @contextlib.contextmanager
     def _counting_training_codes(self):
         """The training counter is the quantiser's ``usage_observer`` inside (around the training batches of ``fit()`` only:
-        validation, ``sample_images``, the metrics and the tools count nothing here); nothing without restarts."""
-        if self.codebook is None:
+        validation, ``sample_images``, the metrics and the tools count nothing here), and so is ``CodebookEMA.observe`` its
+        ``ema_observer``; nothing without restarts and EMA codebooks."""
+        if self.codebook is None and self.codebook_ema is None:
             yield
             return
         vq = self.model.vq_layer
-        vq.usage_observer = self.codebook.observe
+        if self.codebook is not None:
+            vq.usage_observer = self.codebook.observe
+        if self.codebook_ema is not None:      # the EMA statistics are training-only as well (the loss form is the run's)
+            vq.ema_observer = self.codebook_ema.observe
         try:
             yield
         finally:
             vq.usage_observer = None
+            vq.ema_observer = None
 
     def codebook_restart(self):
         """Called eagerly right behind an optimizer step, next to ``track_gradients()`` / ``ema_update()`` and never inside a
@@ -716,6 +796,8 @@ class VAEXperiment:
         counts, dead, _ = cb.restart(self.optimizer, self.codebook_min_count, self.params.get("manual_seed", 0), self.codebook_ordinal,
                                      reduce=ddp.all_reduce_counts if ddp is not None else None,
                                      broadcast=ddp.broadcast_rows if ddp is not None else None)
+        if self.codebook_ema is not None:      # a restarted code is one observation at its new row
+            self.codebook_ema.reset_codes(dead)
         self.codebook_ordinal += 1
         self.codebook_restarted += len(dead)
         rec = {"codebook_restarts": len(dead)}
@@ -888,6 +970,7 @@ class VAEXperiment:
                     self.window_step(ends)
                     if ends:
                         self.track_gradients()
+                        self.codebook_update()
                         self.ema_update()
                         self.codebook_restart()
                         self.global_step += 1

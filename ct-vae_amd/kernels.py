@@ -2465,6 +2465,43 @@ class VQLookup(Function):
         return (g_lat, None, None, None, None) + (None,) * len(ctx.codebooks)
 
 
+class VQLookupEMA(Function):
+    """``VQLookup`` for EMA codebooks (exp_params.codebook_ema_decay): vq_loss = beta * sum_c mse_c, the commitment term alone
+    (ctvae_vq_lookup_commit), and no codebook gradient -- the backward pass is ctvae_vq_backward's null-``d_codebooks`` path, so
+    the codebooks' block of the flat gradient buffer is never asked for and stays an absent block.  The quantised latents and the
+    latent gradient are bit for bit ``VQLookup``'s."""
+
+    @staticmethod
+    def forward(ctx, latents, inds, beta, K, C, *codebooks):
+        _req_cuda(latents, inds)
+        lat = _c(latents)
+        inds = _c(inds)
+        B, H, W, D = lat.shape
+        q = torch.empty_like(lat)
+        vq_loss = torch.empty((), dtype=torch.float32, device=lat.device)
+        ws = native.workspace(lat.device)
+        native.call("ctvae_vq_lookup_commit", lat.data_ptr(), codebooks[0].data_ptr(), inds.data_ptr(), q.data_ptr(),
+                    vq_loss.data_ptr(), float(beta), B, H * W, D, K, C, ws.data_ptr(), ws.numel() * 4)
+        ctx.meta = (float(beta), K, C)
+        ctx.codebooks = codebooks
+        ctx.save_for_backward(lat, inds)
+        return q, vq_loss
+
+    @staticmethod
+    def backward(ctx, g_q, g_vq):
+        lat, inds = ctx.saved_tensors
+        beta, K, C = ctx.meta
+        B, H, W, D = lat.shape
+        g_q = _c(g_q) if g_q is not None else None
+        g_vq = _c(g_vq) if g_vq is not None else None
+        g_lat = torch.empty_like(lat) if ctx.needs_input_grad[0] else None
+        if g_lat is not None:
+            ws = native.workspace(lat.device)
+            native.call("ctvae_vq_backward", native.ptr(g_q), native.ptr(g_vq), lat.data_ptr(), ctx.codebooks[0].data_ptr(),
+                        inds.data_ptr(), g_lat.data_ptr(), None, 0, beta, B, H * W, D, K, C, ws.data_ptr(), ws.numel() * 4)
+        return (g_lat, None, None, None, None) + (None,) * len(ctx.codebooks)
+
+
 # ---------------------------------------------------------------------------------------------------
 # flat fused Adam
 # ---------------------------------------------------------------------------------------------------
@@ -2821,6 +2858,71 @@ def vq_restart(entries, pool, valid_rows, codebooks, exp_avg, exp_avg_sq, rows=N
     native.call("ctvae_vq_restart", dev_ent.data_ptr(), ent.size(0), native.ptr(pool if rows is None else None),
                 int(valid_rows) if rows is None else 0, D, native.ptr(rows), codebooks.data_ptr(), exp_avg.data_ptr(),
                 exp_avg_sq.data_ptr(), C, K, Dc)
+
+
+# ---------------------------------------------------------------------------------------------------
+# EMA codebooks (csrc/vqema.hip; optim.CodebookEMA)
+# ---------------------------------------------------------------------------------------------------
+VQ_EMA_MAX_K, VQ_EMA_MAX_C, VQ_EMA_MAX_DC = 16384, 8, 256      # what ctvae_vq_ema_stats / ctvae_vq_ema_update cover
+
+
+def vq_ema_supported(K, C, Dc):
+    return 1 <= K <= VQ_EMA_MAX_K and 1 <= C <= VQ_EMA_MAX_C and 1 <= Dc <= VQ_EMA_MAX_DC
+
+
+def _vq_ema_accumulators(what, acc_n, acc_s):
+    """The checks both EMA wrappers make of the window accumulators; returns (C, K, Dc)."""
+    _req_dense(what, "acc_n", acc_n, torch.int64)
+    _req_dense(what, "acc_s", acc_s, torch.float32)
+    if acc_n.dim() != 2 or acc_s.dim() != 3 or tuple(acc_s.shape[:2]) != tuple(acc_n.shape) or acc_s.numel() == 0:
+        raise ValueError(f"{what}: acc_n [C, K] {tuple(acc_n.shape)} and acc_s [C, K, Dc] {tuple(acc_s.shape)} do not fit "
+                         "together")
+    C, K, Dc = acc_s.shape
+    if not vq_ema_supported(K, C, Dc):
+        raise ValueError(f"{what}: K={K}, C={C}, Dc={Dc} is not covered: the kernels need 1 <= K <= {VQ_EMA_MAX_K}, C <= "
+                         f"{VQ_EMA_MAX_C} and Dc <= {VQ_EMA_MAX_DC}")
+    return C, K, Dc
+
+
+def vq_ema_stats(latents_nhwc, inds, acc_n, acc_s, invalid):
+    """The EMA statistics of one micro-batch, added to the window accumulators (ctvae_vq_ema_stats): acc_n[c][k] += the number of
+    positions with inds[:, c] == k, acc_s[c][k][d] += the sum of latents[p][c + d] over those positions (the slice quirk).
+    latents: fp32 [..., D] NHWC with D = C * Dc; inds: int64 [B, C, ...] as ``vq_compute_inds`` returns it; acc_n int64 [C, K],
+    acc_s fp32 [C, K, Dc], invalid one int64 word (indices outside [0, K)).  A wrong dtype or shape, a non-contiguous tensor or
+    an uncovered (K, C, Dc) raises a ValueError that names it, before any launch."""
+    what = "vq_ema_stats"
+    C, K, Dc = _vq_ema_accumulators(what, acc_n, acc_s)
+    _req_dense(what, "latents", latents_nhwc, torch.float32)
+    _req_dense(what, "inds", inds, torch.int64)
+    _req_dense(what, "invalid", invalid, torch.int64)
+    if inds.dim() < 3 or inds.size(1) != C or inds.numel() == 0 or invalid.numel() != 1 or latents_nhwc.dim() < 2 \
+            or latents_nhwc.size(-1) != C * Dc or latents_nhwc.numel() // (C * Dc) * C != inds.numel():
+        raise ValueError(f"{what}: latents [..., D = {C * Dc}] {tuple(latents_nhwc.shape)}, inds [B, C = {C}, ...] "
+                         f"{tuple(inds.shape)} and invalid [1] {tuple(invalid.shape)} do not fit together")
+    _req_cuda(latents_nhwc, inds, acc_n, acc_s, invalid)
+    B = inds.size(0)
+    ws = native.workspace(latents_nhwc.device)
+    native.call("ctvae_vq_ema_stats", latents_nhwc.data_ptr(), inds.data_ptr(), acc_n.data_ptr(), acc_s.data_ptr(),
+                invalid.data_ptr(), B, inds.numel() // (B * C), C * Dc, K, C, ws.data_ptr(), ws.numel() * 4)
+
+
+def vq_ema_update(codebooks, N, M, acc_n, acc_s, decay, eps):
+    """The EMA codebook update behind an optimizer step (ctvae_vq_ema_update): N = decay N + (1 - decay) acc_n, M likewise from
+    acc_s, E = M / Ntilde with the Laplace-smoothed cluster sizes, every code overwritten, the accumulators zeroed in the same
+    launch.  codebooks / M / acc_s: fp32 [C, K, Dc]; N fp32 [C, K]; acc_n int64 [C, K]; decay in (0, 1) and eps > 0 are handed
+    over by value (as fp32).  Checked before the launch like ``vq_ema_stats``.  The caller bumps the parameter epoch."""
+    what = "vq_ema_update"
+    C, K, Dc = _vq_ema_accumulators(what, acc_n, acc_s)
+    for name, t in (("codebooks", codebooks), ("N", N), ("M", M)):
+        _req_dense(what, name, t, torch.float32)
+    if tuple(codebooks.shape) != (C, K, Dc) or tuple(M.shape) != (C, K, Dc) or tuple(N.shape) != (C, K):
+        raise ValueError(f"{what}: codebooks {tuple(codebooks.shape)} and M {tuple(M.shape)} must be [C, K, Dc] = {(C, K, Dc)}, "
+                         f"N {tuple(N.shape)} [C, K]")
+    if isinstance(decay, bool) or not 0.0 < float(decay) < 1.0 or isinstance(eps, bool) or not float(eps) > 0.0:
+        raise ValueError(f"{what}: decay {decay!r} must lie in (0, 1) and eps {eps!r} above 0")
+    _req_cuda(codebooks, N, M, acc_n, acc_s)
+    native.call("ctvae_vq_ema_update", codebooks.data_ptr(), N.data_ptr(), M.data_ptr(), acc_n.data_ptr(), acc_s.data_ptr(),
+                C, K, Dc, float(decay), float(eps))
 
 
 def adam_flags_window(window, table, mode):

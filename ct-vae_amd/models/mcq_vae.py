@@ -23,18 +23,23 @@ class VectorQuantizerMS(nn.Module):
         self.K, self.D, self.beta = num_embeddings, embedding_dim, beta
         self.embedding = PackedEmbedding(self.K, self.D)
         self.usage_observer = None      # called with (inds [B,1,H,W], latents NHWC) after every index search (optim.CodebookUsage)
+        self.ema = None                 # an optim.CodebookEMA: commitment-only loss, no codebook gradient (kernels.VQLookupEMA)
+        self.ema_observer = None        # its observe(), attached around the training batches only
 
     def compute_inds(self, latents: Tensor) -> Tensor:
         lat = K.to_nhwc(latents)
         inds = K.vq_compute_inds(lat, [self.embedding.weight], self.K, 1)
         if self.usage_observer is not None:
             self.usage_observer(inds, lat)
+        if self.ema_observer is not None:
+            self.ema_observer(inds, lat)
         return inds[:, 0]                                                                   # [B,H,W]
 
     def compute_latents(self, latents: Tensor, encoding_inds: Tensor):
         lat = K.to_nhwc(latents)
         B, H, W, _ = lat.shape
-        q, vq_loss = K.VQLookup.apply(lat, encoding_inds.reshape(B, 1, H, W), self.beta, self.K, 1, self.embedding.weight)
+        lookup = K.VQLookup if self.ema is None else K.VQLookupEMA
+        q, vq_loss = lookup.apply(lat, encoding_inds.reshape(B, 1, H, W), self.beta, self.K, 1, self.embedding.weight)
         return K.to_nchw_view(q), vq_loss
 
     def forward(self, latents: Tensor, inds: bool = False):
@@ -55,6 +60,8 @@ class MultipleCodebookVectorQuantizer(nn.Module):
         self.quantizers = nn.ModuleList([VectorQuantizerMS(num_embeddings, self.reduced_embedding_dim, beta)
                                          for _ in range(codebooks)])
         self.usage_observer = None      # called with (inds [B,C,H,W], latents NHWC) after every index search (optim.CodebookUsage)
+        self.ema = None                 # an optim.CodebookEMA: commitment-only loss, no codebook gradient (kernels.VQLookupEMA)
+        self.ema_observer = None        # its observe(), attached around the training batches only
 
     def _codebooks(self):
         ws = [q.embedding.weight for q in self.quantizers]
@@ -70,11 +77,14 @@ class MultipleCodebookVectorQuantizer(nn.Module):
         inds = K.vq_compute_inds(lat, self._codebooks(), self.num_embeddings, self.nb_codebooks)
         if self.usage_observer is not None:
             self.usage_observer(inds, lat)
+        if self.ema_observer is not None:
+            self.ema_observer(inds, lat)
         return inds
 
     def compute_latents(self, latents: Tensor, encoding_inds: Tensor):
-        q, vq_loss = K.VQLookup.apply(K.to_nhwc(latents), encoding_inds, self.beta, self.num_embeddings, self.nb_codebooks,
-                                      *self._codebooks())
+        lookup = K.VQLookup if self.ema is None else K.VQLookupEMA
+        q, vq_loss = lookup.apply(K.to_nhwc(latents), encoding_inds, self.beta, self.num_embeddings, self.nb_codebooks,
+                                  *self._codebooks())
         return K.to_nchw_view(q), vq_loss
 
     def forward(self, latents: Tensor, inds: bool = False):

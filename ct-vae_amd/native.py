@@ -129,6 +129,9 @@ SIGNATURES = {
     "ctvae_vq_usage_pool_fill": [_fp, _fp, _fp, _i, _i, _i, _i, _fp, _fp, _l, _i, _l, _vp],
     "ctvae_vq_restart": [_fp, _i, _fp, _i, _i, _fp, _fp, _fp, _fp, _i, _i, _i, _vp],
     "ctvae_vq_restart_gather": [_fp, _i, _fp, _i, _i, _i, _i, _fp, _vp],
+    "ctvae_vq_ema_stats": [_fp, _fp, _fp, _fp, _fp, _i, _i, _i, _i, _i, _fp, _sz, _vp],
+    "ctvae_vq_ema_update": [_fp, _fp, _fp, _fp, _fp, _i, _i, _i, _f, _f, _vp],
+    "ctvae_vq_lookup_commit": [_fp, _fp, _fp, _fp, _fp, _f, _i, _i, _i, _i, _i, _fp, _sz, _vp],
     "ctvae_grad_segment_stats": [_fp, _l, _f, _f, _fp, _i, _fp, _fp, _fp, _i, _fp, _fp, _fp, _fp, _fp, _fp, _fp, _fp, _fp, _i, _vp],
     "ctvae_grad_segment_hist": [_fp, _l, _f, _fp, _i, _fp, _fp, _i, _fp, _fp, _vp],
     "ctvae_mssim_forward": [_fp, _fp, _fp, _fp, _fp, _fp, _fp, _i, _i, _i, _i, _vp],
@@ -155,6 +158,7 @@ _RESTYPES = {
     "ctvae_grad_clip_workspace_floats": _c.c_size_t,
     "ctvae_grad_accumulate_pass_floats": _c.c_size_t,
     "ctvae_vq_usage_pass_indices": _c.c_size_t,
+    "ctvae_vq_ema_supported": _c.c_int,
     "ctvae_grad_segment_chunk_floats": _c.c_size_t,
     "ctvae_mssim_part_floats": _c.c_size_t,
     "ctvae_freebits_workspace_bytes": _c.c_size_t,
@@ -200,6 +204,7 @@ def load():
                        "ctvae_conv_bn_act_apply_is_separate": [_c.c_int] * 10 + [_c.c_size_t],
                        "ctvae_winograd_enable": [_c.c_int],
                        "ctvae_dip_state_floats": [_c.c_int, _c.c_int],
+                       "ctvae_vq_ema_supported": [_c.c_int] * 3,
                        "ctvae_freebits_workspace_bytes": [_c.c_int],
                        "ctvae_glinear_wgrad_ws_bytes": [_c.c_int] * 5,
                        "ctvae_conv_wino_filter_floats": [_c.c_int] * 10 + [_c.c_size_t],

@@ -68,6 +68,12 @@ index tensors the quantiser computes anyway (csrc/vqusage.hip; integer atomics, 
 list (``codebook_dead_list``), the draw of pool rows (``codebook_restart_rows``) and the ``ctvae_vq_restart`` launch that writes
 the codes and zeroes their Adam moments.  The reference has neither: what they compute is defined here.  Without the keys nothing
 is allocated or launched.
+
+EMA codebooks (``exp_params.codebook_ema_decay`` / ``codebook_ema_eps``; ``CodebookEMA`` beside ``CodebookUsage``,
+``codebook_ema_settings`` its validator): the codebooks of a quantising model as running means of the latents assigned to each
+code (van den Oord et al. 2017, appendix A.1) instead of optimizer-trained weights -- window statistics by ``ctvae_vq_ema_stats``
+per micro-batch, one ``ctvae_vq_ema_update`` launch behind every optimizer step (csrc/vqema.hip; no float atomics).  The reference
+has no such update: what it computes is defined here.  Without the key nothing is allocated or launched.
 """
 import contextlib
 import math
@@ -600,6 +606,136 @@ class CodebookUsage:
         if lo is None:
             raise RuntimeError("the codebooks lie outside the optimizer's slice")
         return cb, optimizer.exp_avg[lo:lo + cb.numel()].view(cb.shape), optimizer.exp_avg_sq[lo:lo + cb.numel()].view(cb.shape)
+
+
+CODEBOOK_EMA_DECAY_KEY, CODEBOOK_EMA_EPS_KEY = "codebook_ema_decay", "codebook_ema_eps"
+CODEBOOK_EMA_EPS_DEFAULT = 1e-5
+
+
+def codebook_ema_settings(decay, eps=None):
+    """Validated ``(codebook_ema_decay, codebook_ema_eps)``, both rounded to fp32 once (what the update launch receives).
+    ``decay`` None means off: (None, None), and then ``eps`` may not be set.  Otherwise ``decay`` is a float with 0 < d < 1 that is
+    still inside (0, 1) in fp32, and ``eps`` (None: 1e-5) a finite float > 0 that is still > 0 in fp32.  Anything else -- a bool,
+    an int or a string, a value outside the range -- raises a ValueError that names the key."""
+    if decay is None:
+        if eps is not None:
+            raise ValueError(f"{CODEBOOK_EMA_EPS_KEY} is set without {CODEBOOK_EMA_DECAY_KEY}: there is no codebook average to "
+                             "apply it to")
+        return None, None
+    if isinstance(decay, bool) or not isinstance(decay, float) or not 0.0 < decay < 1.0 or not 0.0 < _fp32(decay) < 1.0:
+        raise ValueError(f"{CODEBOOK_EMA_DECAY_KEY} {decay!r} is invalid: it must be a float with 0 < {CODEBOOK_EMA_DECAY_KEY} < 1")
+    if eps is None:
+        eps = CODEBOOK_EMA_EPS_DEFAULT
+    if isinstance(eps, bool) or not isinstance(eps, float) or not 0.0 < eps < 3.0e38 or not _fp32(eps) > 0.0:
+        raise ValueError(f"{CODEBOOK_EMA_EPS_KEY} {eps!r} is invalid: it must be a float > 0")
+    return _fp32(decay), _fp32(eps)
+
+
+def codebook_ema_serves(model) -> bool:
+    """Whether ``model`` is one of the quantising models the EMA codebook update is defined for (MCQVAE, VQVAE, CTMCQVAE: a
+    ``vq_layer`` quantiser with an ``ema`` switch)."""
+    vq = getattr(model, "vq_layer", None)
+    return vq is not None and hasattr(vq, "ema_observer") and hasattr(vq, "ema")
+
+
+class CodebookEMA:
+    """Exponential-moving-average codebooks (``exp_params.codebook_ema_decay``; van den Oord et al. 2017, appendix A.1), kept by
+    HIP kernels of their own (csrc/vqema.hip).  The reference has no such update: what it computes is defined here.
+
+    State per codebook c and code k, fp32 and hidden (not part of ``state_dict`` of the model): ``N[c][k]``, starting at 1, and
+    ``M[c][k][:]``, starting at E_c[k] -- "one observation at the current value".  Window accumulators: ``acc_n`` (int64) and
+    ``acc_s`` (fp32), plus an ``invalid`` word (indices outside [0, K)); acc_n and invalid are one int64 buffer and acc_s one fp32
+    buffer; a data-parallel update hands the counts and the sums to ``reduce`` at once (``ddp.all_reduce_codebook_ema``: one
+    collective).
+
+    ``observe`` is what the experiment sets as the quantiser's ``ema_observer``: one ``ctvae_vq_ema_stats`` call per index search
+    of a training micro-batch, acc += the batch's counts and sums (source channel c + d, the slice quirk).  Pointers and shapes
+    only, so it replays inside a captured step; every buffer is allocated here, outside any capture.
+
+    ``update`` runs eagerly behind an optimizer step: [``reduce(ints, floats)``: SUM over ranks,] then ONE launch,
+    N <- g N + (1-g) acc_n, M <- g M + (1-g) acc_s, n = sum_k N_k, Nt_k = (N_k + eps) / (n + K eps) * n, E_k <- M_k / Nt_k for
+    every code -- whatever the optimizer did to E is overwritten -- and the accumulators back to zero.  The parameter epoch
+    moves.  ``reset_codes`` gives restarted codes N = 1 and M = their new row."""
+
+    def __init__(self, vq_layer, decay, eps=None):
+        self.decay, self.eps = codebook_ema_settings(decay, eps)
+        if self.decay is None:
+            raise ValueError(f"{CODEBOOK_EMA_DECAY_KEY} is None: no codebook average is wanted, build no CodebookEMA")
+        self.vq = vq_layer
+        cb, self.D = quantizer_codebooks(vq_layer)
+        self.C, self.K, self.Dc = cb.shape
+        if not K.vq_ema_supported(self.K, self.C, self.Dc):
+            raise ValueError(f"{CODEBOOK_EMA_DECAY_KEY}: num_embeddings {self.K} with {self.C} codebooks of width {self.Dc} is not "
+                             f"covered by the EMA kernels (K <= {K.VQ_EMA_MAX_K}, C <= {K.VQ_EMA_MAX_C}, Dc <= {K.VQ_EMA_MAX_DC})")
+        dev = cb.device
+        self.N = torch.ones((self.C, self.K), dtype=torch.float32, device=dev)
+        self.M = cb.detach().clone().contiguous()
+        self.words = torch.zeros(self.C * self.K + 1, dtype=torch.int64, device=dev)
+        self.acc_n, self.invalid = self.words[:-1].view(self.C, self.K), self.words[-1:]
+        self.acc_s = torch.zeros((self.C, self.K, self.Dc), dtype=torch.float32, device=dev)
+        self.observed = self.updates = 0       # calls so far (host counters; a replayed step runs no Python and is not counted)
+
+    def codebooks(self):
+        return quantizer_codebooks(self.vq)[0]
+
+    def restart_from_codebooks(self):
+        """N = 1, M = the codebooks as they stand, empty window: the state of a fresh run (``load_weights_only``)."""
+        self.N.fill_(1.0)
+        self.M.copy_(self.codebooks())
+        self.words.zero_()
+        self.acc_s.zero_()
+
+    def observe(self, inds, latents_nhwc):
+        lat = latents_nhwc.detach()
+        K.vq_ema_stats(lat if lat.is_contiguous() else lat.contiguous(), inds, self.acc_n, self.acc_s, self.invalid)
+        self.observed += 1
+
+    def update(self, reduce=None):
+        if reduce is not None:
+            reduce(self.words[:-1], self.acc_s)      # (the invalid word stays this rank's own count)
+        K.vq_ema_update(self.codebooks(), self.N, self.M, self.acc_n, self.acc_s, self.decay, self.eps)
+        K.bump_param_epoch()
+        self.updates += 1
+
+    def reset_codes(self, entries, rows=None):
+        """Restarted codes: for every entry (c, k[, ...]) N[c][k] = 1 and M[c][k] = rows[i], or with ``rows`` None the code's
+        current codebook row (what ``ctvae_vq_restart`` has just written)."""
+        ent = torch.as_tensor([[int(e[0]), int(e[1])] for e in entries], dtype=torch.int64).reshape(-1, 2)
+        if ent.numel() == 0:
+            return
+        if bool(((ent < 0) | (ent >= torch.tensor([self.C, self.K]))).any()):
+            raise ValueError("CodebookEMA.reset_codes: an entry (c, k) is out of range")
+        ent = ent.to(self.N.device)
+        c, k = ent[:, 0], ent[:, 1]
+        new = self.codebooks()[c, k] if rows is None else torch.as_tensor(rows, dtype=torch.float32).to(self.M.device)
+        if tuple(new.shape) != (ent.size(0), self.Dc):
+            raise ValueError(f"CodebookEMA.reset_codes: rows must be [n, Dc] = {(ent.size(0), self.Dc)}, got {tuple(new.shape)}")
+        self.M[c, k] = new
+        self.N[c, k] = 1.0
+
+    def cluster_sizes(self):
+        """(min_k N, max_k N) per codebook on the host: one copy."""
+        n = self.N.detach().cpu()
+        return n.min(dim=1).values.tolist(), n.max(dim=1).values.tolist()
+
+    def state_dict(self):
+        return {"decay": float(self.decay), "eps": float(self.eps), "N": self.N.detach().cpu().clone(),
+                "M": self.M.detach().cpu().clone(), "acc_n": self.acc_n.detach().cpu().clone(),
+                "acc_s": self.acc_s.detach().cpu().clone(), "invalid": int(self.invalid.cpu())}
+
+    def load_state_dict(self, sd):
+        if float(sd["decay"]) != self.decay:
+            raise RuntimeError(f"codebook average was kept under {CODEBOOK_EMA_DECAY_KEY}={sd['decay']!r}, this run uses "
+                               f"{self.decay!r}")
+        if float(sd["eps"]) != self.eps:
+            raise RuntimeError(f"codebook average was kept under {CODEBOOK_EMA_EPS_KEY}={sd['eps']!r}, this run uses {self.eps!r}")
+        for name, t in (("N", self.N), ("M", self.M), ("acc_n", self.acc_n), ("acc_s", self.acc_s)):
+            if tuple(sd[name].shape) != tuple(t.shape):
+                raise RuntimeError(f"codebook average: checkpoint's {name} {tuple(sd[name].shape)} does not fit this model's "
+                                   f"codebooks {tuple(t.shape)}")
+        for name, t in (("N", self.N), ("M", self.M), ("acc_n", self.acc_n), ("acc_s", self.acc_s)):
+            t.copy_(sd[name])
+        self.invalid.fill_(int(sd.get("invalid", 0)))
 
 
 TRACK_NORM_KEY = "track_grad_norm"

@@ -41,6 +41,13 @@ encoder outputs of the last batch, zeroing their Adam moments (experiment.py, op
 gains ``trainer['codebook']``; a full resume under the key continues the window bit for bit and refuses other ``every`` /
 ``min_count``; ``load_weights_only`` starts a fresh window; a run without the key ignores the entry.  Restarts are refused when
 ``update_parameters`` leaves the codebooks outside the optimizer's slice.
+``exp_params.codebook_ema_decay: g`` (a float, 0 < g < 1; with ``codebook_ema_eps``, default 1e-5) trains the codebooks of a
+quantising model by the exponential-moving-average update of van den Oord et al. 2017, appendix A.1, instead of the optimizer
+(experiment.py, optim.py: ``CodebookEMA``): ``VQ_Loss`` becomes the commitment term alone, training records gain
+``codebook_ema_min_cluster_<i>`` / ``codebook_ema_max_cluster_<i>``, and the checkpoint gains ``trainer['codebook_ema']``; a full
+resume under the key continues bit for bit and refuses another decay or eps, ``load_weights_only`` starts from the loaded
+codebooks, a run without the key ignores the entry.  Refused like the restarts under ``update_parameters``; a refused value or
+model is a SystemExit that names ``exp_params.codebook_ema_decay`` / ``codebook_ema_eps``.
 ``exp_params.latent_stats: true`` adds the latent usage of a model with a Gaussian posterior to every validation epoch:
 ``val_latent_kl_total`` / ``_active_units`` / ``_collapsed`` / ``_mean_abs_corr`` / ``_gaussian_tc`` / ``_nonfinite`` / ``_rows`` in the
 epoch records and ``metrics_rank0.jsonl``, and ``Latents/latent_stats_<name>_Epoch_<e>.npz`` (per-dimension KL, mean, variance and
@@ -279,6 +286,43 @@ def exp_codebook(config):
     return stats, every, min_count, pool
 
 
+def exp_codebook_ema(config):
+    """``exp_params.codebook_ema_decay`` / ``codebook_ema_eps`` as ``(decay, eps)``, rounded to fp32 (decay None: off).  A refused
+    value, the key on a model that does not quantise, and the key under an ``update_parameters`` other than ``vq_layer`` (the user
+    asked for the codebooks to stand still) are a SystemExit that names the key."""
+    from .optim import codebook_ema_settings
+    ep = config['exp_params']
+    try:
+        decay, eps = codebook_ema_settings(ep.get('codebook_ema_decay'), ep.get('codebook_ema_eps'))
+    except ValueError as e:
+        raise SystemExit(f"exp_params.{e}")
+    if decay is None:
+        return None, None
+    name = config['model_params'].get('name')
+    if name not in VQ_MODELS:
+        raise SystemExit(f"exp_params.codebook_ema_decay needs a model with a vq_layer quantiser ({', '.join(VQ_MODELS)}), "
+                         f"model_params.name is {name!r}")
+    if ep.get('update_parameters') not in (None, 'vq_layer'):
+        raise SystemExit(f"exp_params.codebook_ema_decay cannot move codebooks the optimizer does not step: "
+                         f"exp_params.update_parameters is {ep.get('update_parameters')!r}")
+    return decay, eps
+
+
+def check_codebook_ema_checkpoint(ckpt, path, decay, eps):
+    """Full resume of a run with EMA codebooks: the checkpoint must hold ``trainer['codebook_ema']``, written under this run's
+    decay and eps; otherwise a SystemExit names the key and the path."""
+    entry = ckpt.get("trainer", {}).get("codebook_ema")
+    if entry is None:
+        raise SystemExit(f"exp_params.codebook_ema_decay is set, but {path} holds no codebook average (no trainer['codebook_ema']): "
+                         "it was written by a run without the key; set trainer_params.load_weights_only to start the average "
+                         "from its weights")
+    if float(entry["decay"]) != decay:
+        raise SystemExit(f"exp_params.codebook_ema_decay is {decay!r}, but {path} kept its codebook average under "
+                         f"{entry['decay']!r}")
+    if float(entry["eps"]) != eps:
+        raise SystemExit(f"exp_params.codebook_ema_eps is {eps!r}, but {path} kept its codebook average under {entry['eps']!r}")
+
+
 def exp_latent_stats(config) -> bool:
     """``exp_params.latent_stats`` as a bool (absent: False).  Anything but a bool, and the key on a model without a Gaussian
     posterior, are a SystemExit that names the key."""
@@ -349,6 +393,7 @@ def main(argv=None):
         config = yaml.safe_load(f)
     ema_decay, ema_warmup, _ = exp_ema(config['exp_params'])
     _, restart_every, restart_min_count, _ = exp_codebook(config)
+    cb_ema_decay, cb_ema_eps = exp_codebook_ema(config)    # refused here too; VAEXperiment reads the keys itself
     exp_latent_stats(config)                 # refused here, before a device is touched; VAEXperiment reads the key itself
     kl_schedule, kl_free_bits = exp_kl(config)             # likewise
 
@@ -386,6 +431,8 @@ def main(argv=None):
             check_ema_checkpoint(ckpt, ckpt_path, ema_decay, ema_warmup)
         if restart_every is not None and not weights_only:
             check_codebook_checkpoint(ckpt, ckpt_path, restart_every, restart_min_count)
+        if cb_ema_decay is not None and not weights_only:
+            check_codebook_ema_checkpoint(ckpt, ckpt_path, cb_ema_decay, cb_ema_eps)
         if (kl_schedule is not None or kl_free_bits is not None) and not weights_only:
             check_kl_checkpoint(ckpt, ckpt_path, kl_schedule, kl_free_bits)
         model.load_state_dict({k[6:]: v for k, v in ckpt['state_dict'].items() if k.startswith("model.")}, strict=not weights_only)

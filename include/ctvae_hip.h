@@ -790,6 +790,34 @@ int ctvae_vq_restart(const long* list, int n, const float* pool, int valid_rows,
 int ctvae_vq_restart_gather(const long* list, int n, const float* pool, int valid_rows, int D, int C, int Dc, float* rows,
                             void* stream);
 
+/* Exponential-moving-average codebooks of the vector-quantised models (exp_params.codebook_ema_decay; van den Oord et al. 2017,
+ * appendix A.1): the codebook is the running mean of the latents assigned to each code instead of an optimizer-trained weight.
+ *   ctvae_vq_ema_supported   1 when (K, C, Dc) is covered: 1 <= K <= 16384, 1 <= C <= 8, 1 <= Dc <= 256.
+ *   ctvae_vq_ema_stats       the statistics of one micro-batch, ADDED to the window accumulators: acc_n[c][k] (int64 [C][K]) += the
+ *                            number of positions p with inds[p][c] = k, acc_s[c][k][d] (fp32 [C][K][Dc]) += the sum over those
+ *                            positions of latents[p][c + d] -- the source channel is c + d, not c * Dc + d, the slice codebook c is
+ *                            compared against.  latents [P = B*HW][D] NHWC, inds int64 [B][C][HW], Dc = D / C.  Deterministic: one
+ *                            owner per element, positions in a fixed order, slices of the position range go through `ws` and are
+ *                            added in slice order; no float atomic.  An index outside [0, K) contributes nowhere and adds 1 to the
+ *                            int64 word `invalid`; a non-finite latent is summed like any other value.  Covered: C <= 8, Dc <= 256,
+ *                            D % C == 0, B * HW < 2^31 (scan form: K <= 65535); `ws` must hold at least C*K*Dc + C*K + C words.
+ *                            Everything else returns an error code without a launch.  Pointers and shape integers only: a
+ *                            captured launch replays correctly.  Two launches (statistics per slice, reduce).
+ *   ctvae_vq_ema_update      per codebook c, with g = decay: N[c][k] = fma(g, N[c][k], fl32((1-g) * acc_n[c][k])), M likewise from
+ *                            acc_s, n = sum_k N[c][k] in float64 in index order, Nt_k = fl32((N_k + eps) / (n + K eps) * n) formed
+ *                            in float64, codebooks[c][k][d] = M[c][k][d] / Nt_k for EVERY code; acc_n and acc_s = 0 in the same
+ *                            launch.  0 < decay < 1 and eps > 0 are by-value arguments (do not capture this launch).
+ *   ctvae_vq_lookup_commit   ctvae_vq_lookup with vq_loss = sum_i beta * mse_i, the commitment term alone (the embedding term has
+ *                            no one to train).  `quantized` is bit for bit ctvae_vq_lookup's; the backward pass is
+ *                            ctvae_vq_backward with d_codebooks = NULL. */
+int ctvae_vq_ema_supported(int K, int C, int Dc);
+int ctvae_vq_ema_stats(const float* latents, const long* inds, long* acc_n, float* acc_s, long* invalid, int B, int HW, int D, int K,
+                       int C, float* ws, size_t ws_bytes, void* stream);
+int ctvae_vq_ema_update(float* codebooks, float* N, float* M, long* acc_n, float* acc_s, int C, int K, int Dc, float decay, float eps,
+                        void* stream);
+int ctvae_vq_lookup_commit(const float* latents, const float* codebooks, const int64_t* inds, float* quantized, float* vq_loss,
+                           float beta, int B, int HW, int D, int K, int C, float* ws, size_t ws_bytes, void* stream);
+
 /* Gradient tracking: per-parameter norms and 64-bin histograms from the flat gradient buffer (Lightning's track_grad_norm, wandb's
  * watch).  `grads` (n floats) is read only.  A segment is five 64-bit words (base, rows, period, col_lo, width) and names the
  * elements base + r * period + col_lo + c, r < rows, c < width (a contiguous parameter: one row; the heads of a grouped Linear
