@@ -200,6 +200,11 @@ int launch_heatmap_u8(const float* values, int M, int H, int W, float lo, float 
                       int pad_b, const uint8_t* table, int scanlines, uint8_t* out, size_t out_bytes, hipStream_t st);
 int launch_latent_accumulate(const float* mu, long mu_pitch, const float* logvar, long lv_pitch, int B, int L, double* kl_sum,
                              double* mu_sum, double* sig2_sum, double* cov_sum, int* nonfinite, int* rows, hipStream_t st);
+int launch_recon_record(const float* a, const float* b, int B, int S, int C, const double* consts, double* rec, int* flag, int row0,
+                        int capacity, hipStream_t st);
+int launch_recon_worst(const double* old_ssim, const int* old_row, const float* old_a, const float* old_b, const double* rec,
+                       const int* flag, int row0, int B, int capacity, const float* bat_a, const float* bat_b, int S, int C, int K,
+                       double* new_ssim, int* new_row, float* new_a, float* new_b, int* src, hipStream_t st);
 size_t freebits_workspace_bytes(int L);
 int launch_freebits_kl(const float* mu, long mu_pitch, const float* lv, long lv_pitch, int B, int L, const float* w_dev, float scale,
                        float lambda, float* out4, float* g_mu, float* g_lv, float* ws, size_t ws_bytes, hipStream_t st);
@@ -1118,6 +1123,18 @@ int ctvae_latent_accumulate(const float* mu, long mu_pitch, const float* logvar,
                             double* mu_sum, double* sig2_sum, double* cov_sum, int32_t* nonfinite, int32_t* rows, void* stream) {
   return launch_latent_accumulate(mu, mu_pitch, logvar, logvar_pitch, B, L, kl_sum, mu_sum, sig2_sum, cov_sum, nonfinite, rows,
                                   (hipStream_t)stream);
+}
+
+int ctvae_recon_record(const float* a, const float* b, int B, int S, int C, const double* consts, double* records, int32_t* flags,
+                       int row0, int capacity, void* stream) {
+  return launch_recon_record(a, b, B, S, C, consts, records, flags, row0, capacity, (hipStream_t)stream);
+}
+
+int ctvae_recon_worst(const double* old_ssim, const int32_t* old_row, const float* old_a, const float* old_b, const double* records,
+                      const int32_t* flags, int row0, int B, int capacity, const float* batch_a, const float* batch_b, int S, int C,
+                      int K, double* new_ssim, int32_t* new_row, float* new_a, float* new_b, int32_t* source, void* stream) {
+  return launch_recon_worst(old_ssim, old_row, old_a, old_b, records, flags, row0, B, capacity, batch_a, batch_b, S, C, K, new_ssim,
+                            new_row, new_a, new_b, source, (hipStream_t)stream);
 }
 
 size_t ctvae_freebits_workspace_bytes(int L) { return freebits_workspace_bytes(L); }

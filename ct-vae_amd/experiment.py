@@ -127,6 +127,21 @@ gain ``kld_weight`` (the host's value, no copy), ``KLD_free_bits`` and ``KLD_flo
 ``state_dict()`` carries ``"kl": {schedule, free_bits}``; a full resume under other values is refused by name, the weight itself
 needs no state.  Refused when the experiment is built: either key on another model.  Without the keys there is no buffer, no
 launch, no log key and no entry.
+
+``exp_params.recon_stats`` (a bool; with ``recon_stats_range``, the data range R, a float > 0, default 1.0, and ``recon_stats_worst``,
+an integer 0 <= K <= 32, default 8): the reconstruction quality per validation image, by ``reconstats.ReconStats`` on rank 0.
+``_validate`` resets it, every ``validation_step`` hands it the pair ``BaseVAE.reconstruction_pair`` returns (one
+``ctvae_recon_record`` launch, and the two of ``ctvae_recon_worst`` when K > 0; eager like all of validation, no device-to-host
+copy), and behind the validation steps ``write_recon_stats`` makes the one copy and adds ``val_recon_psnr`` / ``_ssim`` / ``_mae`` /
+``_max_err`` / ``_psnr_p05`` / ``_ssim_p05`` / ``_psnr_min`` / ``_ssim_min`` / ``_rows`` / ``_nonfinite`` / ``_exact`` to the epoch record and
+the JSONL log (what has no image to stand on is left out), and with a ``sample_dir`` writes
+``Recon/recon_stats_<name>_Epoch_<e>.npz`` and, for K > 0, ``Recon/worst_<name>_Epoch_<e>.png``.  CT-MCQ-VAE has two accumulators,
+keyed by the batch's mode: its keys and file stems carry ``_base`` / ``_action`` (in action mode the target is ``input_y``), and
+causal batches, which have no picture pair, feed none.  Under ``ema_eval`` the numbers describe the averaged weights; with several
+ranks they are rank 0's own rows; no collective is added.  It draws nothing and writes no model state, so training is bit for
+bit the same with and without it.  Refused when the experiment is built: a bad value, a dependent key without the main one,
+and IWAE / MIWAE, whose ``forward`` hands out [B, S, C, H, W] samples.  Without the key there is no buffer, no launch, no file and
+no log key.
 """
 import contextlib
 import json
@@ -143,6 +158,8 @@ from .klcontrol import KLControl, kl_settings, needs_served_model, serves as kl_
 from .latentstats import (LATENT_DIR, LatentStats, has_gaussian_posterior, latent_stats_setting, needs_gaussian_posterior,
                           record as latent_record, write_files as write_latent_files)
 from .metrics import _eval_mode as eval_mode
+from .reconstats import (RECON_DIR, ReconStats, recon_settings, record as recon_record, refuses_model as recon_refuses_model,
+                         summarize as recon_summarize, write_files as write_recon_files)
 from .optim import (CodebookEMA, CodebookUsage, ExponentialLR, FlatAdam, GradientTracker, WeightEMA, absent_grad_setting,
                     accumulate_setting, clip_settings, codebook_ema_serves, codebook_ema_settings, codebook_record,
                     codebook_settings, ema_settings, track_grad_norm_setting, watch_settings, with_window_ends)
@@ -330,6 +347,20 @@ class VAEXperiment:
                 raise ValueError(needs_gaussian_posterior(vae_model))
             if self._rank0():
                 self.val_latents = LatentStats(vae_model.latent_dim, next(vae_model.parameters()).device)
+        # reconstruction quality (reconstats.ReconStats): validated on every rank, built on rank 0 only; CT-MCQ-VAE gets one
+        # accumulator per picture mode
+        self.recon_stats, self.recon_range, self.recon_worst = recon_settings(params)
+        self.val_recon = None                   # {key suffix: ReconStats}; "" for every model but CT-MCQ-VAE
+        self._observing_recon = False           # True inside the validation steps of _validate() only
+        if self.recon_stats:
+            why = recon_refuses_model(vae_model)
+            if why is not None:
+                raise ValueError(why)
+            if self._rank0():
+                from .models.ct_mcq_vae import CTMCQVAE
+                dev = next(vae_model.parameters()).device
+                suffixes = ("_base", "_action") if isinstance(vae_model, CTMCQVAE) else ("",)
+                self.val_recon = {sfx: ReconStats(dev, self.recon_range, self.recon_worst) for sfx in suffixes}
         # KL weight schedule / free bits (klcontrol.KLControl): on every rank, the same weight from global_step
         schedule, free_bits = kl_settings(params)
         self.kl = None
@@ -381,7 +412,17 @@ class VAEXperiment:
             val_loss = self.model.loss_function(*results, M_N=1.0, optimizer_idx=optimizer_idx, batch_idx=batch_idx)
             if self._observing_latents:        # latent_stats: one launch, nothing comes back to the host before the epoch ends
                 self.val_latents.observe(*self.model.gaussian_posterior(results))
+            if self._observing_recon:          # recon_stats: one launch (three with a worst set), nothing comes back either
+                pair = self.model.reconstruction_pair(results)
+                if pair is not None:
+                    self.val_recon[self._recon_suffix(results)].observe(*pair)
         return self.log_all(val_loss, batch_size=real_img.size(0), validation=True, force=True)
+
+    def _recon_suffix(self, results) -> str:
+        """Which accumulator a batch with a picture pair feeds: CT-MCQ-VAE's by the batch's mode, else the only one."""
+        if "" in self.val_recon:
+            return ""
+        return "_" + results[4]["mode"]
 
     def metric_func(self, x):
         x = x.to(next(self.model.parameters()).device)
@@ -839,6 +880,25 @@ class VAEXperiment:
             self.log_file.flush()
         return rec
 
+    def write_recon_stats(self, accumulators, epoch: int) -> dict:
+        """What ``recon_stats`` leaves of one validation epoch: per accumulator one copy, the ``val_recon_*`` scalars
+        (``reconstats.summarize``; what has no image to stand on is left out), also as one JSONL line, and with a ``sample_dir`` and
+        at least one row ``Recon/recon_stats_<name>[_<mode>]_Epoch_<e>.npz`` and, with a worst set,
+        ``Recon/worst_<name>[_<mode>]_Epoch_<e>.png``."""
+        rec = {}
+        for sfx, acc in accumulators.items():
+            res = acc.result()
+            rec.update(recon_record(recon_summarize(res["records"], res["flags"], acc.R), suffix=sfx))
+            if self.sample_dir is not None and len(res["flags"]):
+                d = os.path.join(self.sample_dir, RECON_DIR)
+                os.makedirs(d, exist_ok=True)
+                write_recon_files(res, os.path.join(d, f"recon_stats_{self.run_name}{sfx}_Epoch_{epoch}.npz"),
+                                  os.path.join(d, f"worst_{self.run_name}{sfx}_Epoch_{epoch}.png") if acc.K > 0 else None)
+        if self.log_file is not None:
+            self.log_file.write(json.dumps({**rec, "step": self.global_step}) + "\n")
+            self.log_file.flush()
+        return rec
+
     def _load_codebook_state(self, entry):
         """Full resume under ``codebook_restart_every``: the window's counts, the restart ordinal and the total come back, so a
         run resumed inside a window continues bit for bit; other ``every`` / ``min_count`` than the checkpoint's are refused."""
@@ -880,6 +940,11 @@ class VAEXperiment:
         if latents is not None:
             latents.zero()
             self._observing_latents = True
+        recon = self.val_recon                 # recon_stats: rank 0's own validation rows too
+        if recon is not None:
+            for acc in recon.values():
+                acc.reset()
+            self._observing_recon = True
         try:
             for i, batch in enumerate(val_batches()):
                 r = self.validation_step(batch, i)
@@ -893,6 +958,7 @@ class VAEXperiment:
             if usage is not None:
                 self.model.vq_layer.usage_observer = None
             self._observing_latents = False
+            self._observing_recon = False
         rec.update({k: v / max(cnt, 1) for k, v in sums.items()})
         if stats is not None:
             rec.update(self.write_graphs(stats, epoch))
@@ -900,6 +966,8 @@ class VAEXperiment:
             rec.update(self.write_codebook_stats(usage))
         if latents is not None:
             rec.update(self.write_latent_stats(latents, epoch))
+        if recon is not None:
+            rec.update(self.write_recon_stats(recon, epoch))
         rec.update(self.validation_metrics(epoch))
         if self.val_sampling and self.sample_dir is not None and test_batches is not None and self._rank0():
             first = next(iter(test_batches()), None)

@@ -3100,3 +3100,107 @@ def latent_accumulate(mu, log_var, state):
     m, pm = _latent_rows(mu.detach(), L)
     v, pv = _latent_rows(log_var.detach(), L)
     native.call("ctvae_latent_accumulate", m.data_ptr(), pm, v.data_ptr(), pv, B, L, *(state[name].data_ptr() for name, _, _ in LATENT_STATE))
+
+
+# ---------------------------------------------------------------------------------------------------
+# reconstruction quality per image (csrc/reconstat.hip; reconstats.ReconStats)
+# ---------------------------------------------------------------------------------------------------
+RECON_MIN_S, RECON_MAX_S = 11, 64        # what ctvae_recon_record covers: one 11-tap window at least, the LDS ring's width at most
+RECON_MAX_K = 32                         # slots of the worst set
+RECON_COLUMNS = ("mse", "mae", "max_err", "ssim")
+
+
+def recon_consts(data_range: float):
+    """The 13 doubles ``ctvae_recon_record`` reads on the host: the window of Wang et al. 2004, g[t] ~ exp(-(t-5)^2 / (2 * 1.5^2))
+    normalised to sum 1, then C1 = (0.01 R)^2 and C2 = (0.03 R)^2.  Python floats: float64."""
+    import ctypes
+    import math
+    R = float(data_range)
+    if not (R > 0 and R < float("inf")):
+        raise ValueError(f"recon_stats_range must be a finite number > 0, got {data_range!r}")
+    g = [math.exp(-((t - 5) ** 2) / (2.0 * 1.5 ** 2)) for t in range(11)]
+    total = math.fsum(g)
+    return (ctypes.c_double * 13)(*[v / total for v in g], (0.01 * R) ** 2, (0.03 * R) ** 2)
+
+
+def _recon_nhwc(what, name, x):
+    """The NHWC memory under a logical [B, C, S, S] fp32 device tensor: its own when the channels-last view is contiguous, else
+    a contiguous copy."""
+    if not torch.is_tensor(x) or x.dtype != torch.float32 or x.dim() != 4:
+        raise ValueError(f"{what}: {name} must be a torch.float32 [B, C, S, S] tensor, got "
+                         f"{getattr(x, 'dtype', type(x).__name__)} {tuple(getattr(x, 'shape', ()))}")
+    v = x.detach().permute(0, 2, 3, 1)
+    return v if v.is_contiguous() else v.contiguous()
+
+
+def _recon_pair(what, recons, target):
+    a, b = _recon_nhwc(what, "recons", recons), _recon_nhwc(what, "target", target)
+    if a.shape != b.shape:
+        raise ValueError(f"{what}: recons {tuple(recons.shape)} and target {tuple(target.shape)} must have one shape")
+    B, S, S2, C = a.shape
+    if S != S2 or not RECON_MIN_S <= S <= RECON_MAX_S or C < 1:
+        raise ValueError(f"{what}: pictures [B, C, S, S] need {RECON_MIN_S} <= S <= {RECON_MAX_S} and C >= 1, got "
+                         f"{tuple(recons.shape)}")
+    return a, b, B, S, C
+
+
+def _recon_rows(what, records, flags, row0, B):
+    _req_dense(what, "records", records, torch.float64)
+    _req_dense(what, "flags", flags, torch.int32)
+    cap = flags.numel()
+    if records.dim() != 2 or tuple(records.shape) != (cap, 4) or flags.dim() != 1:
+        raise ValueError(f"{what}: records [capacity, 4] and flags [capacity] do not fit: {tuple(records.shape)}, {tuple(flags.shape)}")
+    row0 = int(row0)
+    if row0 < 0 or row0 + B > cap:
+        raise ValueError(f"{what}: rows [{row0}, {row0 + B}) leave the capacity {cap}")
+    return row0, cap
+
+
+def recon_record(recons, target, consts, records, flags, row0):
+    """``ctvae_recon_record``: the per-image mse, mae, max_err and ssim of the pairs (recons, target) -- logical [B, C, S, S] fp32
+    device tensors, read as the NHWC memory underneath (a contiguous copy where it is not one) -- into rows [row0, row0 + B) of
+    ``records`` (float64 [capacity, 4]) and ``flags`` (int32 [capacity]).  ``consts``: ``recon_consts(R)``.  One launch, no host
+    synchronisation.  Returns the two NHWC tensors (``recon_worst`` reads the same memory)."""
+    what = "recon_record"
+    a, b, B, S, C = _recon_pair(what, recons, target)
+    row0, cap = _recon_rows(what, records, flags, row0, B)
+    _req_cuda(a, b, records, flags)
+    if B:
+        native.call("ctvae_recon_record", a.data_ptr(), b.data_ptr(), B, S, C, consts, records.data_ptr(), flags.data_ptr(), row0, cap)
+    return a, b
+
+
+def recon_worst_state(K, S, C, device):
+    """One side of the worst set's ping-pong state, empty: ``ssim`` float64 [K], ``row`` int32 [K] (-1: empty), ``a`` / ``b`` fp32
+    [K, S, S, C] (NHWC), ``source`` int32 [K]."""
+    K = int(K)
+    if not 1 <= K <= RECON_MAX_K:
+        raise ValueError(f"recon_worst_state: 1 <= K <= {RECON_MAX_K}, got {K}")
+    return {"ssim": torch.zeros(K, dtype=torch.float64, device=device), "row": torch.full((K,), -1, dtype=torch.int32, device=device),
+            "a": torch.zeros(K, S, S, C, dtype=torch.float32, device=device), "b": torch.zeros(K, S, S, C, dtype=torch.float32, device=device),
+            "source": torch.full((K,), -1, dtype=torch.int32, device=device)}
+
+
+def recon_worst(old, new, records, flags, row0, a_nhwc, b_nhwc):
+    """``ctvae_recon_worst`` behind ``recon_record`` of the same batch: the K worst of ``old``'s slots and the batch's rows into
+    ``new`` (two ``recon_worst_state`` sides, never the same one).  a_nhwc, b_nhwc: what ``recon_record`` returned.  Two launches."""
+    what = "recon_worst"
+    if old is new or any(old[k].data_ptr() == new[k].data_ptr() for k in ("ssim", "row", "a", "b")):
+        raise ValueError(f"{what}: old and new must be the two sides of the state, nothing is merged in place")
+    K, S, _, C = old["a"].shape
+    for side in (old, new):
+        for k, dtype in (("ssim", torch.float64), ("row", torch.int32), ("a", torch.float32), ("b", torch.float32), ("source", torch.int32)):
+            _req_dense(what, k, side[k], dtype)
+        if tuple(side["a"].shape) != (K, S, S, C) or tuple(side["b"].shape) != (K, S, S, C) or side["ssim"].numel() != K \
+                or side["row"].numel() != K or side["source"].numel() != K:
+            raise ValueError(f"{what}: the two sides must be recon_worst_state(K, S, C) of one K, S, C")
+    for name, t in (("a_nhwc", a_nhwc), ("b_nhwc", b_nhwc)):
+        _req_dense(what, name, t, torch.float32)
+        if t.dim() != 4 or tuple(t.shape[1:]) != (S, S, C) or t.size(0) != a_nhwc.size(0):
+            raise ValueError(f"{what}: {name} must be [B, {S}, {S}, {C}] NHWC, got {tuple(t.shape)}")
+    B = a_nhwc.size(0)
+    row0, cap = _recon_rows(what, records, flags, row0, B)
+    _req_cuda(a_nhwc, b_nhwc, records, flags, *old.values(), *new.values())
+    native.call("ctvae_recon_worst", old["ssim"].data_ptr(), old["row"].data_ptr(), old["a"].data_ptr(), old["b"].data_ptr(),
+                records.data_ptr(), flags.data_ptr(), row0, B, cap, a_nhwc.data_ptr(), b_nhwc.data_ptr(), S, C, K,
+                new["ssim"].data_ptr(), new["row"].data_ptr(), new["a"].data_ptr(), new["b"].data_ptr(), new["source"].data_ptr())

@@ -34,6 +34,16 @@ class BaseVAE(FlatParamMixin, nn.Module):
         None for every other model."""
         return None
 
+    def reconstruction_pair(self, results: List[Tensor]):
+        """(recons, target) of ``forward``'s results as two [B, C, S, S] tensors (reconstats.py), or None when the batch has no
+        picture pair.  The default: ``results[0], results[1]`` when both are 4-D and of one shape."""
+        if len(results) < 2:
+            return None
+        recons, target = results[0], results[1]
+        if not (hasattr(recons, "dim") and hasattr(target, "dim")) or recons.dim() != 4 or recons.shape != target.shape:
+            return None
+        return recons, target
+
     @abstractmethod
     def forward(self, *inputs: Tensor) -> Tensor:
         pass

@@ -168,6 +168,14 @@ class CTMCQVAE(BaseVAE):
             action = action.to(input.device)
         return CTMCQVAE.FORWARD_MODES[mode](self, input=input, input_y=input_y, action=action)
 
+    def reconstruction_pair(self, results):
+        """Base mode: (reconstruction, input).  Action mode: (predicted next picture, ``input_y``), so the numbers measure the
+        prediction.  Causal mode: None -- ``results[0]`` is action logits there."""
+        metrics = results[4] if len(results) > 4 and isinstance(results[4], dict) else {}
+        if metrics.get("mode") == "causal":
+            return None
+        return super().reconstruction_pair(results)
+
     def loss_function(self, *args, **kwargs) -> dict:
         """recons + vq + gamma*ct (ct_mcq_vae.py:594-620); causal mode is a classification (cross-entropy)."""
         recons, input, vq_loss, ct_loss = args[0], args[1], args[2], args[3]

@@ -63,6 +63,15 @@ MSSIMVAE, LogCoshVAE and BetaVAE with ``loss_type: 'H'``; the training records g
 ``KLD_floored_dims``, validation is unchanged, and the checkpoint gains ``trainer['kl']``: a full resume under other settings is
 refused, ``load_weights_only`` starts the schedule at step 0, a run without the keys ignores the entry.  A refused value or model
 is a SystemExit that names ``exp_params.kld_schedule`` or ``exp_params.kld_free_bits``.
+``exp_params.recon_stats: true`` (with ``recon_stats_range``, the data range R of the pictures, a float > 0, default 1.0, and
+``recon_stats_worst``, an integer 0 <= K <= 32, default 8) adds the reconstruction quality per validation image to every validation
+epoch: ``val_recon_psnr`` / ``_ssim`` / ``_mae`` / ``_max_err``, the 5th percentiles and minima ``_psnr_p05`` / ``_ssim_p05`` / ``_psnr_min``
+/ ``_ssim_min`` and the counts ``_rows`` / ``_nonfinite`` / ``_exact`` in the epoch records and ``metrics_rank0.jsonl``, and
+``Recon/recon_stats_<name>_Epoch_<e>.npz`` (the per-image values) with ``Recon/worst_<name>_Epoch_<e>.png`` (the K worst targets over
+their reconstructions) in the log directory (experiment.py, reconstats.py); CT-MCQ-VAE reports its base and action batches apart,
+under ``_base`` / ``_action``.  ``python -m ctvae_amd.recon_stats`` does the same for a checkpoint.  The top-k checkpoints are still
+chosen by ``val_Reconstruction_Loss``.  A bad value, a dependent key without ``recon_stats``, and IWAE / MIWAE are a SystemExit
+that names ``exp_params.recon_stats`` (or the dependent key).
 """
 import argparse
 import json
@@ -338,6 +347,24 @@ def exp_latent_stats(config) -> bool:
     return on
 
 
+def exp_recon_stats(config) -> tuple:
+    """``exp_params.recon_stats`` / ``recon_stats_range`` / ``recon_stats_worst`` as ``(on, R, K)``.  A refused value, a dependent key
+    without the main one, and a model that hands out several reconstructions per image (IWAE, MIWAE) are a SystemExit that
+    names the key."""
+    from . import reconstats
+    try:
+        on, R, K = reconstats.recon_settings(config['exp_params'])
+    except ValueError as e:
+        raise SystemExit(f"exp_params.{e}")
+    name = config['model_params'].get('name')
+    cls = vae_models.get(name)
+    if on:
+        why = f"recon_stats: model_params.name {name!r} is not a model" if cls is None else reconstats.refuses_model(cls, name=repr(name))
+        if why is not None:
+            raise SystemExit(f"exp_params.{why} (model_params.name)")
+    return on, R, K
+
+
 def exp_kl(config):
     """``exp_params.kld_schedule`` / ``kld_free_bits`` as ``(schedule, free_bits)`` (both None: off).  A refused value, and either key
     on a model whose loss is not recon + c * M_N * KL (BetaVAE's default ``loss_type: 'B'`` among them), are a SystemExit that
@@ -396,6 +423,7 @@ def main(argv=None):
     cb_ema_decay, cb_ema_eps = exp_codebook_ema(config)    # refused here too; VAEXperiment reads the keys itself
     exp_latent_stats(config)                 # refused here, before a device is touched; VAEXperiment reads the key itself
     kl_schedule, kl_free_bits = exp_kl(config)             # likewise
+    recon_on, _, _ = exp_recon_stats(config)               # likewise
 
     rank =int(os.environ.get("RANK", "0"))
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -451,6 +479,9 @@ def main(argv=None):
             os.makedirs(os.path.join(log_dir, d), exist_ok=True)
     if val_graphs and rank == 0:
         os.makedirs(os.path.join(log_dir, VAEXperiment.GRAPH_DIR), exist_ok=True)
+    if recon_on and rank == 0:
+        from .reconstats import RECON_DIR
+        os.makedirs(os.path.join(log_dir, RECON_DIR), exist_ok=True)
     exp = VAEXperiment(model, config['exp_params'], ddp=ddp, log_file=log_file, gradient_clip_val=tp.get('gradient_clip_val'),
                        gradient_clip_algorithm=tp.get('gradient_clip_algorithm'), val_sampling=val_sampling, sample_dir=log_dir,
                        run_name=config['logging_params'].get('name', mp['name']), val_graphs=val_graphs,

@@ -617,6 +617,35 @@ int ctvae_graph_accumulate(const float* adj, const int32_t* group, const float* 
 int ctvae_latent_accumulate(const float* mu, long mu_pitch, const float* logvar, long logvar_pitch, int B, int L, double* kl_sum,
                             double* mu_sum, double* sig2_sum, double* cov_sum, int32_t* nonfinite, int32_t* rows, void* stream);
 
+/* Reconstruction quality per image (exp_params.recon_stats; reconstats.py: ReconStats).  a (the reconstruction) and b (the target)
+ * are fp32 NHWC [B][S][S][C], 11 <= S <= 64, C >= 1.  consts: 13 doubles in HOST memory, read before the call returns: the 11-tap
+ * window g (Wang et al. 2004: g[t] ~ exp(-(t-5)^2 / (2 * 1.5^2)), normalised to sum 1), then C1 = (0.01 R)^2 and C2 = (0.03 R)^2
+ * for the data range R, both > 0.  Image i writes row row0 + i of records [capacity][4] double and of flags [capacity] int32:
+ *   records[.][0] mse   the mean over all S*S*C elements of (a - b)^2, in double
+ *   records[.][1] mae   the mean of |a - b|
+ *   records[.][2] max   the largest |a - b|
+ *   records[.][3] ssim  the mean over the (S-10)^2 VALID window positions of every channel of
+ *                       (2 mu_a mu_b + C1)(2 s_ab + C2) / ((mu_a^2 + mu_b^2 + C1)(s_aa + s_bb + C2)),
+ *                       mu_x = G*x, s_xy = G*(x y) - mu_x mu_y, G = g (x) g; no padding.  Identical pictures give exactly 1.0
+ *   flags[.]            1 when any element of either picture is NaN or +-inf, else 0
+ * One workgroup per image, a fixed summation order, no atomics: a row's bits do not depend on B, on row0 or on the other images
+ * of the batch.  One launch, no host synchronisation.  B == 0 is a successful no-op; B < 0, another S or C, row0 < 0,
+ * row0 + B > capacity, a constant that is not > 0 or a NULL pointer returns -22 and launches nothing. */
+int ctvae_recon_record(const float* a, const float* b, int B, int S, int C, const double* consts, double* records, int32_t* flags,
+                       int row0, int capacity, void* stream);
+
+/* The running set of the K worst images (1 <= K <= 32) behind ctvae_recon_record of the same batch.  The state is K slots --
+ * ssim [K] double, row [K] int32 (the global row; -1: the slot is empty), and both pictures [K][S][S][C] fp32 -- held twice:
+ * the call reads the old side and writes the new side, nothing moves in place (a pointer shared by the two sides returns -22).
+ * Select (one launch): the old slots and rows [row0, row0 + B) of records whose flag is 0 are ordered by (ssim ascending, row
+ * ascending) -- the rows are distinct, so ties are decided -- and the first K fill new_ssim / new_row; the slots behind the last
+ * candidate are empty; source [K] int32 says where a slot comes from: j in [0, K) old slot j, K + i batch image i, -1 empty.
+ * Gather (one launch): the pictures follow word for word; an empty slot's pictures are zeroed.  After any cut of a stream of
+ * images into batches the state equals the first K of a sort of the whole stream. */
+int ctvae_recon_worst(const double* old_ssim, const int32_t* old_row, const float* old_a, const float* old_b, const double* records,
+                      const int32_t* flags, int row0, int B, int capacity, const float* batch_a, const float* batch_b, int S, int C,
+                      int K, double* new_ssim, int32_t* new_row, float* new_a, float* new_b, int32_t* source, void* stream);
+
 /* The Gaussian KL term with free bits and a weight that lives in device memory (exp_params.kld_free_bits / kld_schedule;
  * klcontrol.py, kernels.FreeBitsKL).  mu and logvar are fp32 [B][L] with a row pitch each, as for ctvae_latent_accumulate.
  *   t_bd = 1 + lv - m^2 - e^lv in fp32 (ctvae_loss_forward's expression);  m_d = -0.5 * (sum_b t_bd) / B, the sum in double with
