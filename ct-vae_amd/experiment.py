@@ -23,6 +23,21 @@ eagerly: one graph per signature serves every position in a window.  Under DDP a
 collective at all; the one that ends it sends the merged block flags (skip modes) and the window's sum, and steps with
 ``grad_scale = 1 / (world * k)``.  ``ddp.SplitBackward``'s ranged exchange is refused in this mode.
 
+The step's tail.  ``finish_batch`` follows every backward pass, captured, eager or accumulated: the stash or the step (nothing
+when Adam was part of the captured body), and behind a batch that ends its window ``_after_optimizer_step``, "the tail" below:
+``track_gradients()`` (the flat buffer still holds what was stepped), ``codebook_update()`` (it overwrites the codebooks Adam
+moved), ``ema_update()`` (the weight average sees the codebook the step ends with), ``codebook_restart()`` (a restarted code gets
+N = 1 and M = its row; the weight average goes on towards the new row), then ``global_step += 1``: all four see the number of
+the step that ran.  The tail is eager, never captured (decays are by-value kernel arguments, which a captured launch would
+freeze; the dead list is formed on the host), and runs once per optimizer step, so once per accumulation window.
+
+The validation order.  ``_validate`` arms every report the run has (a context each: reset or rebuilt, then observing; disarmed
+in a ``finally``), runs the validation steps, and collects in the key order of the epoch record: the steps' means,
+``write_graphs``, ``write_codebook_stats``, ``write_latent_stats``, ``write_recon_stats``, ``validation_metrics``, and last
+``sample_images``.  The reports are eager like all of validation, make their one device-to-host copy behind the steps, are rank
+0's own rows (no collective) and, under ``ema_eval``, describe the averaged weights; a ``validation_step`` outside ``_validate``
+observes nothing.
+
 ``val_metric`` (a ``metrics.MetricSet``): the reference recomputes the disentanglement metrics inside EVERY validation batch
 and lets Lightning average the copies (experiment.py:72-74).  That is a cost, not a semantic -- the metric does not read the
 batch -- so ``fit()`` computes it ONCE per validation epoch, after the validation batches, on rank 0 only and without a
@@ -47,48 +62,42 @@ the causal-mode batches' hypothesised actions are not observed).  Afterwards ran
 ``Graphs/adjacency_<name>_Epoch_<e>.png`` -- the mean adjacency of every group that had rows, group 0 first, one tile each --
 and ``Graphs/mask_<name>_Epoch_<e>.png`` -- the mean mask of every action that had rows as an h x w picture -- under
 ``sample_dir``, and adds ``val_graph_edges_<group>``, the mean number of edges above 0.5 per graph, to the epoch record and the
-JSONL log.  Validation is eager, the captured training steps never see the observer, and it draws nothing: the run's
-trajectory is the same with and without it.  With several ranks the pictures and numbers are rank 0's own validation rows; the
-graphs are not reduced across ranks.
+JSONL log.  The captured training steps never see the observer, and it draws nothing: the run's trajectory is the same with
+and without it.
 
 ``track_grad_norm`` (Lightning's Trainer flag: a norm type > 0 or 'inf'; None / -1 off) and ``watch_gradients`` with
 ``watch_log_freq`` (the reference's ``wb_logger.watch(model, log_freq=500)``, run.py:55; off by default): gradient tracking by
-``optim.GradientTracker``, which ``track_gradients()`` drives eagerly right behind the optimizer step of a batch that ends a
-window -- never inside a captured graph, and only on tracking steps: the norm record joins ``log_file`` where the training
-scalars are logged (``global_step % log_every == 0``), the histogram record goes to ``grad_log_file`` every ``watch_log_freq``
-optimizer steps.  No Adam kernel writes the gradient, so at that point the optimizer's slice of the flat buffer holds exactly
-what was stepped, before any scale; with the step's ``grad_scale`` 1 / (world * k) the tracker sees the averaged pre-clip
-gradient, where Lightning's ``_track_grad_norm`` sits.  Rank 0 measures and writes (three launches, one device-to-host copy);
-the other ranks build no tracker.  The run ends bit for bit as it does without tracking; without both keys there is no tracker,
-no launch and no key.
+``optim.GradientTracker``, which ``track_gradients()`` drives first in the tail (above), and only on tracking steps: the norm
+record joins ``log_file`` where the training scalars are logged (``global_step % log_every == 0``), the histogram record goes to
+``grad_log_file`` every ``watch_log_freq`` optimizer steps.  No Adam kernel writes the gradient, so at that point the optimizer's
+slice of the flat buffer holds exactly what was stepped, before any scale; with the step's ``grad_scale`` 1 / (world * k) the
+tracker sees the averaged pre-clip gradient, where Lightning's ``_track_grad_norm`` sits.  Rank 0 measures and writes (three
+launches, one device-to-host copy); the other ranks build no tracker.  The run ends bit for bit as it does without tracking;
+without both keys there is no tracker, no launch and no key.
 
 ``exp_params.ema_decay`` (a float, 0 < d < 1; absent: off) with ``ema_warmup`` (default false) and ``ema_eval`` (default true): an
 exponential moving average of the weights the optimizer steps, kept by ``optim.WeightEMA`` on the optimizer's slice of the flat
-parameter buffer.  ``ema_update()`` runs once per optimizer step, eagerly, right behind it and next to ``track_gradients()`` --
-never inside a captured graph (the decay is a by-value kernel argument, which a captured launch would freeze), once per window
-under ``accumulate_grad_batches``, and on every rank without a collective: the stepped parameters are identical on all ranks, so
-the averages are too.  With ``ema_eval`` the validation part of ``fit()`` -- the validation steps, ``write_graphs``,
-``validation_metrics`` and ``sample_images`` -- runs with the averaged weights swapped into the flat buffer
-(``WeightEMA.swapped_in``): the epoch record's ``val_*`` values, and what run.py chooses by them, describe the averaged weights;
-BatchNorm running statistics and all random streams are the live ones, and the live weights come back bit for bit, so the run
-trains exactly as it does without the key.  ``state_dict()`` carries ``"ema": {decay, warmup, updates}``; the buffer itself
-travels as weights (``ema_model_state_dict`` / ``load_ema_model_state_dict``, the checkpoint's ``ema_state_dict``).  Without
-``ema_decay`` there is no buffer, no launch and no entry.
+parameter buffer.  ``ema_update()`` is part of the tail (above), on every rank without a collective: the stepped parameters are
+identical on all ranks, so the averages are too.  With ``ema_eval`` all of ``_validate`` runs with the averaged weights swapped
+into the flat buffer (``WeightEMA.swapped_in``): the epoch record's ``val_*`` values, and what run.py chooses by them, describe
+the averaged weights; BatchNorm running statistics and all random streams are the live ones, and the live weights come back
+bit for bit, so the run trains exactly as it does without the key.  ``state_dict()`` carries ``"ema": {decay, warmup, updates}``
+(``WeightEMA.state_dict(buffer=False)``); the buffer itself travels as weights (``ema_model_state_dict`` /
+``load_ema_model_state_dict``, the checkpoint's ``ema_state_dict``).  Without ``ema_decay`` there is no buffer, no launch and no entry.
 
 ``exp_params.codebook_stats`` (a bool) and ``exp_params.codebook_restart_every`` (an integer N >= 1; with
 ``codebook_restart_min_count``, default 1, and ``codebook_restart_pool``, default 1024): codebook usage of the models with a
-``vq_layer`` quantiser, by ``optim.CodebookUsage`` as the quantiser's ``usage_observer`` -- attached and detached with a
-``finally``, in the style of ``graph_observer``.  The validation counter (rank 0 only) observes the validation steps alone and
-adds ``val_codebook_perplexity_<i>`` / ``_usage_<i>`` / ``_dead_<i>`` and their means to the epoch record and the JSONL log;
-``sample_images``, ``validation_metrics``, rollouts and the tools run without an observer.  The training counter observes the
-training batches of ``fit()``: its launch is part of the forward, inside the captured body when the step is captured and
-identical in eager steps, once per micro-batch.  ``codebook_restart()`` runs eagerly behind the optimizer step that makes
-``global_step`` a multiple of N, next to ``track_gradients()`` / ``ema_update()`` and never captured (its docstring has the
-sequence); the weight average is not special-cased and goes on averaging towards a restarted row, and the per-block Adam
-counters of the skip modes are untouched.  ``state_dict()`` carries ``"codebook": {every, min_count, pool, counts, ordinal,
-restarted, valid_rows}``; a full resume restores it and refuses other ``every`` / ``min_count``.  Refused when the experiment is
-built: either key on a model without such a quantiser, and restarts when ``update_parameters`` leaves the codebooks outside the
-optimizer's slice.  Without the keys there is no buffer, no launch, no log key and no entry.
+``vq_layer`` quantiser, by ``optim.CodebookUsage`` as the quantiser's ``usage_observer``.  The validation counter (rank 0 only) is
+one of the reports of ``_validate`` (above): it observes the validation steps alone and adds ``val_codebook_perplexity_<i>`` /
+``_usage_<i>`` / ``_dead_<i>`` and their means to the epoch record and the JSONL log; ``sample_images``, ``validation_metrics``,
+rollouts and the tools run without an observer.  The training counter observes the training batches of ``fit()``: its launch is
+part of the forward, inside the captured body when the step is captured and identical in eager steps, once per micro-batch.
+``codebook_restart()`` closes the tail (above) of the optimizer step that makes ``global_step`` a multiple of N (its docstring
+has the sequence); the weight average is not special-cased, and the per-block Adam counters of the skip modes are untouched.
+``state_dict()`` carries ``"codebook": {every, min_count, pool, counts, ordinal, restarted, valid_rows}``; a full resume restores
+it and refuses other ``every`` / ``min_count``.  Refused when the experiment is built: either key on a model without such a
+quantiser, and restarts when ``update_parameters`` leaves the codebooks outside the optimizer's slice.  Without the keys there
+is no buffer, no launch, no log key and no entry.
 
 ``exp_params.codebook_ema_decay`` (a float, 0 < g < 1; absent: off) with ``codebook_ema_eps`` (default 1e-5): EMA codebooks (van den
 Oord et al. 2017, appendix A.1) for the models with a ``vq_layer`` quantiser, by ``optim.CodebookEMA``.  With the key the
@@ -96,9 +105,7 @@ quantiser's ``ema`` is set for good -- ``VQ_Loss`` is the commitment term alone,
 training and validation records alike, and no codebook gradient is formed: the codebooks' block of the flat gradient buffer is an
 absent block -- and ``CodebookEMA.observe`` is its ``ema_observer`` around the training batches of ``fit()`` only
 (``_counting_training_codes``): one statistics call per index search, part of the forward, inside the captured body when the step
-is captured.  ``codebook_update()`` runs eagerly behind every optimizer step, once per window under ``accumulate_grad_batches``,
-in the order ``track_gradients()``, ``codebook_update()``, ``ema_update()`` (the weight average sees the codebook the step ends
-with), ``codebook_restart()`` (a restarted code gets N = 1, M = its row).  Under DDP the window accumulators are SUM-reduced first:
+is captured.  ``codebook_update()`` is part of the tail (above).  Under DDP the window accumulators are SUM-reduced first:
 one small collective per optimizer step, none inside a window, and all ranks hold the same N, M and codebooks.  Records on
 logging steps: ``codebook_ema_min_cluster[_<i>]`` / ``codebook_ema_max_cluster[_<i>]``.  ``state_dict()`` carries ``"codebook_ema":
 {decay, eps, N, M, acc_n, acc_s, invalid}``; a full resume restores it and refuses another decay or eps, or a checkpoint
@@ -106,14 +113,13 @@ without the entry.  Refused when the experiment is built: the key on another mod
 the codebooks outside the optimizer's slice.  Without the key there is no buffer, no launch, no log key and no entry.
 
 ``exp_params.latent_stats`` (a bool): latent usage of the models with a Gaussian posterior (``BaseVAE.gaussian_posterior``), by
-``latentstats.LatentStats`` on rank 0.  ``_validate`` zeroes it, every ``validation_step`` hands it the batch's ``mu`` / ``log_var``
-views (one ``ctvae_latent_accumulate`` launch, eager like all of validation, no device-to-host copy), and behind the validation
-steps ``write_latent_stats`` makes the one copy and adds ``val_latent_kl_total`` / ``_active_units`` / ``_collapsed`` /
-``_mean_abs_corr`` / ``_gaussian_tc`` / ``_nonfinite`` / ``_rows`` to the epoch record and the JSONL log (what is undefined is left
-out), and with a ``sample_dir`` writes ``Latents/latent_stats_<name>_Epoch_<e>.npz`` and ``Latents/corr_<name>_Epoch_<e>.png``.
-Under ``ema_eval`` the numbers describe the averaged weights; with several ranks they are rank 0's own rows.  It draws nothing and
-writes no model state, so training is bit for bit the same with and without it.  Refused when the experiment is built: the key
-on a model whose hook returns None.  Without the key there is no buffer, no launch, no file and no log key.
+``latentstats.LatentStats`` on rank 0, a report of ``_validate`` (above).  Armed, it is zeroed and every ``validation_step`` hands
+it the batch's ``mu`` / ``log_var`` views (one ``ctvae_latent_accumulate`` launch); ``write_latent_stats`` adds
+``val_latent_kl_total`` / ``_active_units`` / ``_collapsed`` / ``_mean_abs_corr`` / ``_gaussian_tc`` / ``_nonfinite`` / ``_rows`` to the
+epoch record and the JSONL log (what is undefined is left out), and with a ``sample_dir`` writes
+``Latents/latent_stats_<name>_Epoch_<e>.npz`` and ``Latents/corr_<name>_Epoch_<e>.png``.  It draws nothing and writes no model
+state, so training is bit for bit the same with and without it.  Refused when the experiment is built: the key on a model
+whose hook returns None.  Without the key there is no buffer, no launch, no file and no log key.
 
 ``exp_params.kld_schedule`` (a mapping: linear warm-up or cyclical annealing of the KL weight) and ``exp_params.kld_free_bits`` (a
 float >= 0, nats per latent dimension): ``klcontrol.KLControl`` (its module docstring has the definitions), on the models whose
@@ -129,24 +135,21 @@ needs no state.  Refused when the experiment is built: either key on another mod
 launch, no log key and no entry.
 
 ``exp_params.recon_stats`` (a bool; with ``recon_stats_range``, the data range R, a float > 0, default 1.0, and ``recon_stats_worst``,
-an integer 0 <= K <= 32, default 8): the reconstruction quality per validation image, by ``reconstats.ReconStats`` on rank 0.
-``_validate`` resets it, every ``validation_step`` hands it the pair ``BaseVAE.reconstruction_pair`` returns (one
-``ctvae_recon_record`` launch, and the two of ``ctvae_recon_worst`` when K > 0; eager like all of validation, no device-to-host
-copy), and behind the validation steps ``write_recon_stats`` makes the one copy and adds ``val_recon_psnr`` / ``_ssim`` / ``_mae`` /
-``_max_err`` / ``_psnr_p05`` / ``_ssim_p05`` / ``_psnr_min`` / ``_ssim_min`` / ``_rows`` / ``_nonfinite`` / ``_exact`` to the epoch record and
-the JSONL log (what has no image to stand on is left out), and with a ``sample_dir`` writes
-``Recon/recon_stats_<name>_Epoch_<e>.npz`` and, for K > 0, ``Recon/worst_<name>_Epoch_<e>.png``.  CT-MCQ-VAE has two accumulators,
-keyed by the batch's mode: its keys and file stems carry ``_base`` / ``_action`` (in action mode the target is ``input_y``), and
-causal batches, which have no picture pair, feed none.  Under ``ema_eval`` the numbers describe the averaged weights; with several
-ranks they are rank 0's own rows; no collective is added.  It draws nothing and writes no model state, so training is bit for
-bit the same with and without it.  Refused when the experiment is built: a bad value, a dependent key without the main one,
-and IWAE / MIWAE, whose ``forward`` hands out [B, S, C, H, W] samples.  Without the key there is no buffer, no launch, no file and
-no log key.
+an integer 0 <= K <= 32, default 8): the reconstruction quality per validation image, by ``reconstats.ReconStats`` on rank 0,
+a report of ``_validate`` (above).  Armed, it is reset and every ``validation_step`` hands it the pair
+``BaseVAE.reconstruction_pair`` returns (one ``ctvae_recon_record`` launch, and the two of ``ctvae_recon_worst`` when K > 0);
+``write_recon_stats`` adds ``val_recon_psnr`` / ``_ssim`` / ``_mae`` / ``_max_err`` / ``_psnr_p05`` / ``_ssim_p05`` / ``_psnr_min`` /
+``_ssim_min`` / ``_rows`` / ``_nonfinite`` / ``_exact`` to the epoch record and the JSONL log (what has no image to stand on is left
+out), and with a ``sample_dir`` writes ``Recon/recon_stats_<name>_Epoch_<e>.npz`` and, for K > 0,
+``Recon/worst_<name>_Epoch_<e>.png``.  CT-MCQ-VAE has two accumulators, keyed by the batch's mode: its keys and file stems carry
+``_base`` / ``_action`` (in action mode the target is ``input_y``), and causal batches, which have no picture pair, feed none.  It
+draws nothing and writes no model state, so training is bit for bit the same with and without it.  Refused when the
+experiment is built: a bad value, a dependent key without the main one, and IWAE / MIWAE, whose ``forward`` hands out
+[B, S, C, H, W] samples.  Without the key there is no buffer, no launch, no file and no log key.
 """
 import contextlib
 import json
 import os
-import sys
 import time
 
 import torch
@@ -161,8 +164,8 @@ from .metrics import _eval_mode as eval_mode
 from .reconstats import (RECON_DIR, ReconStats, recon_settings, record as recon_record, refuses_model as recon_refuses_model,
                          summarize as recon_summarize, write_files as write_recon_files)
 from .optim import (CodebookEMA, CodebookUsage, ExponentialLR, FlatAdam, GradientTracker, WeightEMA, absent_grad_setting,
-                    accumulate_setting, clip_settings, codebook_ema_serves, codebook_ema_settings, codebook_record,
-                    codebook_settings, ema_settings, track_grad_norm_setting, watch_settings, with_window_ends)
+                    accumulate_setting, clip_settings, codebook_ema_serves, codebook_ema_settings, codebook_offset,
+                    codebook_record, codebook_settings, ema_settings, track_grad_norm_setting, watch_settings, with_window_ends)
 
 
 def _graph_key(real_img, kwargs):
@@ -256,16 +259,7 @@ class _GraphedTrainStep:
         else:
             losses = self._body()
         self.seen += 1
-        if exp.accumulate > 1:
-            exp.window_step(ends_window, self.pattern)
-        elif exp.ddp is not None:
-            exp.ddp_step(self.pattern)
-        if ends_window:
-            exp.track_gradients()          # eager, behind the replay: the flat buffer holds the gradient that was just stepped
-            exp.codebook_update()          # eager too (decay and eps are by-value arguments), in front of the weight average
-            exp.ema_update()               # eager too: the decay is a by-value argument that a captured launch would freeze
-            exp.codebook_restart()         # eager too: the dead list is formed on the host
-            exp.global_step += 1
+        exp.finish_batch(ends_window, self.pattern, stepped=in_graph)      # eager, behind the replay
         return losses
 
 
@@ -341,7 +335,6 @@ class VAEXperiment:
         # latent usage (latentstats.LatentStats): validated on every rank, built on rank 0 only
         self.latent_stats = latent_stats_setting(params.get("latent_stats"))
         self.val_latents = None
-        self._observing_latents = False         # True inside the validation steps of _validate() only
         if self.latent_stats:
             if not has_gaussian_posterior(vae_model):
                 raise ValueError(needs_gaussian_posterior(vae_model))
@@ -351,7 +344,7 @@ class VAEXperiment:
         # accumulator per picture mode
         self.recon_stats, self.recon_range, self.recon_worst = recon_settings(params)
         self.val_recon = None                   # {key suffix: ReconStats}; "" for every model but CT-MCQ-VAE
-        self._observing_recon = False           # True inside the validation steps of _validate() only
+        self._val_observers = []                # what validation_step hands its results: empty outside _validate()
         if self.recon_stats:
             why = recon_refuses_model(vae_model)
             if why is not None:
@@ -410,19 +403,9 @@ class VAEXperiment:
         with torch.no_grad():
             results = self.forward(real_img, labels=labels, **kwargs)
             val_loss = self.model.loss_function(*results, M_N=1.0, optimizer_idx=optimizer_idx, batch_idx=batch_idx)
-            if self._observing_latents:        # latent_stats: one launch, nothing comes back to the host before the epoch ends
-                self.val_latents.observe(*self.model.gaussian_posterior(results))
-            if self._observing_recon:          # recon_stats: one launch (three with a worst set), nothing comes back either
-                pair = self.model.reconstruction_pair(results)
-                if pair is not None:
-                    self.val_recon[self._recon_suffix(results)].observe(*pair)
+            for observe in self._val_observers:        # launches only: nothing comes back to the host before the epoch ends
+                observe(results)
         return self.log_all(val_loss, batch_size=real_img.size(0), validation=True, force=True)
-
-    def _recon_suffix(self, results) -> str:
-        """Which accumulator a batch with a picture pair feeds: CT-MCQ-VAE's by the batch's mode, else the only one."""
-        if "" in self.val_recon:
-            return ""
-        return "_" + results[4]["mode"]
 
     def metric_func(self, x):
         x = x.to(next(self.model.parameters()).device)
@@ -434,19 +417,31 @@ class VAEXperiment:
         metric or off rank 0.  The metric's own generator is seeded per epoch; no torch generator and no model state moves."""
         if self.val_metric is None or not self._rank0():
             return {}
-        seed = int(self.params.get('manual_seed', 0) or 0) * 1_000_003 + int(epoch)
-        res = {"val_" + k: v for k, v in self.val_metric.compute(self.metric_func, model=self.model, seed=seed).items()}
-        if self.log_file is not None:
-            self.log_file.write(json.dumps({**res, "step": self.global_step}) + "\n")
-            self.log_file.flush()
-        return res
+        res = self.val_metric.compute(self.metric_func, model=self.model, seed=self.epoch_seed(epoch))
+        return self._write_epoch_record({"val_" + k: v for k, v in res.items()})
 
     def _rank0(self):
         return self.ddp is None or not torch.distributed.is_initialized() or torch.distributed.get_rank() == 0
 
-    def sample_seed(self, epoch: int) -> int:
-        """Seed of the epoch's ``sample_images`` draws (the rule of ``validation_metrics``)."""
+    def _active_ddp(self):
+        """The gradient exchange when it has a process group to send on (the codebook collectives go through it), else None."""
+        return self.ddp if self.ddp is not None and getattr(self.ddp, "active", False) else None
+
+    def epoch_seed(self, epoch: int) -> int:
+        """Seed of what validation draws in an epoch: the metric's generator, the ``sample_images`` draws."""
         return int(self.params.get('manual_seed', 0) or 0) * 1_000_003 + int(epoch)
+
+    def _write_record(self, rec: dict, gradients: bool = False):
+        """One JSONL line to ``log_file`` (gradients: to ``grad_log_file``), flushed; nothing without the file."""
+        file = self.grad_log_file if gradients else self.log_file
+        if file is not None:
+            file.write(json.dumps(rec) + "\n")
+            file.flush()
+
+    def _write_epoch_record(self, rec: dict) -> dict:
+        """A validation report's part of the epoch record, also as one JSONL line with the step behind its keys; returns it."""
+        self._write_record({**rec, "step": self.global_step})
+        return rec
 
     def sample_images(self, test_batch, epoch: int) -> list:
         """experiment.py:114-150 on one test batch ``(input, labels, *options)``: the input, ``model.generate`` and
@@ -471,7 +466,7 @@ class VAEXperiment:
             imagegrid.save_image(img, p, normalize=True, nrow=12)
             written.append(p)
 
-        with eval_mode(self.model), seeded_torch_rng(self.sample_seed(epoch), dev):
+        with eval_mode(self.model), seeded_torch_rng(self.epoch_seed(epoch), dev):
             save(test_input, path("Inputs", "inputs"))
             save(self.model.generate(test_input, labels=test_label, **kwargs), path("Reconstructions", "recons"))
             try:
@@ -502,16 +497,14 @@ class VAEXperiment:
                 h, w = res["hw"]
                 causalgraph.save_heatmaps(res["mask_mean"][masked].reshape(len(masked), -1, w),
                                           os.path.join(d, f"mask_{self.run_name}_Epoch_{epoch}.png"), cell=self.MASK_CELL)
-        if self.log_file is not None and rec:
-            self.log_file.write(json.dumps({**rec, "step": self.global_step}) + "\n")
-            self.log_file.flush()
-        return rec
+        return self._write_epoch_record(rec) if rec else rec
 
-    def log_all(self, losses: dict, batch_size, validation: bool = False, force: bool = False):
+    def log_all(self, losses: dict, batch_size, validation: bool = False, force: bool = False, step=None):
         """Scalar tensors only (strings are dropped like experiment.py:93-106; the reference logs the 2-D ``ct_adjacency`` /
         ``ct_mask`` batch means as images, here ``val_graphs`` writes them per action instead); one fused all-reduce over
-        ranks (sync_dist=True) and one D2H copy."""
-        if not force and (self.global_step % self.log_every) != 0:
+        ranks (sync_dist=True) and one D2H copy.  step: the optimizer step the record is of (None: ``global_step``)."""
+        step = self.global_step if step is None else step
+        if not force and (step % self.log_every) != 0:
             return None
         prefix = "val_" if validation else ""
         scal = {prefix + k: v for k, v in losses.items()
@@ -522,11 +515,9 @@ class VAEXperiment:
         vals = torch.stack([scal[k].detach().float().reshape(()) for k in keys]).cpu().tolist() if keys else []
         rec = dict(zip(keys, vals))
         if self.kl is not None and not validation:
-            rec["kld_weight"] = self.kl.weight(self.global_step)      # the host's value of the step that ran: no copy
-        rec["step"] = self.global_step
-        if self.log_file is not None:
-            self.log_file.write(json.dumps(rec) + "\n")
-            self.log_file.flush()
+            rec["kld_weight"] = self.kl.weight(step)      # the host's value of the step that ran: no copy
+        rec["step"] = step
+        self._write_record(rec)
         return rec
 
     # -- optimisation (experiment.py:152-187) ---------------------------------------------------------------
@@ -566,7 +557,7 @@ class VAEXperiment:
         if rng is not None:
             sd["model_rng"] = rng.detach().cpu()
         if self.ema is not None:           # (the buffer itself travels as weights: the checkpoint's ema_state_dict, run.py)
-            sd["ema"] = {"decay": float(self.ema.decay), "warmup": bool(self.ema.warmup), "updates": int(self.ema.updates)}
+            sd["ema"] = self.ema.state_dict(buffer=False)
         if self.codebook is not None:      # (the pool does not travel: the next forward refills it before a restart can read it)
             cb = self.codebook
             sd["codebook"] = {"every": int(self.codebook_every), "min_count": int(self.codebook_min_count),
@@ -653,19 +644,33 @@ class VAEXperiment:
         else:
             self.optimizer.step(grad_scale=1.0 / self.accumulate, pattern=pattern)
 
-    def optimizer_step(self):
-        """One optimizer step on the gradients in the flat buffer (under gradient accumulation: the end of a window)."""
-        if self.accumulate > 1:
-            self.window_step(True)
+    def finish_batch(self, ends_window=True, pattern=None, stepped=False):
+        """What follows every backward pass of training, captured or eager: the stash or the step -- ``window_step`` under
+        gradient accumulation, ``ddp_step`` with a gradient exchange, else the plain step; none of them when the captured body
+        has ``stepped`` already -- and, where the batch ends its window, the step's tail.  pattern: see ``FlatAdam.step``."""
+        if stepped:
+            pass
+        elif self.accumulate > 1:
+            self.window_step(ends_window, pattern)
         elif self.ddp is not None:
-            self.ddp_step()
+            self.ddp_step(pattern)
         else:
             self.optimizer.step()
+        if ends_window:
+            self._after_optimizer_step()
+
+    def _after_optimizer_step(self):
+        """The tail of every optimizer step, eager also behind a replay, in the order the module docstring gives the reasons
+        for; ``global_step`` names the step that ran until the last line."""
         self.track_gradients()
         self.codebook_update()
         self.ema_update()
         self.codebook_restart()
         self.global_step += 1
+
+    def optimizer_step(self):
+        """One optimizer step on the gradients in the flat buffer (under gradient accumulation: the end of a window)."""
+        self.finish_batch()
 
     # -- gradient tracking (trainer_params.track_grad_norm, exp_params.watch_gradients; optim.GradientTracker) -----
     def _build_tracker(self, track_grad_norm, watch_gradients, watch_log_freq):
@@ -678,34 +683,27 @@ class VAEXperiment:
         return GradientTracker(self.optimizer, norm_type, watch, freq)
 
     def track_gradients(self):
-        """Called eagerly right behind an optimizer step, ``global_step`` still naming the step that ran; never inside a capture.
-        On a step where a record is due (norms: where the training scalars are logged; histograms: every ``watch_log_freq``
-        steps) rank 0 measures the stepped gradient -- the optimizer's slice of the flat buffer times the step's ``grad_scale``
-        1 / (world * k) -- and writes ``{"grad_<p>_norm/model.<name>": ..., "grad_<p>_norm_total": ..., "lr-Adam": lr, "step": s}``
-        to the metrics log and ``{"step": s, "gradients/<name>": {"min", "max", "counts", "nonfinite"}, ...}`` to the gradient
-        log.  On every other step, and without a tracker, nothing is launched or allocated."""
+        """First in the step's tail (``_after_optimizer_step``).  On a step where a record is due (norms: where the training
+        scalars are logged; histograms: every ``watch_log_freq`` steps) rank 0 measures the stepped gradient -- the optimizer's
+        slice of the flat buffer times the step's ``grad_scale`` 1 / (world * k) -- and writes ``{"grad_<p>_norm/model.<name>":
+        ..., "grad_<p>_norm_total": ..., "lr-Adam": lr, "step": s}`` to the metrics log and ``{"step": s, "gradients/<name>":
+        {"min", "max", "counts", "nonfinite"}, ...}`` to the gradient log.  On every other step, and without a tracker, nothing
+        is launched or allocated."""
         tr = self.grad_tracker
         if tr is None:
             return
         scale = (self.ddp.grad_scale if self.ddp is not None else 1.0) / self.accumulate
         norms, hists = tr.record(self.global_step, self.log_every, scale)
         if norms is not None:
-            norms = {**norms, "lr-Adam": float(self.optimizer.lr), "step": self.global_step}   # (the rate itself, unrounded)
-            self.last_grad_norms = norms
-            if self.log_file is not None:
-                self.log_file.write(json.dumps(norms) + "\n")
-                self.log_file.flush()
+            self.last_grad_norms = norms = {**norms, "lr-Adam": float(self.optimizer.lr), "step": self.global_step}   # (unrounded)
+            self._write_record(norms)
         if hists is not None:
-            hists = {"step": self.global_step, **hists}
-            self.last_grad_hists = hists
-            if self.grad_log_file is not None:
-                self.grad_log_file.write(json.dumps(hists) + "\n")
-                self.grad_log_file.flush()
+            self.last_grad_hists = hists = {"step": self.global_step, **hists}
+            self._write_record(hists, gradients=True)
 
     # -- weight average (exp_params.ema_decay / ema_warmup / ema_eval; optim.WeightEMA) ------------------------------
     def ema_update(self):
-        """Called eagerly right behind an optimizer step, next to ``track_gradients()`` and never inside a capture: one
-        ``ctvae_ema_update`` launch on every rank, no collective.  Nothing without ``ema_decay``."""
+        """In the step's tail: one ``ctvae_ema_update`` launch on every rank, no collective.  Nothing without ``ema_decay``."""
         if self.ema is not None:
             self.ema.update()
 
@@ -773,24 +771,21 @@ class VAEXperiment:
                              f"{type(self.model).__name__}")
         vq = self.model.vq_layer
         ema = CodebookEMA(vq, decay, eps)
-        cb = ema.codebooks()
-        lo = (cb.data_ptr() - self.model.flat_params.data_ptr()) // 4 - int(self.optimizer.slice.start or 0)
-        if not (0 <= lo and lo + cb.numel() <= self.model.flat_params[self.optimizer.slice].numel()):
+        if codebook_offset(vq, self.optimizer) is None:
             raise ValueError(f"codebook_ema_decay cannot move codebooks the optimizer does not step: update_parameters="
                              f"{params.get('update_parameters')!r} leaves the codebooks outside the optimizer's slice")
         self.codebook_ema = vq.ema = ema
 
     def codebook_update(self):
-        """Called eagerly right behind an optimizer step and ``track_gradients()``, in front of ``ema_update()`` -- the weight
-        average sees the codebook the step ends with -- and never inside a capture: [DDP: one SUM all-reduce of the window
-        accumulators,] one ``ctvae_vq_ema_update`` launch, a parameter-epoch bump.  On the steps that log training scalars one
+        """In the step's tail, in front of ``ema_update()``: [DDP: one SUM all-reduce of the window accumulators,] one
+        ``ctvae_vq_ema_update`` launch, a parameter-epoch bump.  On the steps that log training scalars one
         JSONL line ``{"codebook_ema_min_cluster_<i>": min_k N, "codebook_ema_max_cluster_<i>": max_k N, ...,
         "codebook_ema_min_cluster": ..., "codebook_ema_max_cluster": ..., "step": s}`` (rank 0, one device-to-host copy).
         Nothing without ``codebook_ema_decay``."""
         ema = self.codebook_ema
         if ema is None:
             return
-        ddp = self.ddp if self.ddp is not None and getattr(self.ddp, "active", False) else None
+        ddp = self._active_ddp()
         ema.update(reduce=ddp.all_reduce_codebook_ema if ddp is not None else None)
         if self.global_step % self.log_every == 0 and self._rank0():
             lo, hi = ema.cluster_sizes()
@@ -800,9 +795,7 @@ class VAEXperiment:
             rec["codebook_ema_min_cluster"], rec["codebook_ema_max_cluster"] = min(lo), max(hi)
             rec["step"] = self.global_step
             self.last_codebook_ema = rec
-            if self.log_file is not None:
-                self.log_file.write(json.dumps(rec) + "\n")
-                self.log_file.flush()
+            self._write_record(rec)
 
     @contextlib.contextmanager
     def _counting_training_codes(self):
@@ -824,16 +817,15 @@ class VAEXperiment:
             vq.ema_observer = None
 
     def codebook_restart(self):
-        """Called eagerly right behind an optimizer step, next to ``track_gradients()`` / ``ema_update()`` and never inside a
-        capture, ``global_step`` still naming the step that ran.  Every ``codebook_restart_every`` optimizer steps: [DDP: one SUM
-        all-reduce of the counts,] one device-to-host copy, the dead list, the draw from a CPU generator of its own, the
-        restart launch [DDP: on rank 0's rows, one broadcast], a parameter-epoch bump, counts back to zero and one JSONL line
-        ``{"codebook_restarts": n, "codebook_restarts_<i>": ..., "codebook_perplexity_<i>": ..., "codebook_usage_<i>": ...,
-        "step": s}`` over the window that ended.  On every other step, and without the key, nothing."""
+        """Last in the step's tail.  Every ``codebook_restart_every`` optimizer steps: [DDP: one SUM all-reduce of the counts,]
+        one device-to-host copy, the dead list, the draw from a CPU generator of its own, the restart launch [DDP: on rank 0's
+        rows, one broadcast], a parameter-epoch bump, counts back to zero and one JSONL line ``{"codebook_restarts": n,
+        "codebook_restarts_<i>": ..., "codebook_perplexity_<i>": ..., "codebook_usage_<i>": ..., "step": s}`` over the window
+        that ended.  On every other step, and without the key, nothing."""
         cb = self.codebook
         if cb is None or (self.global_step + 1) % self.codebook_every != 0:
             return
-        ddp = self.ddp if self.ddp is not None and getattr(self.ddp, "active", False) else None
+        ddp = self._active_ddp()
         counts, dead, _ = cb.restart(self.optimizer, self.codebook_min_count, self.params.get("manual_seed", 0), self.codebook_ordinal,
                                      reduce=ddp.all_reduce_counts if ddp is not None else None,
                                      broadcast=ddp.broadcast_rows if ddp is not None else None)
@@ -847,9 +839,8 @@ class VAEXperiment:
         rec.update({k: v for k, v in codebook_record(counts, "").items() if "_dead" not in k and k[-1].isdigit()})
         rec["step"] = self.global_step
         self.last_codebook_restart = rec
-        if self.log_file is not None and self._rank0():
-            self.log_file.write(json.dumps(rec) + "\n")
-            self.log_file.flush()
+        if self._rank0():
+            self._write_record(rec)
 
     def write_codebook_stats(self, usage) -> dict:
         """What ``codebook_stats`` leaves of one validation epoch: ``val_codebook_perplexity_<i>`` / ``_usage_<i>`` / ``_dead_<i>``
@@ -859,10 +850,7 @@ class VAEXperiment:
         rec = codebook_record(counts, "val_")
         if invalid:
             rec["val_codebook_invalid"] = invalid
-        if self.log_file is not None:
-            self.log_file.write(json.dumps({**rec, "step": self.global_step}) + "\n")
-            self.log_file.flush()
-        return rec
+        return self._write_epoch_record(rec)
 
     def write_latent_stats(self, latents, epoch: int) -> dict:
         """What ``latent_stats`` leaves of one validation epoch: the ``val_latent_*`` scalars (``latentstats.summarize``, float64 on
@@ -875,10 +863,7 @@ class VAEXperiment:
             os.makedirs(d, exist_ok=True)
             write_latent_files(res, os.path.join(d, f"latent_stats_{self.run_name}_Epoch_{epoch}.npz"),
                                os.path.join(d, f"corr_{self.run_name}_Epoch_{epoch}.png"))
-        if self.log_file is not None:
-            self.log_file.write(json.dumps({**rec, "step": self.global_step}) + "\n")
-            self.log_file.flush()
-        return rec
+        return self._write_epoch_record(rec)
 
     def write_recon_stats(self, accumulators, epoch: int) -> dict:
         """What ``recon_stats`` leaves of one validation epoch: per accumulator one copy, the ``val_recon_*`` scalars
@@ -894,10 +879,7 @@ class VAEXperiment:
                 os.makedirs(d, exist_ok=True)
                 write_recon_files(res, os.path.join(d, f"recon_stats_{self.run_name}{sfx}_Epoch_{epoch}.npz"),
                                   os.path.join(d, f"worst_{self.run_name}{sfx}_Epoch_{epoch}.png") if acc.K > 0 else None)
-        if self.log_file is not None:
-            self.log_file.write(json.dumps({**rec, "step": self.global_step}) + "\n")
-            self.log_file.flush()
-        return rec
+        return self._write_epoch_record(rec)
 
     def _load_codebook_state(self, entry):
         """Full resume under ``codebook_restart_every``: the window's counts, the restart ordinal and the total come back, so a
@@ -919,55 +901,77 @@ class VAEXperiment:
         cb.valid_rows = None if valid < 0 else min(valid, cb.pool.size(0))
         self.codebook_ordinal, self.codebook_restarted = int(entry["ordinal"]), int(entry["restarted"])
 
+    # -- validation reports: contexts armed around the validation steps, each yielding what writes its part of the epoch record --
+    @contextlib.contextmanager
+    def _graph_report(self, epoch):
+        from . import causalgraph
+        ct = self.model.ct_layer
+        stats = causalgraph.GraphStats(ct.action_dim + 1, causalgraph.model_nodes(self.model), next(self.model.parameters()).device)
+        ct.graph_observer = stats.observe
+        try:
+            yield lambda: self.write_graphs(stats, epoch)
+        finally:
+            ct.graph_observer = None
+
+    @contextlib.contextmanager
+    def _codebook_report(self, epoch):
+        self.val_codebook.zero()
+        self.model.vq_layer.usage_observer = self.val_codebook.observe
+        try:
+            yield lambda: self.write_codebook_stats(self.val_codebook)
+        finally:
+            self.model.vq_layer.usage_observer = None
+
+    @contextlib.contextmanager
+    def _observing_results(self, observe):
+        """``validation_step`` hands ``observe`` every step's results inside."""
+        self._val_observers.append(observe)
+        try:
+            yield
+        finally:
+            self._val_observers.remove(observe)
+
+    @contextlib.contextmanager
+    def _latent_report(self, epoch):
+        self.val_latents.zero()
+        with self._observing_results(lambda results: self.val_latents.observe(*self.model.gaussian_posterior(results))):
+            yield lambda: self.write_latent_stats(self.val_latents, epoch)
+
+    @contextlib.contextmanager
+    def _recon_report(self, epoch):
+        for acc in self.val_recon.values():
+            acc.reset()
+
+        def observe(results):        # CT-MCQ-VAE feeds the accumulator of the batch's mode, every other model the only one
+            pair = self.model.reconstruction_pair(results)
+            if pair is not None:
+                self.val_recon["" if "" in self.val_recon else "_" + results[4]["mode"]].observe(*pair)
+
+        with self._observing_results(observe):
+            yield lambda: self.write_recon_stats(self.val_recon, epoch)
+
+    def _val_reports(self):
+        """The reports this run has on this rank, in the order of their keys in the epoch record."""
+        reports = ((self._graph_report, self.val_graphs and self._rank0()), (self._codebook_report, self.val_codebook is not None),
+                   (self._latent_report, self.val_latents is not None), (self._recon_report, self.val_recon is not None))
+        return [report for report, on in reports if on]
+
     def _validate(self, epoch, val_batches, test_batches):
-        """The validation part of one epoch of ``fit()``: the validation steps' means, ``write_graphs``, ``validation_metrics``
-        and ``sample_images``; returns what joins the epoch record."""
-        rec = {}
+        """The validation part of one epoch of ``fit()``: the validation steps' means, what the armed reports write,
+        ``validation_metrics`` and ``sample_images``; returns what joins the epoch record."""
         self.model.eval()
         sums, cnt = {}, 0
-        stats = None
-        if self.val_graphs and self._rank0():
-            from . import causalgraph
-            ct = self.model.ct_layer
-            stats = causalgraph.GraphStats(ct.action_dim + 1, causalgraph.model_nodes(self.model),
-                                           next(self.model.parameters()).device)
-            ct.graph_observer = stats.observe
-        usage = self.val_codebook              # codebook_stats: rank 0's own validation rows, as val_graphs
-        if usage is not None:
-            usage.zero()
-            self.model.vq_layer.usage_observer = usage.observe
-        latents = self.val_latents             # latent_stats: rank 0's own validation rows too
-        if latents is not None:
-            latents.zero()
-            self._observing_latents = True
-        recon = self.val_recon                 # recon_stats: rank 0's own validation rows too
-        if recon is not None:
-            for acc in recon.values():
-                acc.reset()
-            self._observing_recon = True
-        try:
+        with contextlib.ExitStack() as armed:
+            writers = [armed.enter_context(report(epoch)) for report in self._val_reports()]
             for i, batch in enumerate(val_batches()):
                 r = self.validation_step(batch, i)
                 for k, v in r.items():
                     if k != "step":
                         sums[k] = sums.get(k, 0.0) + v
                 cnt += 1
-        finally:
-            if stats is not None:
-                self.model.ct_layer.graph_observer = None
-            if usage is not None:
-                self.model.vq_layer.usage_observer = None
-            self._observing_latents = False
-            self._observing_recon = False
-        rec.update({k: v / max(cnt, 1) for k, v in sums.items()})
-        if stats is not None:
-            rec.update(self.write_graphs(stats, epoch))
-        if usage is not None:
-            rec.update(self.write_codebook_stats(usage))
-        if latents is not None:
-            rec.update(self.write_latent_stats(latents, epoch))
-        if recon is not None:
-            rec.update(self.write_recon_stats(recon, epoch))
+        rec = {k: v / max(cnt, 1) for k, v in sums.items()}
+        for write in writers:
+            rec.update(write())
         rec.update(self.validation_metrics(epoch))
         if self.val_sampling and self.sample_dir is not None and test_batches is not None and self._rank0():
             first = next(iter(test_batches()), None)
@@ -989,7 +993,7 @@ class VAEXperiment:
             # (one batch of look-ahead: the loader is an iterable) -- no window state crosses an epoch boundary
             stream = ((b, True) for b in train_batches()) if k == 1 else with_window_ends(train_batches(), k)
             with self._counting_training_codes():
-                n = self._train_epoch(stream, k)
+                n = self._train_epoch(stream)
             if self.scheduler is not None:
                 self.scheduler.step()                      # Lightning steps ExponentialLR once per epoch
             rec = {"epoch": epoch, "train_images": n, "epoch_seconds": time.time() - t0}
@@ -1002,7 +1006,7 @@ class VAEXperiment:
                 on_epoch_end(epoch, rec)
         return history
 
-    def _train_epoch(self, stream, k):
+    def _train_epoch(self, stream):
         """The training batches of one epoch of ``fit()``: ``stream`` yields (batch, ends_window); returns the images seen."""
         n = 0
         for i, (batch, ends) in enumerate(stream):
@@ -1019,10 +1023,8 @@ class VAEXperiment:
                     gs = self._graphed[key] = _GraphedTrainStep(self, real_img, kwargs)
                 self.curr_device = real_img.device
                 losses = gs.run(real_img, kwargs, ends)
-                if ends:
-                    self.global_step -= 1              # log_all keys on the step that just ran
-                    self.log_all(losses, batch_size=real_img.size(0), validation=False)
-                    self.global_step += 1
+                if ends:                               # the record of the step that just ran: global_step has moved on
+                    self.log_all(losses, batch_size=real_img.size(0), validation=False, step=self.global_step - 1)
             else:
                 self.model.zero_grad(lazy=True)
                 self._log_train = ends                 # a record per optimizer step, with the losses of its last micro-batch
@@ -1032,15 +1034,6 @@ class VAEXperiment:
                     self._log_train = True
                 K.backward(loss)
                 self.model.settle_grads()
-                if k == 1:
-                    self.optimizer_step()
-                else:
-                    self.window_step(ends)
-                    if ends:
-                        self.track_gradients()
-                        self.codebook_update()
-                        self.ema_update()
-                        self.codebook_restart()
-                        self.global_step += 1
+                self.finish_batch(ends)
             n += batch[0].size(0)
         return n

@@ -409,8 +409,10 @@ class WeightEMA:
         finally:
             self.swap()
 
-    def state_dict(self):
-        return {"decay": self.decay, "warmup": self.warmup, "updates": int(self.updates), "buffer": self.buffer}
+    def state_dict(self, buffer=True):
+        """buffer=False: the checkpoint's ``"ema"`` entry, plain numbers only -- the buffer travels as weights there."""
+        sd = {"decay": self.decay, "warmup": self.warmup, "updates": int(self.updates)}
+        return {**sd, "buffer": self.buffer} if buffer else sd
 
     def load_state_dict(self, sd):
         if float(sd["decay"]) != self.decay or bool(sd["warmup"]) != self.warmup:
@@ -523,6 +525,15 @@ def quantizer_codebooks(vq_layer):
     return w.detach().unsqueeze(0), w.size(1)
 
 
+def codebook_offset(vq_layer, optimizer):
+    """Offset of a quantiser's codebooks inside the optimizer's slice of the flat parameter buffer; None when they lie outside."""
+    cb, _ = quantizer_codebooks(vq_layer)
+    flat = optimizer.model.flat_params
+    lo = (cb.data_ptr() - flat.data_ptr()) // 4 - int(optimizer.slice.start or 0)
+    n = flat[optimizer.slice].numel()
+    return lo if 0 <= lo and lo + cb.numel() <= n else None
+
+
 class CodebookUsage:
     """How often every code of a model's quantiser is chosen (``exp_params.codebook_stats`` / ``codebook_restart_every``), counted
     by HIP kernels of its own (csrc/vqusage.hip) from the index tensors the quantiser computes anyway.
@@ -592,12 +603,7 @@ class CodebookUsage:
         return counts, dead, rows
 
     def codebook_offset(self, optimizer):
-        """Offset of the codebooks inside the optimizer's slice of the flat parameter buffer; None when they lie outside it."""
-        cb, _ = quantizer_codebooks(self.vq)
-        flat = optimizer.model.flat_params
-        lo = (cb.data_ptr() - flat.data_ptr()) // 4 - int(optimizer.slice.start or 0)
-        n = flat[optimizer.slice].numel()
-        return lo if 0 <= lo and lo + cb.numel() <= n else None
+        return codebook_offset(self.vq, optimizer)
 
     def codebook_views(self, optimizer):
         """The codebooks and the two Adam moments of the same elements as [C, K, Dc] views."""
