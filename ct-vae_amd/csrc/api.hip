@@ -200,6 +200,14 @@ int launch_heatmap_u8(const float* values, int M, int H, int W, float lo, float 
                       int pad_b, const uint8_t* table, int scanlines, uint8_t* out, size_t out_bytes, hipStream_t st);
 int launch_latent_accumulate(const float* mu, long mu_pitch, const float* logvar, long lv_pitch, int B, int L, double* kl_sum,
                              double* mu_sum, double* sig2_sum, double* cov_sum, int* nonfinite, int* rows, hipStream_t st);
+int launch_gmm_estep(const float* X, int N, int D, int K, int full, const float* log_w, const float* mu, const float* P,
+                     const float* ldh, float* r, float* ll, int* nonfinite, hipStream_t st);
+int gmm_mstep_slabs(int N, int D, int K, int full);
+size_t gmm_mstep_workspace_bytes(int N, int D, int K, int full);
+int launch_gmm_mstep(const float* X, const float* r, const int* nonfinite, int N, int D, int K, int full, const float* m, double* Nk,
+                     double* S1, double* S2, double* ws, size_t ws_bytes, hipStream_t st);
+int launch_gmm_sample(const float* u, const float* eps, int n, int D, int K, int full, const double* cdf, const float* mu,
+                      const float* L, float* z, int* comp, hipStream_t st);
 int launch_recon_record(const float* a, const float* b, int B, int S, int C, const double* consts, double* rec, int* flag, int row0,
                         int capacity, hipStream_t st);
 int launch_recon_worst(const double* old_ssim, const int* old_row, const float* old_a, const float* old_b, const double* rec,
@@ -1123,6 +1131,24 @@ int ctvae_latent_accumulate(const float* mu, long mu_pitch, const float* logvar,
                             double* mu_sum, double* sig2_sum, double* cov_sum, int32_t* nonfinite, int32_t* rows, void* stream) {
   return launch_latent_accumulate(mu, mu_pitch, logvar, logvar_pitch, B, L, kl_sum, mu_sum, sig2_sum, cov_sum, nonfinite, rows,
                                   (hipStream_t)stream);
+}
+
+int ctvae_gmm_estep(const float* X, int N, int D, int K, int full, const float* log_w, const float* mu, const float* P,
+                    const float* log_det_half, float* r, float* ll, int32_t* nonfinite, void* stream) {
+  return launch_gmm_estep(X, N, D, K, full, log_w, mu, P, log_det_half, r, ll, nonfinite, (hipStream_t)stream);
+}
+
+int ctvae_gmm_mstep_slabs(int N, int D, int K, int full) { return gmm_mstep_slabs(N, D, K, full); }
+size_t ctvae_gmm_mstep_workspace_bytes(int N, int D, int K, int full) { return gmm_mstep_workspace_bytes(N, D, K, full); }
+
+int ctvae_gmm_mstep(const float* X, const float* r, const int32_t* nonfinite, int N, int D, int K, int full, const float* m,
+                    double* Nk, double* S1, double* S2, double* ws, size_t ws_bytes, void* stream) {
+  return launch_gmm_mstep(X, r, nonfinite, N, D, K, full, m, Nk, S1, S2, ws, ws_bytes, (hipStream_t)stream);
+}
+
+int ctvae_gmm_sample(const float* u, const float* eps, int n, int D, int K, int full, const double* cdf, const float* mu,
+                     const float* L, float* z, int32_t* comp, void* stream) {
+  return launch_gmm_sample(u, eps, n, D, K, full, cdf, mu, L, z, comp, (hipStream_t)stream);
 }
 
 int ctvae_recon_record(const float* a, const float* b, int B, int S, int C, const double* consts, double* records, int32_t* flags,

@@ -33,7 +33,7 @@ freeze; the dead list is formed on the host), and runs once per optimizer step, 
 
 The validation order.  ``_validate`` arms every report the run has (a context each: reset or rebuilt, then observing; disarmed
 in a ``finally``), runs the validation steps, and collects in the key order of the epoch record: the steps' means,
-``write_graphs``, ``write_codebook_stats``, ``write_latent_stats``, ``write_recon_stats``, ``validation_metrics``, and last
+``write_graphs``, ``write_codebook_stats``, ``write_latent_stats``, ``write_recon_stats``, ``write_prior``, ``validation_metrics``, and last
 ``sample_images``.  The reports are eager like all of validation, make their one device-to-host copy behind the steps, are rank
 0's own rows (no collective) and, under ``ema_eval``, describe the averaged weights; a ``validation_step`` outside ``_validate``
 observes nothing.
@@ -134,6 +134,15 @@ gain ``kld_weight`` (the host's value, no copy), ``KLD_free_bits`` and ``KLD_flo
 needs no state.  Refused when the experiment is built: either key on another model.  Without the keys there is no buffer, no
 launch, no log key and no entry.
 
+``exp_params.sample_prior`` (a mapping with ``type: gmm``; ``latentprior.prior_setting``): a Gaussian-mixture prior fitted to the
+validation codes of the models in ``latentprior.PRIOR_MODELS``, on rank 0, a report of ``_validate``.  Armed, the code buffer
+(``latentprior.CodeBuffer``) is cleared and every ``validation_step`` hands it the batch's ``mu`` view (``codes: sample``: ``mu +
+exp(0.5 log_var) * eps`` with eps from a generator of the report's own), one device-to-device copy; ``write_prior`` fits the rows
+with an even ordinal (``latentprior.GaussianMixturePrior``, csrc/gmm.hip), holds out the odd ones and adds
+``val_prior_mixture_loglik`` / ``_standard_loglik`` / ``_iterations`` / ``_rows`` / ``_nonfinite`` to the epoch record (a refused fit:
+``val_prior_error``) and, with a ``sample_dir``, ``Priors/latent_prior_<name>_Epoch_<e>.npz``; with ``val_sampling``
+``sample_mixture_images`` writes ``Samples/sample_mixture_<name>_Epoch_<e>.png`` from a generator of its own next to the unchanged
+``sample_<name>_...png``.  It adds nothing to checkpoints and moves no random stream.
 ``exp_params.recon_stats`` (a bool; with ``recon_stats_range``, the data range R, a float > 0, default 1.0, and ``recon_stats_worst``,
 an integer 0 <= K <= 32, default 8): the reconstruction quality per validation image, by ``reconstats.ReconStats`` on rank 0,
 a report of ``_validate`` (above).  Armed, it is reset and every ``validation_step`` hands it the pair
@@ -158,6 +167,8 @@ from . import imagegrid
 from . import kernels as K
 from .ddp import GradBucketAllReduce
 from .klcontrol import KLControl, kl_settings, needs_served_model, serves as kl_serves
+from .latentprior import (PRIOR_DIR, CodeBuffer, GaussianMixturePrior, draw_codes, needs_supported_model, prior_setting,
+                          prior_supported)
 from .latentstats import (LATENT_DIR, LatentStats, has_gaussian_posterior, latent_stats_setting, needs_gaussian_posterior,
                           record as latent_record, write_files as write_latent_files)
 from .metrics import _eval_mode as eval_mode
@@ -340,6 +351,15 @@ class VAEXperiment:
                 raise ValueError(needs_gaussian_posterior(vae_model))
             if self._rank0():
                 self.val_latents = LatentStats(vae_model.latent_dim, next(vae_model.parameters()).device)
+        # sample prior (latentprior.GaussianMixturePrior): validated on every rank, the code buffer on rank 0 only
+        self.sample_prior = prior_setting(params.get("sample_prior"))
+        self.val_prior = None                   # the epoch's validation codes (latentprior.CodeBuffer)
+        self.last_prior = None                  # the mixture the last validation epoch fitted (None: none, or the fit was refused)
+        if self.sample_prior is not None:
+            if not prior_supported(vae_model):
+                raise ValueError(needs_supported_model(vae_model))
+            if self._rank0():
+                self.val_prior = CodeBuffer(vae_model.latent_dim, next(vae_model.parameters()).device)
         # reconstruction quality (reconstats.ReconStats): validated on every rank, built on rank 0 only; CT-MCQ-VAE gets one
         # accumulator per picture mode
         self.recon_stats, self.recon_range, self.recon_worst = recon_settings(params)
@@ -865,6 +885,54 @@ class VAEXperiment:
                                os.path.join(d, f"corr_{self.run_name}_Epoch_{epoch}.png"))
         return self._write_epoch_record(rec)
 
+    def write_prior(self, codes, epoch: int) -> dict:
+        """What ``sample_prior`` leaves of one validation epoch.  The rows of ``codes`` (a ``latentprior.CodeBuffer``) with an even
+        ordinal are fitted, the rows with an odd ordinal are held out: ``val_prior_mixture_loglik`` and
+        ``val_prior_standard_loglik`` are the mean log-likelihoods, in nats, of the finite held-out rows under the mixture and
+        under N(0, I) (left out when there is no such row), ``val_prior_iterations``, ``val_prior_rows`` (the finite rows
+        fitted) and ``val_prior_nonfinite`` (the non-finite rows of both halves); also one JSONL line, and with a ``sample_dir``
+        ``Priors/latent_prior_<name>_Epoch_<e>.npz``.  A refused fit -- too few rows, a covariance that is not positive definite --
+        leaves ``val_prior_error``, a string, in place of all that, and the epoch goes on."""
+        cfg = self.sample_prior
+        X = codes.view()
+        fitted, held = X[0::2].contiguous(), X[1::2].contiguous()
+        prior = GaussianMixturePrior(codes.D, cfg["components"], cfg["covariance"], cfg["reg_covar"], codes.device)
+        self.last_prior = None
+        try:
+            info = prior.fit(fitted, seed=self.epoch_seed(epoch), max_iter=cfg["max_iter"], tol=cfg["tol"])
+        except ValueError as e:
+            return self._write_epoch_record({"val_prior_error": str(e)})
+        self.last_prior = prior
+        rec = {}
+        ll, bad = prior.log_prob(held)
+        mix = prior.mean_over_finite(ll, bad)
+        if mix is not None:
+            rec["val_prior_mixture_loglik"] = mix
+            rec["val_prior_standard_loglik"] = prior.mean_over_finite(*prior.standard_log_prob(held))
+        rec.update(val_prior_iterations=info["iterations"], val_prior_rows=info["rows"],
+                   val_prior_nonfinite=info["nonfinite"] + int(bad.sum()))
+        if self.sample_dir is not None:
+            d = os.path.join(self.sample_dir, PRIOR_DIR)
+            os.makedirs(d, exist_ok=True)
+            prior.save(os.path.join(d, f"latent_prior_{self.run_name}_Epoch_{epoch}.npz"))
+        return self._write_epoch_record(rec)
+
+    def sample_mixture_images(self, n: int, epoch: int):
+        """``Samples/sample_mixture_<name>_Epoch_<e>.png`` next to ``sample_images``' prior samples: ``n`` draws from the mixture
+        this epoch fitted, decoded.  The draws come from a generator of their own: no other random stream moves.  Returns the
+        path, or None when this epoch fitted no mixture."""
+        if self.last_prior is None:
+            return None
+        dev = next(self.model.parameters()).device
+        g = torch.Generator(device=dev)
+        g.manual_seed(self.epoch_seed(epoch))
+        os.makedirs(os.path.join(self.sample_dir, "Samples"), exist_ok=True)
+        p = os.path.join(self.sample_dir, "Samples", f"sample_mixture_{self.run_name}_Epoch_{epoch}.png")
+        with eval_mode(self.model), torch.no_grad():
+            z, _ = self.last_prior.sample(n, g)
+            imagegrid.save_image(self.model.decode(z), p, normalize=True, nrow=12)
+        return p
+
     def write_recon_stats(self, accumulators, epoch: int) -> dict:
         """What ``recon_stats`` leaves of one validation epoch: per accumulator one copy, the ``val_recon_*`` scalars
         (``reconstats.summarize``; what has no image to stand on is left out), also as one JSONL line, and with a ``sample_dir`` and
@@ -950,10 +1018,26 @@ class VAEXperiment:
         with self._observing_results(observe):
             yield lambda: self.write_recon_stats(self.val_recon, epoch)
 
+    @contextlib.contextmanager
+    def _prior_report(self, epoch):
+        """The codes of every validation batch -- views the step already holds -- are copied into the code buffer."""
+        self.val_prior.clear()
+        g = None
+        if self.sample_prior["codes"] == "sample":     # a generator of the report's own: no other random stream moves
+            g = torch.Generator(device=self.val_prior.device)
+            g.manual_seed(self.epoch_seed(epoch))
+
+        def observe(results):
+            self.val_prior.append(draw_codes(*self.model.gaussian_posterior(results), self.sample_prior["codes"], g))
+
+        with self._observing_results(observe):
+            yield lambda: self.write_prior(self.val_prior, epoch)
+
     def _val_reports(self):
         """The reports this run has on this rank, in the order of their keys in the epoch record."""
         reports = ((self._graph_report, self.val_graphs and self._rank0()), (self._codebook_report, self.val_codebook is not None),
-                   (self._latent_report, self.val_latents is not None), (self._recon_report, self.val_recon is not None))
+                   (self._latent_report, self.val_latents is not None), (self._recon_report, self.val_recon is not None),
+                   (self._prior_report, self.val_prior is not None))
         return [report for report, on in reports if on]
 
     def _validate(self, epoch, val_batches, test_batches):
@@ -977,6 +1061,8 @@ class VAEXperiment:
             first = next(iter(test_batches()), None)
             if first is not None:
                 self.sample_images(first, epoch)
+                if self.val_prior is not None:
+                    self.sample_mixture_images(min(32, self._unpack(first)[0].size(0)), epoch)
         return rec
 
     def fit(self, train_batches, val_batches=None, max_epochs=1, on_epoch_end=None, start_epoch=0, test_batches=None):

@@ -3204,3 +3204,108 @@ def recon_worst(old, new, records, flags, row0, a_nhwc, b_nhwc):
     native.call("ctvae_recon_worst", old["ssim"].data_ptr(), old["row"].data_ptr(), old["a"].data_ptr(), old["b"].data_ptr(),
                 records.data_ptr(), flags.data_ptr(), row0, B, cap, a_nhwc.data_ptr(), b_nhwc.data_ptr(), S, C, K,
                 new["ssim"].data_ptr(), new["row"].data_ptr(), new["a"].data_ptr(), new["b"].data_ptr(), new["source"].data_ptr())
+
+
+# ---------------------------------------------------------------------------------------------------
+# a Gaussian-mixture latent prior fitted by EM (csrc/gmm.hip; latentprior.GaussianMixturePrior)
+# ---------------------------------------------------------------------------------------------------
+GMM_MAX_D, GMM_MAX_K = 256, 64           # what the ctvae_gmm_* entry points cover
+
+
+def _gmm_dims(what, X, K, name="X"):
+    """(N, D) of a [N, D] fp32 tensor after the checks every ctvae_gmm_* wrapper shares."""
+    if not torch.is_tensor(X) or X.dtype != torch.float32 or X.dim() != 2:
+        raise ValueError(f"{what}: {name} must be a torch.float32 [N, D] tensor, got "
+                         f"{getattr(X, 'dtype', type(X).__name__)} {tuple(getattr(X, 'shape', ()))}")
+    if not X.is_contiguous():
+        raise ValueError(f"{what}: {name} must be contiguous")
+    N, D = X.shape
+    if not 1 <= D <= GMM_MAX_D:
+        raise ValueError(f"{what}: D={D} is not covered: the kernels need 1 <= D <= {GMM_MAX_D}")
+    if isinstance(K, bool) or not isinstance(K, int) or not 1 <= K <= GMM_MAX_K:
+        raise ValueError(f"{what}: K={K!r} is not covered: the kernels need 1 <= K <= {GMM_MAX_K}")
+    return N, D
+
+
+def _gmm_param(what, name, t, shape, dtype=torch.float32):
+    _req_dense(what, name, t, dtype)
+    if tuple(t.shape) != tuple(shape):
+        raise ValueError(f"{what}: {name} must be {list(shape)}, got {list(t.shape)}")
+
+
+def gmm_estep(X, log_w, mu, P, log_det_half, full=True):
+    """``ctvae_gmm_estep``: X fp32 [N, D] and the mixture as the host prepared it -- ``log_w`` [K], ``mu`` [K, D], ``P`` ([K, D, D]
+    the inverse lower Cholesky factors for ``full``, [K, D] = 1 / sqrt(var) else), ``log_det_half`` [K], all fp32 on the device.
+    Returns ``(r [N, K] fp32, ll [N] fp32, nonfinite [N] int32)``.  One launch, no host synchronisation.  A CPU tensor is a
+    RuntimeError (there is no CPU fallback); a wrong dtype, shape, D or K raises a ValueError that names it, before any launch."""
+    what = "gmm_estep"
+    K = int(log_w.numel()) if torch.is_tensor(log_w) else 0
+    N, D = _gmm_dims(what, X, K)
+    _gmm_param(what, "log_w", log_w, (K,))
+    _gmm_param(what, "mu", mu, (K, D))
+    _gmm_param(what, "P", P, (K, D, D) if full else (K, D))
+    _gmm_param(what, "log_det_half", log_det_half, (K,))
+    _req_cuda(X, log_w, mu, P, log_det_half)
+    r = torch.empty(N, K, dtype=torch.float32, device=X.device)
+    ll = torch.empty(N, dtype=torch.float32, device=X.device)
+    bad = torch.empty(N, dtype=torch.int32, device=X.device)
+    if N:
+        native.call("ctvae_gmm_estep", X.data_ptr(), N, D, K, 1 if full else 0, log_w.data_ptr(), mu.data_ptr(), P.data_ptr(),
+                    log_det_half.data_ptr(), r.data_ptr(), ll.data_ptr(), bad.data_ptr())
+    return r, ll, bad
+
+
+def gmm_mstep_slabs(N, D, K, full=True) -> int:
+    """The number of row slabs ``ctvae_gmm_mstep`` splits N rows into."""
+    return int(native.load().ctvae_gmm_mstep_slabs(int(N), int(D), int(K), 1 if full else 0))
+
+
+def gmm_mstep(X, r, nonfinite, means, full=True, ws=None):
+    """``ctvae_gmm_mstep``: the float64 sums of one M step, centred at ``means`` (fp32 [K, D]): ``(Nk [K], S1 [K, D], S2)`` with S2
+    [K, D, D] for ``full`` and [K, D] else, float64 device tensors.  ``r`` fp32 [N, K] and ``nonfinite`` int32 [N] (or None) are
+    ``gmm_estep``'s.  ``ws``: a float64 device tensor to reuse as scratch (at least ``ctvae_gmm_mstep_workspace_bytes`` / 8
+    elements; None: allocated here).  Three launches (two for diag), no host synchronisation.  N < K is a ValueError."""
+    what = "gmm_mstep"
+    K = int(means.size(0)) if torch.is_tensor(means) and means.dim() == 2 else 0
+    N, D = _gmm_dims(what, X, K)
+    _gmm_param(what, "means", means, (K, D))
+    _gmm_param(what, "r", r, (N, K))
+    if nonfinite is not None:
+        _gmm_param(what, "nonfinite", nonfinite, (N,), torch.int32)
+    if N < K:
+        raise ValueError(f"{what}: {N} rows cannot carry K={K} components: the M step needs N >= K")
+    _req_cuda(X, r, nonfinite, means)
+    need = int(native.load().ctvae_gmm_mstep_workspace_bytes(N, D, K, 1 if full else 0))
+    if ws is None:
+        ws = torch.empty(need // 8, dtype=torch.float64, device=X.device)
+    else:
+        _req_dense(what, "ws", ws, torch.float64)
+        _req_cuda(ws)
+        if ws.numel() * 8 < need:
+            raise ValueError(f"{what}: ws holds {ws.numel() * 8} bytes, {need} are needed")
+    Nk = torch.empty(K, dtype=torch.float64, device=X.device)
+    S1 = torch.empty(K, D, dtype=torch.float64, device=X.device)
+    S2 = torch.empty((K, D, D) if full else (K, D), dtype=torch.float64, device=X.device)
+    native.call("ctvae_gmm_mstep", X.data_ptr(), r.data_ptr(), native.ptr(nonfinite), N, D, K, 1 if full else 0, means.data_ptr(),
+                Nk.data_ptr(), S1.data_ptr(), S2.data_ptr(), ws.data_ptr(), ws.numel() * 8)
+    return Nk, S1, S2
+
+
+def gmm_sample(u, eps, cdf, mu, L, full=True):
+    """``ctvae_gmm_sample``: ``u`` fp32 [n] in [0, 1), ``eps`` fp32 [n, D], ``cdf`` float64 [K], ``mu`` fp32 [K, D], ``L`` fp32
+    ([K, D, D] lower Cholesky factors for ``full``, [K, D] = sqrt(var) else).  Returns ``(z [n, D] fp32, k [n] int32)``: row i is
+    ``mu_k + L_k eps[i]`` for the first k whose cdf exceeds u[i].  One launch; the kernel holds no random state."""
+    what = "gmm_sample"
+    K = int(cdf.numel()) if torch.is_tensor(cdf) else 0
+    n, D = _gmm_dims(what, eps, K, name="eps")
+    _gmm_param(what, "u", u, (n,))
+    _gmm_param(what, "cdf", cdf, (K,), torch.float64)
+    _gmm_param(what, "mu", mu, (K, D))
+    _gmm_param(what, "L", L, (K, D, D) if full else (K, D))
+    _req_cuda(u, eps, cdf, mu, L)
+    z = torch.empty(n, D, dtype=torch.float32, device=eps.device)
+    k = torch.empty(n, dtype=torch.int32, device=eps.device)
+    if n:
+        native.call("ctvae_gmm_sample", u.data_ptr(), eps.data_ptr(), n, D, K, 1 if full else 0, cdf.data_ptr(), mu.data_ptr(),
+                    L.data_ptr(), z.data_ptr(), k.data_ptr())
+    return z, k

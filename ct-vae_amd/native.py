@@ -112,6 +112,9 @@ SIGNATURES = {
     "ctvae_graph_accumulate": [_fp, _fp, _fp, _f, _i, _i, _i, _fp, _fp, _fp, _fp, _fp, _fp, _vp],
     "ctvae_heatmap_u8": [_fp, _i, _i, _i, _f, _f, _i, _i, _i, _i, _i, _i, _fp, _i, _fp, _sz, _vp],
     "ctvae_latent_accumulate": [_fp, _l, _fp, _l, _i, _i, _fp, _fp, _fp, _fp, _fp, _fp, _vp],
+    "ctvae_gmm_estep": [_fp, _i, _i, _i, _i, _fp, _fp, _fp, _fp, _fp, _fp, _fp, _vp],
+    "ctvae_gmm_mstep": [_fp, _fp, _fp, _i, _i, _i, _i, _fp, _fp, _fp, _fp, _fp, _sz, _vp],
+    "ctvae_gmm_sample": [_fp, _fp, _i, _i, _i, _i, _fp, _fp, _fp, _fp, _fp, _vp],
     "ctvae_recon_record": [_fp, _fp, _i, _i, _i, _fp, _fp, _fp, _i, _i, _vp],
     "ctvae_recon_worst": [_fp] * 6 + [_i] * 3 + [_fp] * 2 + [_i] * 3 + [_fp] * 5 + [_vp],
     "ctvae_freebits_kl_forward_grad": [_fp, _l, _fp, _l, _i, _i, _fp, _f, _f, _fp, _fp, _fp, _fp, _sz, _vp],
@@ -164,6 +167,8 @@ _RESTYPES = {
     "ctvae_grad_segment_chunk_floats": _c.c_size_t,
     "ctvae_mssim_part_floats": _c.c_size_t,
     "ctvae_freebits_workspace_bytes": _c.c_size_t,
+    "ctvae_gmm_mstep_slabs": _c.c_int,
+    "ctvae_gmm_mstep_workspace_bytes": _c.c_size_t,
     "ctvae_glinear_wgrad_ws_bytes": _c.c_size_t,
     "ctvae_conv_input_transform_supported": _c.c_int,
     "ctvae_conv_wgrad_bn_apply_supported": _c.c_int,
@@ -208,6 +213,8 @@ def load():
                        "ctvae_dip_state_floats": [_c.c_int, _c.c_int],
                        "ctvae_vq_ema_supported": [_c.c_int] * 3,
                        "ctvae_freebits_workspace_bytes": [_c.c_int],
+                       "ctvae_gmm_mstep_slabs": [_c.c_int] * 4,
+                       "ctvae_gmm_mstep_workspace_bytes": [_c.c_int] * 4,
                        "ctvae_glinear_wgrad_ws_bytes": [_c.c_int] * 5,
                        "ctvae_conv_wino_filter_floats": [_c.c_int] * 10 + [_c.c_size_t],
                        "ctvae_conv_input_transform_supported": [_c.c_int] * 10,

@@ -63,6 +63,12 @@ MSSIMVAE, LogCoshVAE and BetaVAE with ``loss_type: 'H'``; the training records g
 ``KLD_floored_dims``, validation is unchanged, and the checkpoint gains ``trainer['kl']``: a full resume under other settings is
 refused, ``load_weights_only`` starts the schedule at step 0, a run without the keys ignores the entry.  A refused value or model
 is a SystemExit that names ``exp_params.kld_schedule`` or ``exp_params.kld_free_bits``.
+``exp_params.sample_prior: {type: gmm}`` (with ``components``, 1..64, default 10; ``covariance``, full | diag; ``max_iter``, default 50;
+``tol``, default 1e-3; ``reg_covar``, default 1e-6; ``codes``, mean | sample) fits a Gaussian-mixture prior to the validation codes of
+every validation epoch (experiment.py, latentprior.py): ``val_prior_mixture_loglik`` / ``_standard_loglik`` / ``_iterations`` /
+``_rows`` / ``_nonfinite`` in the epoch records and ``metrics_rank0.jsonl``, ``Priors/latent_prior_<name>_Epoch_<e>.npz`` and, with
+``val_sampling``, ``Samples/sample_mixture_<name>_Epoch_<e>.png`` in the log directory; ``python -m ctvae_amd.fit_prior`` does the same
+for a checkpoint over the training split.  A refused value or model is a SystemExit that names ``exp_params.sample_prior``.
 ``exp_params.recon_stats: true`` (with ``recon_stats_range``, the data range R of the pictures, a float > 0, default 1.0, and
 ``recon_stats_worst``, an integer 0 <= K <= 32, default 8) adds the reconstruction quality per validation image to every validation
 epoch: ``val_recon_psnr`` / ``_ssim`` / ``_mae`` / ``_max_err``, the 5th percentiles and minima ``_psnr_p05`` / ``_ssim_p05`` / ``_psnr_min``
@@ -347,6 +353,21 @@ def exp_latent_stats(config) -> bool:
     return on
 
 
+def exp_sample_prior(config):
+    """``exp_params.sample_prior`` as None (absent: off) or the complete mapping (``latentprior.prior_setting``).  A refused value
+    and a model the mixture does not serve are a SystemExit that names the key."""
+    from . import latentprior
+    try:
+        cfg = latentprior.prior_setting(config['exp_params'].get('sample_prior'))
+    except ValueError as e:
+        raise SystemExit(f"exp_params.{e}")
+    name = config['model_params'].get('name')
+    cls = vae_models.get(name)
+    if cfg is not None and (cls is None or not latentprior.prior_supported(cls)):
+        raise SystemExit(f"exp_params.{latentprior.needs_supported_model(cls, name=repr(name))} (model_params.name)")
+    return cfg
+
+
 def exp_recon_stats(config) -> tuple:
     """``exp_params.recon_stats`` / ``recon_stats_range`` / ``recon_stats_worst`` as ``(on, R, K)``.  A refused value, a dependent key
     without the main one, and a model that hands out several reconstructions per image (IWAE, MIWAE) are a SystemExit that
@@ -424,6 +445,7 @@ def main(argv=None):
     exp_latent_stats(config)                 # refused here, before a device is touched; VAEXperiment reads the key itself
     kl_schedule, kl_free_bits = exp_kl(config)             # likewise
     recon_on, _, _ = exp_recon_stats(config)               # likewise
+    exp_sample_prior(config)                               # likewise
 
     rank =int(os.environ.get("RANK", "0"))
     world = int(os.environ.get("WORLD_SIZE", "1"))

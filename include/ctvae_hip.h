@@ -617,6 +617,45 @@ int ctvae_graph_accumulate(const float* adj, const int32_t* group, const float* 
 int ctvae_latent_accumulate(const float* mu, long mu_pitch, const float* logvar, long logvar_pitch, int B, int L, double* kl_sum,
                             double* mu_sum, double* sig2_sum, double* cov_sum, int32_t* nonfinite, int32_t* rows, void* stream);
 
+/* A Gaussian-mixture latent prior fitted by EM (latentprior.py: GaussianMixturePrior; csrc/gmm.hip).  X is fp32 [N][D] row-major,
+ * 1 <= D <= 256, K components with 1 <= K <= 64; full != 0: full covariances, full == 0: diagonal ones.  The host prepares the
+ * mixture (fp32 device buffers): log_w [K]; mu [K][D]; P, for full [K][D][D] the INVERSE of the lower Cholesky factor L_k of
+ * Sigma_k (lower triangular; only j <= i is read), for diag [K][D] = 1 / sqrt(var); log_det_half [K] = sum_i log diag(L_k)_i.
+ *
+ * E step.  lp[n][k] = log_w[k] - 0.5 * |P_k (x_n - mu_k)|^2 - log_det_half[k] - 0.5 * D * log(2 pi)   (x_n - mu_k is formed in fp32
+ * before the product; full: f32 MFMA tiles with a row-norm epilogue, the k order of the chain is ascending j),
+ * ll[n] = m + log(sum_k exp(lp[n][k] - m)) with m = max_k lp[n][k], r[n][k] = exp(lp[n][k] - ll[n]).  Writes r [N][K] and ll [N]
+ * fp32 and nonfinite [N] int32.  A row with a NaN or +-inf element gets r = 0, ll = 0 and nonfinite = 1 (else 0).  A fixed
+ * summation order: the same bits from run to run.  One launch, no host synchronisation.  N == 0 is a successful no-op; N < 0,
+ * another D or K or a NULL pointer returns -22 and launches nothing. */
+int ctvae_gmm_estep(const float* X, int N, int D, int K, int full, const float* log_w, const float* mu, const float* P,
+                    const float* log_det_half, float* r, float* ll, int32_t* nonfinite, void* stream);
+
+/* M step: one pass over X and r [N][K] (ctvae_gmm_estep's) forms the float64 sums, centred at the CURRENT means m [K][D] fp32:
+ *   Nk [K]              sum_n r[n][k]
+ *   S1 [K][D]           sum_n r[n][k] (x_n - m_k)
+ *   S2                  full: [K][D][D] = sum_n r[n][k] (x_n - m_k)(x_n - m_k)^T, the lower triangle mirrored into the upper;
+ *                       diag: [K][D], that matrix's diagonal
+ * Rows whose nonfinite [N] flag is not 0 are left out (nonfinite may be NULL: no row is).  The host finishes: mu_new = m + S1 / Nk,
+ * Sigma = S2 / Nk - (mu_new - m)(mu_new - m)^T.  Nk, S1 and the diagonal of S2 are float64 throughout (the fp32 operands are
+ * converted first); an off-diagonal tile of the full S2 is an fp32 MFMA sum over 256 rows at a time, added in float64 across
+ * those blocks.  The rows are split into slabs, ctvae_gmm_mstep_slabs(N, D, K, full) of them, every slab summed in ascending row
+ * order by one owner per element and the slabs merged in ascending order by a second launch: no atomics, the same bits from run
+ * to run.  ws: ctvae_gmm_mstep_workspace_bytes(N, D, K, full) bytes of scratch, 8-byte aligned.  N < K, N < 1, another D or K or a
+ * NULL pointer (nonfinite excepted) returns -22, a workspace too small -12; nothing is launched then. */
+int ctvae_gmm_mstep_slabs(int N, int D, int K, int full);
+size_t ctvae_gmm_mstep_workspace_bytes(int N, int D, int K, int full);
+int ctvae_gmm_mstep(const float* X, const float* r, const int32_t* nonfinite, int N, int D, int K, int full, const float* m,
+                    double* Nk, double* S1, double* S2, double* ws, size_t ws_bytes, void* stream);
+
+/* Sampling: z[i][:] = mu_k + L_k eps[i][:] with k = the first index whose cdf[k] > u[i] (K - 1 when none is: a cdf whose last
+ * entry rounds below 1).  u [n] fp32 in [0, 1), eps [n][D] fp32, cdf [K] double (the running sum of the weights), mu [K][D] fp32,
+ * L for full [K][D][D] the lower Cholesky factors (only j <= i is read; an fp32 fma chain over ascending j), for diag [K][D] =
+ * sqrt(var).  Writes z [n][D] fp32 and comp [n] int32.  The kernel holds no random state.  n == 0 is a successful no-op; n < 0,
+ * another D or K or a NULL pointer returns -22 and launches nothing. */
+int ctvae_gmm_sample(const float* u, const float* eps, int n, int D, int K, int full, const double* cdf, const float* mu,
+                     const float* L, float* z, int32_t* comp, void* stream);
+
 /* Reconstruction quality per image (exp_params.recon_stats; reconstats.py: ReconStats).  a (the reconstruction) and b (the target)
  * are fp32 NHWC [B][S][S][C], 11 <= S <= 64, C >= 1.  consts: 13 doubles in HOST memory, read before the call returns: the 11-tap
  * window g (Wang et al. 2004: g[t] ~ exp(-(t-5)^2 / (2 * 1.5^2)), normalised to sum 1), then C1 = (0.01 R)^2 and C2 = (0.03 R)^2
