@@ -1,5 +1,17 @@
 """GPU: every HIP entry point, called through the C ABI, against torch fp32 CPU arithmetic of the same op
-(tolerance 1e-4 absolute on O(1) data, the north_star bound)."""
+(tolerance 1e-4 absolute on O(1) data, the north_star bound).
+
+A first pass over every kernel.  Several families have since got op-by-op suites of their own against float64 references,
+with NaN-prefilled outputs and workspace, two runs for bit-identity and derived bounds; what this file says about them is the
+coarser check:
+  vector quantiser                      tests/test_vq_ops_gpu.py            (tests/vq_checks.py)
+  causal-transition kernels             tests/test_ct_ops_gpu.py            (tests/ct_ops_checks.py)
+  BatchNorm                             tests/test_bn_ops_gpu.py            (tests/bn_checks.py)
+  loss.hip, reparam_* / gauss_latent_* / act_* of pointwise.hip, ladder.hip, tcvae.hip, vamp.hip, swd.hip, gamma.hip,
+  dip.hip, catlatent.hip, mmd.hip, iwloss.hip, ssim.hip
+                                        tests/test_loss_ops_gpu.py          (tests/loss_checks.py)
+Of these, this file holds the first-pass tests of loss / reparam, the categorical latent, MMD, the IW loss and DIP; ladder,
+tcvae, vamp, swd, gamma and ssim have their first-pass checks in tests/test_models_gpu.py."""
 import numpy as np
 import pytest
 import torch
