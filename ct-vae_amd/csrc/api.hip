@@ -455,6 +455,20 @@ int ctvae_conv_backward_bn_rows(int kind, int B, int H, int W, int Ci, int Co, i
 }
 
 static thread_local int g_lazy_pixel_major = 0;   // layout of the slices the next conv_backward_impl(dx_slices) leaves (set by its caller)
+// set by the callers of the next conv_backward_impl (and taken by it):
+static thread_local int g_no_dx = 0;                          // ctvae_conv_backward_nodx: the picture-side conv's g_a is not written
+static thread_local const DyRecompute* g_recompute = nullptr; // ctvae_conv_backward_recompute: dy is absent, formed in the kernel
+
+// the picture-side conv behind the transposed conv of geometry g1 (kind 0): its data-gradient taps for the recompute mode
+static bool recompute_geom(const ConvGeom& g1, int kind2, int Co2, int k2, int stride2, int pad2, int out_pad2, DyRecompute* rc) {
+  if (!upconv_wgrad_supported(g1) || !conv_kind_ok(kind2)) return false;
+  ConvGeom g2;
+  if (conv_geom(g2, kind2, 2, g1.B, g1.sH, g1.sW, g1.sC, Co2, k2, stride2, pad2, out_pad2)) return false;
+  if (!img_dgrad_supported(g2) || g2.B != g1.B || g2.sH != g1.sH || g2.sW != g1.sW) return false;
+  if (rc != nullptr)
+    for (int t = 0; t < 9; ++t) { rc->tdy[t] = g2.taps[0][t].dy; rc->tdx[t] = g2.taps[0][t].dx; rc->twt[t] = g2.taps[0][t].wtap; }
+  return true;
+}
 
 // dx_slices != nullptr: the data gradient must run split-K and leaves its raw slices there, channel-major (SplitKRaw); dx is
 // not written (ctvae_conv_backward_lazy)
@@ -466,7 +480,12 @@ static int conv_backward_impl(int kind, const float* x, const float* dy, const f
                         const float* in_scale, const float* in_shift, int in_act,
                         const float* dy_bn_y, const float* dy_bn_coef, int dy_bn_act, float* gy_out, float* ws, size_t ws_bytes,
                         void* stream, float* dx_slices) {
-  if (!x || !dy || !w || !dw || (!dx && !dx_slices) || !ws || !conv_kind_ok(kind)) return kErrBadArg;
+  const bool no_dx = g_no_dx != 0;
+  const DyRecompute* const recompute = g_recompute;
+  g_no_dx = 0;
+  g_recompute = nullptr;
+  if (!x || (!dy && !recompute) || !w || !dw || (!dx && !dx_slices && !no_dx) || !ws || !conv_kind_ok(kind)) return kErrBadArg;
+  if (recompute != nullptr && (dy_bn_y == nullptr || gy_out == nullptr)) return kErrBadArg;
   const bool bn = bn_part != nullptr;
   if (bn_coef_out != nullptr && !bn) return kErrBadArg;
   if ((bn_dgamma != nullptr) != (bn_dbeta != nullptr) || (bn_dgamma != nullptr && bn_coef_out == nullptr)) return kErrBadArg;
@@ -500,10 +519,17 @@ static int conv_backward_impl(int kind, const float* x, const float* dy, const f
     ctx.dgrad_chunks = pl.splitk > 1 ? (kmax + pl.splitk - 1) / pl.splitk : kmax;
   }
   const InXform xf{in_scale, in_shift, in_act};
-  const DyXform dyx{dy_bn_y, dy_bn_coef, gy_out, dy_bn_act};
+  DyXform dyx{dy_bn_y, dy_bn_coef, gy_out, dy_bn_act};
+  dyx.rc = recompute;
   int rc;
-  if (bn && bn_act != ACT_TANH && x == bn_y && in_scale != nullptr && in_act == bn_act && mask == nullptr && dy_bn_y == nullptr &&
-      img_conv_supported(gw) && img_dgrad_supported(gd) && img_backward_fused_ws_floats(gd) <= half_floats) {
+  const bool img_fused = bn && bn_act != ACT_TANH && x == bn_y && in_scale != nullptr && in_act == bn_act && mask == nullptr &&
+                         dy_bn_y == nullptr && img_conv_supported(gw) && img_dgrad_supported(gd) &&
+                         img_backward_fused_ws_floats(gd) <= half_floats;
+  if ((no_dx && !img_fused) || (recompute != nullptr && !upconv_wgrad_supported(gw))) {   // only the kernels that can do without
+    pair_ctx() = nullptr;
+    return kErrBadArg;
+  }
+  if (img_fused) {
     // picture-side conv behind BatchNorm + activation (final_layer.1-3): the data gradient's pass over y also forms the
     // weight gradient (image.hip img_bwd_fused_kernel) -- x of the weight gradient is act(BN(y)), which that pass computes
     float *part = nullptr, *pb = nullptr;
@@ -550,6 +576,67 @@ int ctvae_conv_backward(int kind, const float* x, const float* dy, const float* 
                             wino_filters, bn_y, bn_mean, bn_invstd, bn_gamma, bn_beta, bn_act, bn_part, bn_part_rows, bn_coef_out,
                             bn_dgamma, bn_dbeta, bn_accumulate, in_scale, in_shift, in_act, dy_bn_y, dy_bn_coef, dy_bn_act, gy_out, ws,
                             ws_bytes, stream, nullptr);
+}
+
+int ctvae_conv_backward_nodx(int kind, const float* x, const float* dy, const float* w, float* dw, float* dbias, int B, int H,
+                             int W, int Ci, int Co, int k, int stride, int pad, int out_pad, int accumulate, const float* bn_y,
+                             const float* bn_mean, const float* bn_invstd, const float* bn_gamma, const float* bn_beta, int bn_act,
+                             float* bn_part, int bn_part_rows, float* bn_coef_out, float* bn_dgamma, float* bn_dbeta,
+                             int bn_accumulate, const float* in_scale, const float* in_shift, int in_act, float* ws, size_t ws_bytes,
+                             void* stream) {
+  g_no_dx = 1;
+  return conv_backward_impl(kind, x, dy, w, dw, dbias, nullptr, B, H, W, Ci, Co, k, stride, pad, out_pad, accumulate, nullptr, 0,
+                            nullptr, bn_y, bn_mean, bn_invstd, bn_gamma, bn_beta, bn_act, bn_part, bn_part_rows, bn_coef_out,
+                            bn_dgamma, bn_dbeta, bn_accumulate, in_scale, in_shift, in_act, nullptr, nullptr, 0, nullptr, ws, ws_bytes,
+                            stream, nullptr);
+}
+
+int ctvae_conv_recompute_supported(int kind, int B, int H, int W, int Ci, int Co, int k, int stride, int pad, int out_pad, int kind2,
+                                   int Co2, int k2, int stride2, int pad2, int out_pad2) {
+  if (!conv_kind_ok(kind)) return 0;
+  ConvGeom g;
+  if (conv_geom(g, kind, 0, B, H, W, Ci, Co, k, stride, pad, out_pad)) return 0;
+  return recompute_geom(g, kind2, Co2, k2, stride2, pad2, out_pad2, nullptr) ? 1 : 0;
+}
+
+int ctvae_conv_backward_recompute(int kind, const float* x, const float* g_pre, const float* w2, const float* w, float* dw,
+                                  float* dbias, float* dx, int B, int H, int W, int Ci, int Co, int k, int stride, int pad, int out_pad,
+                                  int accumulate, const float* bn_y, const float* bn_mean, const float* bn_invstd,
+                                  const float* bn_gamma, const float* bn_beta, int bn_act, float* bn_part, int bn_part_rows,
+                                  float* bn_coef_out, float* bn_dgamma, float* bn_dbeta, int bn_accumulate, const float* in_scale,
+                                  const float* in_shift, int in_act, const float* dy_bn_y, const float* dy_bn_coef, int dy_bn_act,
+                                  float* gy_out, int kind2, int Co2, int k2, int stride2, int pad2, int out_pad2, float* ws,
+                                  size_t ws_bytes, void* stream) {
+  if (!g_pre || !w2 || !dx || !dy_bn_y || !dy_bn_coef || !gy_out || !conv_kind_ok(kind)) return kErrBadArg;
+  ConvGeom g;
+  DyRecompute rc{g_pre, w2, {}, {}, {}};
+  if (conv_geom(g, kind, 0, B, H, W, Ci, Co, k, stride, pad, out_pad)) return kErrBadArg;
+  if (!recompute_geom(g, kind2, Co2, k2, stride2, pad2, out_pad2, &rc)) return kErrBadArg;
+  g_recompute = &rc;
+  return conv_backward_impl(kind, x, nullptr, w, dw, dbias, dx, B, H, W, Ci, Co, k, stride, pad, out_pad, accumulate, nullptr, 0,
+                            nullptr, bn_y, bn_mean, bn_invstd, bn_gamma, bn_beta, bn_act, bn_part, bn_part_rows, bn_coef_out,
+                            bn_dgamma, bn_dbeta, bn_accumulate, in_scale, in_shift, in_act, dy_bn_y, dy_bn_coef, dy_bn_act, gy_out, ws,
+                            ws_bytes, stream, nullptr);
+}
+
+int ctvae_conv_wgrad_recompute(int kind, const float* x, const float* g_pre, const float* w2, float* dw, float* dbias, int B, int H,
+                               int W, int Ci, int Co, int k, int stride, int pad, int out_pad, int accumulate, const float* in_scale,
+                               const float* in_shift, int in_act, const float* dy_bn_y, const float* dy_bn_coef, int dy_bn_act,
+                               float* gy_out, int kind2, int Co2, int k2, int stride2, int pad2, int out_pad2, float* ws,
+                               size_t ws_bytes, void* stream) {
+  if (!x || !g_pre || !w2 || !dw || !ws || !dy_bn_y || !dy_bn_coef || !gy_out || !conv_kind_ok(kind)) return kErrBadArg;
+  if ((in_scale != nullptr) != (in_shift != nullptr)) return kErrBadArg;
+  ConvGeom g;
+  DyRecompute rc{g_pre, w2, {}, {}, {}};
+  if (conv_geom(g, kind, 0, B, H, W, Ci, Co, k, stride, pad, out_pad)) return kErrBadArg;
+  if (!recompute_geom(g, kind2, Co2, k2, stride2, pad2, out_pad2, &rc)) return kErrBadArg;
+  const InXform xf{in_scale, in_shift, in_act};
+  DyXform dyx{dy_bn_y, dy_bn_coef, gy_out, dy_bn_act};
+  dyx.rc = &rc;
+  float* wws = defer_wgrad_ws(ws, ws_bytes / sizeof(float));
+  const int rcode = launch_wgrad(g, x, nullptr, dw, dbias, wws, ws_bytes, accumulate, (hipStream_t)stream, &xf, &dyx);
+  defer_wgrad_done();
+  return rcode;
 }
 
 int ctvae_conv_backward_lazy_slices(int kind, int B, int H, int W, int Ci, int Co, int k, int stride, int pad, int out_pad,

@@ -163,6 +163,14 @@ struct InXform {
 // Lazy BatchNorm-backward apply: a weight-gradient kernel is handed g_a (gradient w.r.t. the BatchNorm+activation
 // output) instead of g_y and forms g_y = k1*g_a*act'(y*scale+shift) + k2*y + k3 itself while loading, also writing it
 // to gy_out for the data-gradient kernel that follows.  coef = [5][C]: k1, k2, k3, scale, shift (bn_bwd_finalize_kernel).
+// g_a itself is absent: the 32 -> 3 picture-side conv behind the BatchNorm left only its 3-channel gradient, and the
+// weight-gradient kernel forms g_a = dgrad(g_pre, w2) per tile as image.hip img_bwd_fused_kernel does (upconv.hip, recompute mode)
+struct DyRecompute {
+  const float* g_pre;   // [B,sH,sW,3]
+  const float* w2;      // [9][32][3]
+  int tdy[9], tdx[9], twt[9];   // the image conv's data-gradient taps (ConvGeom kind 2, class 0)
+};
+
 struct DyXform {
   const float* y;
   const float* coef;
@@ -171,6 +179,7 @@ struct DyXform {
   float* dgamma = nullptr;   // with gy_out null: the kernel also commits the BatchNorm's parameter gradients (coef rows 5, 6)
   float* dbeta = nullptr;
   int bn_accumulate = 0;
+  const DyRecompute* rc = nullptr;   // dY of the launch is then ignored (may be null)
 };
 
 // Winograd filter hand-over between a layer's forward launch and its data-gradient launch (wino.hip)

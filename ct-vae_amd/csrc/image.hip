@@ -560,6 +560,9 @@ __global__ __launch_bounds__(256, 4) void img_dgrad_kernel(const ImgArgs a) {
 // img_wgrad_kernel's own pass over the 134 MB activation (VanillaVAE bs = 256: 67 us).  a = act(gamma * xhat + beta) is the value
 // the BatchNorm-backward sums need anyway.  Slabs out[blockIdx.x][wtap*32 + ci][co] and bias partials pbias[blockIdx.x][co] like
 // img_wgrad_kernel; all merges in a fixed order.
+// STORE = false: g_a is not written (a.out is null) -- the transposed conv's weight-gradient kernel forms it again from the
+// 3-channel gradient (upconv.hip, recompute mode); sums, weight gradient, slabs and bias partials are the same values in the same order.
+template <bool STORE>
 __global__ __launch_bounds__(256, 4) void img_bwd_fused_kernel(const ImgArgs a, float* __restrict__ wpart, float* __restrict__ wpbias) {
   kernarg_warm<sizeof(ImgArgs) + 16>();
   const float bn_slope = act_slope(a.bn_act);
@@ -570,7 +573,7 @@ __global__ __launch_bounds__(256, 4) void img_bwd_fused_kernel(const ImgArgs a, 
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, li = lane & 31, lh = lane >> 5;
   const __amdgpu_buffer_rsrc_t rG = rsrc(a.dY, (long)a.B * a.H * a.W * NO * 4);
   const long obytes = (long)a.B * a.H * a.W * C * 4;
-  const __amdgpu_buffer_rsrc_t rO = rsrc(a.out, obytes);
+  const __amdgpu_buffer_rsrc_t rO = rsrc(a.out, STORE ? obytes : 0);
   const __amdgpu_buffer_rsrc_t rY = rsrc(a.bn_y, obytes);
 
   int koff[14];
@@ -643,8 +646,10 @@ __global__ __launch_bounds__(256, 4) void img_bwd_fused_kernel(const ImgArgs a, 
       const float* gp = &sG[((ly + 1) * PW + li + 1) * 4];
 #pragma unroll
       for (int s = 0; s < 14; ++s) acc = __builtin_amdgcn_mfma_f32_32x32x2f32(gp[koff[s]], bw[s], acc, 0, 0, 0);
+      if constexpr (STORE) {
 #pragma unroll
-      for (int r = 0; r < 16; ++r) st1(rO, rowoff + (unsigned)((8 * (r >> 2) + 4 * lh + (r & 3)) * C) * 4u, acc[r]);
+        for (int r = 0; r < 16; ++r) st1(rO, rowoff + (unsigned)((8 * (r >> 2) + 4 * lh + (r & 3)) * C) * 4u, acc[r]);
+      }
       const float* gw = &sG[ly * PW * 4 + wlane];
       // the BatchNorm's activation is identity / LeakyReLU / ReLU (host-checked): one select for the value, one for the derivative
 #pragma unroll
@@ -1077,8 +1082,11 @@ int launch_img_backward_fused(const ConvGeom& g, const float* dY, const float* W
   const int nwg = img_dgrad_rows(g);
   float* part = ws;
   float* pb = want_bias ? ws + (size_t)nwg * NT * C * NO : nullptr;
-  ProfScope ps("img_bwd_fused_kernel", st, 4.0 * a.ntiles * TH * TW * NT * C * NO, 4.0 * a.ntiles * TH * TW * (C * 2 + NO));
-  hipLaunchKernelGGL(img_bwd_fused_kernel, dim3(nwg), dim3(256), 0, st, a, part, pb);
+  // dX null: the caller forms g_a again where it is consumed (ctvae_conv_backward_nodx); y is read, nothing of that size is written
+  ProfScope ps("img_bwd_fused_kernel", st, 4.0 * a.ntiles * TH * TW * NT * C * NO,
+               4.0 * a.ntiles * TH * TW * (C * (dX != nullptr ? 2 : 1) + NO));
+  if (dX != nullptr) hipLaunchKernelGGL(img_bwd_fused_kernel<true>, dim3(nwg), dim3(256), 0, st, a, part, pb);
+  else hipLaunchKernelGGL(img_bwd_fused_kernel<false>, dim3(nwg), dim3(256), 0, st, a, part, pb);
   CTVAE_LAUNCH_CHECK();
   *part_out = part;
   *pbias_out = pb;

@@ -26,6 +26,8 @@ constexpr int TH = 8, TW = 32, PH = 9, PW = 33, NP = PH * PW /*297*/;
 constexpr int LDA = 36, C = 32, NT = 9, NCLS = 4, MAXT = 4;
 constexpr int NLD = (NP * 8 + 255) / 256;   // 10 float4 per thread
 constexpr unsigned kOOBu = 0x80000000u;
+// recompute mode of the weight gradient: the 3-channel gradient patch of a tile's 16 x 64 output pixels + 1 halo pixel, 4 floats each
+constexpr int GPH = 2 * TH + 2, GPW = 2 * TW + 2, GNP = GPH * GPW /*1188*/, GNLD = (GNP + 255) / 256 /*5*/, NO = 3, NJ = 27;
 
 struct UpArgs {
   const float* X;     // [B,H,W,32]
@@ -39,6 +41,10 @@ struct UpArgs {
   const float* dy_coef;
   float* gy_out;
   int dy_act;
+  // wgrad, recompute mode: dY is absent; g_a = dgrad(rc_g [B,2H,2W,3], rc_w [9][32][3]) of the picture-side conv is formed per block
+  const float* rc_g;
+  const float* rc_w;
+  int rc_tdy[NT], rc_tdx[NT], rc_twt[NT];
   // lazy BatchNorm apply (InXform): X is the raw BatchNorm input of the previous block; the patch is staged as
   // max(t, t*slope), t = X*scale[c] + shift[c] (LeakyReLU / ReLU / none), pixels beyond the image stay 0
   const float* xf_scale;
@@ -307,17 +313,26 @@ struct ClsInfo {
 // whose `s_waitcnt vmcnt(0)` also drains the dy / y loads just issued for the next step -- the read-ahead overlapped nothing:
 // 45 -> 27 us at bs = 64 (one workgroup per CU anyway), and still ahead at bs = 256 where a second workgroup per CU is given up
 // (step 1.582 -> 1.567 ms).
-template <bool FUSED>
-__global__ __launch_bounds__(256, 1) void up_wgrad_kernel(const UpArgs a) {
+//
+// MODE 0: dY is g_y.  MODE 1 (FUSED): dY is g_a, g_y is formed on load and written out.  MODE 2 (RECOMP): FUSED without a g_a
+// tensor -- per (input row, parity class) the 32 class pixels' g_a is 14 MFMAs of the LDS-staged 3-channel gradient patch with the
+// picture-side conv's weights (K = 27, as image.hip img_bwd_fused_kernel: same K order, same operand pairing, so the same values).
+// Lane li's A-operand row is class pixel q(li), q(8a + b) = 8a + 2b, q(8a + 4 + b) = 8a + 2b + 1 (b < 4): register r of lane half
+// lh then holds class pixel 2r + lh, the pixel pair MFMA step r of the weight gradient consumes -- the order of the FUSED path.
+template <int MODE>
+__device__ __forceinline__ void up_wgrad_body(const UpArgs& a) {
+  constexpr bool FUSED = MODE >= 1, RECOMP = MODE == 2;
   kernarg_warm<sizeof(UpArgs)>();
   __shared__ __attribute__((aligned(16))) float sA[NP * LDA];   // 42.8 KB
-  __shared__ __attribute__((aligned(16))) float sR[4 * C * C];  // 16 KB: cross-wave merge, one tap at a time
+  // 16 KB: cross-wave merge, one tap at a time.  RECOMP: during the tile loop the gradient patch [GNP][4] (19 KB) lives here
+  __shared__ __attribute__((aligned(16))) float sR[RECOMP ? GNP * 4 : 4 * C * C];
+  static_assert(GNP * 4 >= 4 * C * C, "the gradient patch is the larger tenant");
   __shared__ float sB[4 * C];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, li = lane & 31, lh = lane >> 5;
   const __amdgpu_buffer_rsrc_t rX = rsrc(a.X, (long)a.B * a.H * a.W * C * 4);
   const int OH = 2 * a.H, OW = 2 * a.W;
   const long obytes = (long)a.B * OH * OW * C * 4;
-  const __amdgpu_buffer_rsrc_t rG = rsrc(a.dY, obytes);
+  const __amdgpu_buffer_rsrc_t rG = RECOMP ? rsrc(a.rc_g, (long)a.B * OH * OW * NO * 4) : rsrc(a.dY, obytes);
   const __amdgpu_buffer_rsrc_t rYb = rsrc(a.dy_y, FUSED ? obytes : 0);
   const __amdgpu_buffer_rsrc_t rGY = rsrc(a.gy_out, FUSED ? obytes : 0);
   const float k1 = FUSED ? a.dy_coef[li] : 0.f, k2 = FUSED ? a.dy_coef[C + li] : 0.f, k3 = FUSED ? a.dy_coef[2 * C + li] : 0.f;
@@ -327,6 +342,23 @@ __global__ __launch_bounds__(256, 1) void up_wgrad_kernel(const UpArgs a) {
   const f32x4 xsc = xf ? *reinterpret_cast<const f32x4*>(a.xf_scale + 4 * (tid & 7)) : f32x4{0.f, 0.f, 0.f, 0.f};
   const f32x4 xsh = xf ? *reinterpret_cast<const f32x4*>(a.xf_shift + 4 * (tid & 7)) : f32x4{0.f, 0.f, 0.f, 0.f};
   const float xns = a.xf_act == ACT_LRELU ? kLeaky : (a.xf_act == ACT_RELU ? 0.f : 1.f);
+
+  // RECOMP: k = 2s + lh = 3t + co: A element = g_pre[p + off_t][co] (LDS offset koff), B element = W2[t][ci = li][co]
+  int koff[RECOMP ? 14 : 1];
+  float bw[RECOMP ? 14 : 1];
+  const int qli = (li & ~7) + 2 * (li & 3) + ((li >> 2) & 1);
+  if constexpr (RECOMP) {
+#pragma unroll
+    for (int s = 0; s < 14; ++s) {
+      const int k0 = 2 * s, k1 = 2 * s + 1;
+      const int t0 = k0 / 3, c0 = k0 % 3, t1 = (k1 < NJ ? k1 : 0) / 3, c1 = (k1 < NJ ? k1 : 0) % 3;
+      const int o0 = (a.rc_tdy[t0] * GPW + a.rc_tdx[t0]) * 4 + c0, o1 = (a.rc_tdy[t1] * GPW + a.rc_tdx[t1]) * 4 + c1;
+      const float w0 = a.rc_w[(a.rc_twt[t0] * C + li) * NO + c0];
+      const float w1 = k1 < NJ ? a.rc_w[(a.rc_twt[t1] * C + li) * NO + c1] : 0.f;
+      koff[s] = lh ? (k1 < NJ ? o1 : 0) : o0;
+      bw[s] = lh ? w1 : w0;
+    }
+  }
 
   f32x16 acc[NT];
 #pragma unroll
@@ -340,13 +372,40 @@ __global__ __launch_bounds__(256, 1) void up_wgrad_kernel(const UpArgs a) {
     const TileXY cur = tile_xy(a, tile);
     CTVAE_PH(up, 1, 1);
     // no cross-tile prefetch here: the nine accumulators need the registers (the CU's second workgroup covers the
-    // wait); the patch goes through in two rounds of 5 float4 per thread for the same reason
+    // wait); the patch goes through in two rounds of 5 float4 per thread for the same reason.  RECOMP (512 registers, and a
+    // tile per workgroup at bs = 64: every round trip of the prologue is on the critical path): the first block's y loads, the
+    // gradient patch and the whole input patch are in flight together, one round
+    constexpr int YS = 2;   // y slots: loads run YS - 1 blocks ahead (a third slot spills: 5 registers to scratch at 512)
+    float yv[RECOMP ? YS : 1][16];
+    unsigned boff[YS];
+    auto y_issue = [&](auto n_c) {
+      constexpr int N = decltype(n_c)::value;
+      const int ly = wave + 4 * (N / 4);
+      boff[N % YS] = (unsigned)((((cur.b * OH + 2 * (cur.y0 + ly) + a.cpy[N % 4]) * OW + 2 * cur.x0 + a.cpx[N % 4] + 2 * lh) * C + li)) * 4u;
 #pragma unroll
-    for (int h = 0; h < 2; ++h) {
-      f32x4 v[NLD / 2];
+      for (int r = 0; r < 16; ++r) yv[N % YS][r] = ld1(rYb, boff[N % YS] + (unsigned)(4 * r * C) * 4u);
+    };
+    float gq[RECOMP ? GNLD : 1][NO];
+    if constexpr (RECOMP) {   // gradient patch: output pixels (2 y0 - 1 + py, 2 x0 - 1 + px), outside the image 0
+      y_issue(std::integral_constant<int, 0>{});
 #pragma unroll
-      for (int j = 0; j < NLD / 2; ++j) {
-        const int e = tid + 256 * (j + h * (NLD / 2));
+      for (int j = 0; j < GNLD; ++j) {
+        const int pp = tid + 256 * j;
+        const int py = pp / GPW, px = pp - py * GPW;
+        const int iy = 2 * cur.y0 - 1 + py, ix = 2 * cur.x0 - 1 + px;
+        const bool ok = pp < GNP && (unsigned)iy < (unsigned)OH && (unsigned)ix < (unsigned)OW;
+        const unsigned off = (unsigned)(((cur.b * OH + iy) * OW + ix) * NO) * 4u;
+#pragma unroll
+        for (int n = 0; n < NO; ++n) gq[j][n] = ld1(rG, ok ? off + 4u * n : kOOBu);
+      }
+    }
+    constexpr int NR = RECOMP ? 1 : 2, NPR = NLD / NR;
+#pragma unroll
+    for (int h = 0; h < NR; ++h) {
+      f32x4 v[NPR];
+#pragma unroll
+      for (int j = 0; j < NPR; ++j) {
+        const int e = tid + 256 * (j + h * (NPR));
         const int pp = e >> 3, c4 = e & 7;
         const int py = (pp * 1986) >> 16, px = pp - py * PW;
         const int iy = cur.y0 + py, ix = cur.x0 + px;
@@ -355,8 +414,8 @@ __global__ __launch_bounds__(256, 1) void up_wgrad_kernel(const UpArgs a) {
       }
       if (xf) {   // lazy BatchNorm apply of the previous block (channel quad e & 7 = tid & 7: per-thread coefficients)
 #pragma unroll
-        for (int j = 0; j < NLD / 2; ++j) {
-          const int e = tid + 256 * (j + h * (NLD / 2));
+        for (int j = 0; j < NPR; ++j) {
+          const int e = tid + 256 * (j + h * (NPR));
           const int pp = e >> 3;
           const int py = (pp * 1986) >> 16, px = pp - py * PW;
           const float inside = (cur.y0 + py < a.H && cur.x0 + px < a.W) ? 1.f : 0.f;
@@ -368,14 +427,93 @@ __global__ __launch_bounds__(256, 1) void up_wgrad_kernel(const UpArgs a) {
         }
       }
 #pragma unroll
-      for (int j = 0; j < NLD / 2; ++j) {
-        const int e = tid + 256 * (j + h * (NLD / 2));
+      for (int j = 0; j < NPR; ++j) {
+        const int e = tid + 256 * (j + h * (NPR));
         if (e < NP * 8) *reinterpret_cast<f32x4*>(&sA[(e >> 3) * LDA + 4 * (e & 7)]) = v[j];
+      }
+    }
+    if constexpr (RECOMP) {
+#pragma unroll
+      for (int j = 0; j < GNLD; ++j) {
+        const int pp = tid + 256 * j;
+        if (pp < GNP)
+#pragma unroll
+          for (int n = 0; n < NO; ++n) sR[pp * 4 + n] = gq[j][n];
       }
     }
     __syncthreads();
 
     CTVAE_PH(up, 1, 2);
+    if constexpr (RECOMP) {
+      // one block = (row, class): 32 class pixels = 16 pixel pairs.  Its 16 y loads are issued one block ahead (two register
+      // slots; the first block's in front of the staging); the 14 g_a MFMAs of block n + 1 (one dependent chain on one
+      // accumulator) are spread one per pixel pair behind the weight-gradient MFMAs of block n, which are independent of them
+      f32x16 ga[2];
+      auto gp_of = [&](int n) {
+        const int ly = wave + 4 * (n / 4), c = n % 4;
+        return &sR[((2 * ly + a.cpy[c] + 1) * GPW + 2 * qli + a.cpx[c] + 1) * 4];
+      };
+      auto run_blk = [&](auto n_c) {
+        constexpr int N = decltype(n_c)::value;
+        constexpr int CLS = N % 4, slot = N % YS, gs = N % 2, gn = (N + 1) % 2;
+        constexpr bool more = N + 1 < 8;
+        using CI = ClsInfo<CLS>;
+        const int ly = wave + 4 * (N / 4);
+        if constexpr (N + YS - 1 < 8) y_issue(std::integral_constant<int, N + YS - 1>{});
+        const float* gpn = gp_of(more ? N + 1 : N);
+        int xo[CI::ntaps];
+#pragma unroll
+        for (int t = 0; t < CI::ntaps; ++t) xo[t] = ((ly + a.tdy[CLS][t]) * PW + lh + a.tdx[CLS][t]) * LDA + li;
+        float xa[CI::ntaps], xb[CI::ntaps];
+#pragma unroll
+        for (int t = 0; t < CI::ntaps; ++t) xa[t] = sA[xo[t]];
+        float gcur = 0.f, gnxt = 0.f;
+        if constexpr (more) {
+          gcur = gpn[koff[0]];
+#pragma unroll
+          for (int r = 0; r < 16; ++r) ga[gn][r] = 0.f;
+        }
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+          if (r + 1 < 16) {
+#pragma unroll
+            for (int t = 0; t < CI::ntaps; ++t) xb[t] = sA[xo[t] + 2 * (r + 1) * LDA];
+          }
+          if constexpr (more) {
+            if (r + 1 < 14) gnxt = gpn[koff[r + 1]];
+          }
+          const float yy = yv[slot][r];
+          float d = ga[gs][r];
+          const float g1 = (yy * ksc + ksh) > 0.f ? d : d * nslope;   // LeakyReLU / ReLU / identity derivative
+          d = k1 * g1 + k2 * yy + k3;
+          st1(rGY, boff[slot] + (unsigned)(4 * r * C) * 4u, d);
+          bsum += d;
+#pragma unroll
+          for (int t = 0; t < CI::ntaps; ++t)
+            acc[CI::first + t] = __builtin_amdgcn_mfma_f32_32x32x2f32(xa[t], d, acc[CI::first + t], 0, 0, 0);
+          if constexpr (more) {
+            if (r < 14) ga[gn] = __builtin_amdgcn_mfma_f32_32x32x2f32(gcur, bw[r], ga[gn], 0, 0, 0);
+          }
+#pragma unroll
+          for (int t = 0; t < CI::ntaps; ++t) xa[t] = xb[t];
+          gcur = gnxt;
+          __builtin_amdgcn_sched_barrier(0);
+        }
+      };
+      if constexpr (YS > 2) y_issue(std::integral_constant<int, 1>{});
+      {
+        const float* gp0 = gp_of(0);
+#pragma unroll
+        for (int r = 0; r < 16; ++r) ga[0][r] = 0.f;
+#pragma unroll
+        for (int s = 0; s < 14; ++s) ga[0] = __builtin_amdgcn_mfma_f32_32x32x2f32(gp0[koff[s]], bw[s], ga[0], 0, 0, 0);
+      }
+#define UPW_BLK(N_) run_blk(std::integral_constant<int, N_>{});
+      UPW_BLK(0) UPW_BLK(1) UPW_BLK(2) UPW_BLK(3)
+      CTVAE_PH(up, 1, 3);
+      UPW_BLK(4) UPW_BLK(5) UPW_BLK(6) UPW_BLK(7)
+#undef UPW_BLK
+    } else {
     // one step = (row, class, half row): 8 pixel pairs.  Its dy (and y) loads are issued TWO steps ahead (three register slots):
     // with one wave per SIMD a step of the one-tap class is 8 MFMAs = 0.2 us, far less than a memory round trip
     float dv[3][8], yv[FUSED ? 3 : 1][FUSED ? 8 : 1];
@@ -444,6 +582,7 @@ __global__ __launch_bounds__(256, 1) void up_wgrad_kernel(const UpArgs a) {
     CTVAE_PH(up, 1, 3);
     UPW_STEP(8) UPW_STEP(9) UPW_STEP(10) UPW_STEP(11) UPW_STEP(12) UPW_STEP(13) UPW_STEP(14) UPW_STEP(15)
 #undef UPW_STEP
+    }
     CTVAE_PH(up, 1, 4);
     __syncthreads();
   }
@@ -471,6 +610,18 @@ __global__ __launch_bounds__(256, 1) void up_wgrad_kernel(const UpArgs a) {
   merge_tap(a.twt[3][3], acc[8]);
   if (a.pbias != nullptr && tid < C) a.pbias[(long)blockIdx.x * C + tid] = ((sB[tid] + sB[C + tid]) + sB[2 * C + tid]) + sB[3 * C + tid];
   CTVAE_PH(up, 1, 5);
+}
+
+template <bool FUSED>
+__global__ __launch_bounds__(256, 1) void up_wgrad_kernel(const UpArgs a) {
+  up_wgrad_body<FUSED ? 1 : 0>(a);
+}
+// the recompute mode under the same kernel name (traces and traffic summaries are keyed on it)
+struct Recompute {};
+template <typename Mode>
+__global__ __launch_bounds__(256, 1) void up_wgrad_kernel(const UpArgs a) {
+  static_assert(std::is_same<Mode, Recompute>::value, "modes 0 / 1 are up_wgrad_kernel<false> / <true>");
+  up_wgrad_body<2>(a);
 }
 
 void fill(UpArgs& a, const ConvGeom& g) {
@@ -550,11 +701,28 @@ int launch_upconv_wgrad(const ConvGeom& g, const float* X, const float* dY, floa
   }
   if (dyx != nullptr && dyx->y != nullptr && dyx->act != ACT_NONE && dyx->act != ACT_RELU && dyx->act != ACT_LRELU) return kErrBadArg;
   if (dyx != nullptr && dyx->y != nullptr) { a.dy_y = dyx->y; a.dy_coef = dyx->coef; a.gy_out = dyx->gy_out; a.dy_act = dyx->act; }
+  const DyRecompute* rc = dyx != nullptr ? dyx->rc : nullptr;
+  if (rc != nullptr) {
+    if (a.dy_y == nullptr || a.dy_coef == nullptr || a.gy_out == nullptr || rc->g_pre == nullptr || rc->w2 == nullptr) return kErrBadArg;
+    for (int c = 0; c < NCLS; ++c)
+      if (a.cpy[c] < 0 || a.cpy[c] > 1 || a.cpx[c] < 0 || a.cpx[c] > 1) return kErrBadArg;   // the patch has a 1-pixel halo
+    for (int t = 0; t < NT; ++t) {
+      if (rc->tdy[t] < -1 || rc->tdy[t] > 1 || rc->tdx[t] < -1 || rc->tdx[t] > 1 || rc->twt[t] < 0 || rc->twt[t] >= NT) return kErrBadArg;
+      a.rc_tdy[t] = rc->tdy[t]; a.rc_tdx[t] = rc->tdx[t]; a.rc_twt[t] = rc->twt[t];
+    }
+    a.rc_g = rc->g_pre; a.rc_w = rc->w2;
+  } else if (dY == nullptr) {
+    return kErrBadArg;
+  }
   const int nwg = upconv_rows(g);
   a.out = ws;
   a.pbias = want_bias ? ws + (size_t)nwg * NT * C * C : nullptr;
-  ProfScope ps("up_wgrad_kernel", st, 2.0 * a.ntiles * TH * TW * NT * C * C, 4.0 * a.ntiles * TH * TW * C * 5.0);
-  if (a.dy_y != nullptr) hipLaunchKernelGGL(up_wgrad_kernel<true>, dim3(nwg), dim3(256), 0, st, a);
+  // per input pixel: x + the four output pixels of dy; recompute mode reads y and the 3-channel gradient and writes g_y
+  const double px_bytes = rc != nullptr ? 4.0 * (C * 9.0 + 4.0 * NO) : 4.0 * C * 5.0;
+  const double px_flops = 2.0 * NT * C * C + (rc != nullptr ? 2.0 * 4 * NJ * C : 0.0);
+  ProfScope ps("up_wgrad_kernel", st, a.ntiles * TH * TW * px_flops, a.ntiles * TH * TW * px_bytes);
+  if (rc != nullptr) hipLaunchKernelGGL(up_wgrad_kernel<Recompute>, dim3(nwg), dim3(256), 0, st, a);
+  else if (a.dy_y != nullptr) hipLaunchKernelGGL(up_wgrad_kernel<true>, dim3(nwg), dim3(256), 0, st, a);
   else hipLaunchKernelGGL(up_wgrad_kernel<false>, dim3(nwg), dim3(256), 0, st, a);
   CTVAE_LAUNCH_CHECK();
   *part_out = a.out;

@@ -398,6 +398,7 @@ int launch_wgrad(const ConvGeom& g, const float* X, const float* dY, float* dW, 
   // BN-backward on load: the transposed-conv kernel (writes g_y for the data gradient) and encoder.0's (no data gradient, no g_y)
   if (dyx != nullptr && dyx->y != nullptr && !up && !(enc && dyx->gy_out == nullptr)) return kErrBadArg;
   if (dyx != nullptr && dyx->y != nullptr && up && dyx->gy_out == nullptr) return kErrBadArg;
+  if (dyx != nullptr && dyx->rc != nullptr && (!up || dyx->y == nullptr)) return kErrBadArg;   // g_a formed in the kernel: upconv.hip only
   if (up) {
     float *part = nullptr, *pb = nullptr;
     int np = 0;

@@ -453,14 +453,22 @@ def _bn_commit_args(bn_commit):
     return (bn_commit[0].data_ptr(), bn_commit[1].data_ptr(), bn_commit[2]) if bn_commit is not None else (None, None, 0)
 
 
-def conv_wgrad_raw(x, dy, w_param, b_param, spec: ConvSpec, in_coef=None, in_act=ACT_NONE, dy_bn=None, bn_commit=None):
+def conv_wgrad_raw(x, dy, w_param, b_param, spec: ConvSpec, in_coef=None, in_act=ACT_NONE, dy_bn=None, bn_commit=None,
+                   recompute=None):
     """dy_bn = (y, coef[5][Co], act, gy_out): dy is g_a of the BatchNorm behind this layer; g_y is formed on load and
     written to gy_out (ctvae_conv_wgrad dy_bn_*).  gy_out None + bn_commit = (dgamma, dbeta, accumulate): the layer with no
-    data gradient (encoder.0) -- g_y is never written and the kernel commits the BatchNorm's parameter gradients."""
+    data gradient (encoder.0) -- g_y is never written and the kernel commits the BatchNorm's parameter gradients.
+    recompute = (w2, spec2) with dy_bn: dy is the 3-channel gradient of the picture-side conv spec2 behind that BatchNorm and the
+    kernel forms g_a itself (ctvae_conv_wgrad_recompute, where conv_recompute_supported)."""
     B, H, W, _ = x.shape
     ws = native.workspace(x.device)
     gw, gb, acc = _grad_targets(w_param, b_param)
     g = spec.geom(B, H, W)
+    if recompute is not None:
+        native.call("ctvae_conv_wgrad_recompute", g[0], x.data_ptr(), dy.data_ptr(), recompute[0].data_ptr(), gw.data_ptr(),
+                    native.ptr(gb), *g[1:], acc, *_coef_ptrs(in_coef, spec.ci), in_act, *_dy_bn_args(dy_bn),
+                    *_conv2_args(recompute[1]), ws.data_ptr(), ws.numel() * 4)
+        return
     native.call("ctvae_conv_wgrad", g[0], x.data_ptr(), dy.data_ptr(), gw.data_ptr(), native.ptr(gb), *g[1:], acc,
                 *_coef_ptrs(in_coef, spec.ci), in_act, *_dy_bn_args(dy_bn), *_bn_commit_args(bn_commit),
                 ws.data_ptr(), ws.numel() * 4)
@@ -486,12 +494,13 @@ def _conv_backward_lazy(x, dy, w_param, gw, gb, acc, spec, in_coef, in_act, pixe
 
 
 def conv_backward_raw(x, dy, w_param, b_param, spec: ConvSpec, link=None, mask=None, mask_act=ACT_NONE, wino_filters=None,
-                      in_coef=None, in_act=ACT_NONE, dy_bn=None, bn_commit=None, grad_slices=False):
+                      in_coef=None, in_act=ACT_NONE, dy_bn=None, bn_commit=None, grad_slices=False, recompute=None):
     """ctvae_conv_backward: weight (+bias) gradient into ``.grad`` and the data gradient of one layer in one call (the
     two GEMMs share a launch when both run their 64x64 tile kernels).  ``link``: BNLink of the layer that produced x --
     its BatchNorm-backward sums come out of the data gradient's epilogues and its finalize rides in this call's finishing
     launch.  in_coef / in_act / dy_bn: the weight gradient's options of conv_wgrad_raw.  bn_commit = (dgamma, dbeta,
-    accumulate): the rider also commits that BatchNorm's parameter gradients (only where no apply launch follows)."""
+    accumulate): the rider also commits that BatchNorm's parameter gradients (only where no apply launch follows).
+    recompute = (w2, spec2), with dy_bn and without mask / Winograd filters: as in conv_wgrad_raw (ctvae_conv_backward_recompute)."""
     B, H, W, _ = x.shape
     ws = native.workspace(x.device)
     g = spec.geom(B, H, W)
@@ -525,6 +534,17 @@ def conv_backward_raw(x, dy, w_param, b_param, spec: ConvSpec, link=None, mask=N
     cg, cb, cacc = _bn_commit_args(bn_commit)
     if coef is None:
         cg = cb = None        # no rider, nothing commits
+    if recompute is not None:
+        native.call("ctvae_conv_backward_recompute", g[0], x.data_ptr(), dy.data_ptr(), recompute[0].data_ptr(), w_param.data_ptr(),
+                    gw.data_ptr(), native.ptr(gb), dx.data_ptr(), *g[1:], acc,
+                    native.ptr(bn.y if bn else None), native.ptr(bn.mean if bn else None), native.ptr(bn.invstd if bn else None),
+                    native.ptr(bn.gamma if bn else None), native.ptr(bn.beta if bn else None), bn.act if bn else 0,
+                    native.ptr(part), rows, native.ptr(coef), cg, cb, cacc,
+                    *_coef_ptrs(in_coef, spec.ci), in_act, *_dy_bn_args(dy_bn), *_conv2_args(recompute[1]),
+                    ws.data_ptr(), ws.numel() * 4)
+        if bn is not None:
+            bn.publish(dx, part, rows, coef)
+        return dx
     native.call("ctvae_conv_backward", g[0], x.data_ptr(), dy.data_ptr(), w_param.data_ptr(), gw.data_ptr(), native.ptr(gb),
                 dx.data_ptr(), *g[1:], acc, native.ptr(mask), mask_act, native.ptr(wino_filters),
                 native.ptr(bn.y if bn else None), native.ptr(bn.mean if bn else None), native.ptr(bn.invstd if bn else None),
@@ -534,6 +554,37 @@ def conv_backward_raw(x, dy, w_param, b_param, spec: ConvSpec, link=None, mask=N
     if bn is not None:
         bn.publish(dx, part, rows, coef)
     return dx
+
+
+def _conv2_args(spec2: ConvSpec):
+    """kind2, Co2, k2, stride2, pad2, out_pad2: how the ..._recompute entry points name the picture-side conv behind a layer."""
+    return (spec2.kind, spec2.co, spec2.k, spec2.stride, spec2.pad, spec2.out_pad)
+
+
+def conv_recompute_supported(spec: ConvSpec, spec2: ConvSpec, B, H, W) -> bool:
+    """ctvae_conv_recompute_supported: can this layer's weight-gradient kernel form g_a itself from the 3-channel gradient of the
+    picture-side conv spec2 that reads this layer's output through a BatchNorm (the final block)?"""
+    return spec2.ci == spec.co and bool(_geom_query("ctvae_conv_recompute_supported", spec.geom(B, H, W), *_conv2_args(spec2)))
+
+
+def conv_backward_nodx_raw(x, dy, w_param, b_param, spec: ConvSpec, link, in_coef, in_act, bn_commit):
+    """ctvae_conv_backward_nodx: conv_backward_raw of the picture-side conv behind the BatchNorm ``link`` (x is its raw y, read
+    through in_coef) without the data gradient tensor.  Returns the finalized [7][Ci] coefficient block of that BatchNorm, or None
+    where this form does not apply and nothing was launched (the data gradient's pass could not emit the sums)."""
+    B, H, W, _ = x.shape
+    ws = native.workspace(x.device)
+    g = spec.geom(B, H, W)
+    rows = max(_geom_query("ctvae_conv_backward_bn_rows", g, ws.numel() * 4), 0)
+    if rows <= 0 or tuple(link.y.shape) != (B, H, W, spec.ci) or in_coef is None:
+        return None
+    gw, gb, acc = _grad_targets(w_param, b_param)
+    part = torch.empty(rows * spec.ci * 2, dtype=torch.float32, device=dy.device)
+    coef = torch.empty(7 * spec.ci, dtype=torch.float32, device=dy.device)
+    native.call("ctvae_conv_backward_nodx", g[0], x.data_ptr(), dy.data_ptr(), w_param.data_ptr(), gw.data_ptr(), native.ptr(gb),
+                *g[1:], acc, link.y.data_ptr(), link.mean.data_ptr(), link.invstd.data_ptr(), link.gamma.data_ptr(),
+                link.beta.data_ptr(), link.act, part.data_ptr(), rows, coef.data_ptr(), *_bn_commit_args(bn_commit),
+                *_coef_ptrs(in_coef, spec.ci), in_act, ws.data_ptr(), ws.numel() * 4)
+    return coef
 
 
 def wgrad_then_dgrad(x, g, w_param, b_param, spec, need_dgrad, link=None, wino_filters=None, in_coef=None, in_act=ACT_NONE,
@@ -991,7 +1042,9 @@ class ConvBNActConvAct(Function):
 
     The BatchNorm output is never written: conv1 leaves y and the per-channel affine, conv2's forward and weight
     gradient apply affine + LeakyReLU while staging their input tiles, conv2's data gradient emits the BatchNorm's
-    backward sums.  On the 64x64x32 activations of this block that removes two full passes over 134 MB per step."""
+    backward sums.  On the 64x64x32 activations of this block that removes two full passes over 134 MB per step.
+    Backward, where conv_recompute_supported: conv2's data gradient g_a is not written either -- conv1's weight-gradient kernel
+    forms it again per tile from the 3-channel gradient (ctvae_conv_backward_nodx, ctvae_conv_backward_recompute)."""
 
     @staticmethod
     def forward(ctx, x, w1, b1, gamma, beta, running_mean, running_var, num_batches_tracked, w2, b2, training, spec1, spec2, bn_act):
@@ -1026,6 +1079,20 @@ class ConvBNActConvAct(Function):
         grads = _grad_targets(gamma, beta)
         lazy = wgrad_bn_apply_supported(spec1, x.shape[0], x.shape[1], x.shape[2])
         g_y = torch.empty_like(y1)
+        in_coef, in_act = ctx.lazy_in if ctx.lazy_in is not None else (None, ACT_NONE)
+        if lazy and conv_recompute_supported(spec1, spec2, x.shape[0], x.shape[1], x.shape[2]):
+            # g_a [B,2H,2W,32] is never allocated: conv2's backward runs without its data gradient's stores, and conv1's
+            # weight-gradient kernel forms g_a again, tile by tile, from the 3-channel g_pre (same values, bit for bit)
+            c7 = conv_backward_nodx_raw(y1, g_pre, w2, b2, spec2, link, coef, ctx.bn_act, grads)
+            if c7 is not None:
+                dy_bn, rc = (y1, c7, ctx.bn_act, g_y), (w2, spec2)
+                if ctx.needs_input_grad[0]:
+                    g_x = conv_backward_raw(x, g_pre, w1, b1, spec1, link=ctx.link_in, dy_bn=dy_bn, in_coef=in_coef, in_act=in_act,
+                                            recompute=rc)
+                else:
+                    conv_wgrad_raw(x, g_pre, w1, b1, spec1, dy_bn=dy_bn, in_coef=in_coef, in_act=in_act, recompute=rc)
+                    g_x = None
+                return (g_x,) + (None,) * 13
         # conv2's weight gradient, its data gradient (which emits the BatchNorm's backward sums) and the BatchNorm's
         # finalize in one call: the finalize rides in the slab-reduction launch (the link is local to this node, so the
         # rider commits d gamma / d beta itself when no apply launch follows)
@@ -1040,7 +1107,6 @@ class ConvBNActConvAct(Function):
             bcoef = c7                                           # rows 0-4 are the coefficients the weight-gradient kernel reads
         else:
             _bn_backward(g_a, y1, bn, ctx.bn_act, g_y, grads, coef_in=c7)
-        in_coef, in_act = ctx.lazy_in if ctx.lazy_in is not None else (None, ACT_NONE)
         if lazy:
             # the weight-gradient kernel turns g_a into g_y on load and leaves g_y behind for the data gradient
             if ctx.needs_input_grad[0]:

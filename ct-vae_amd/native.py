@@ -27,6 +27,12 @@ SIGNATURES = {
     "ctvae_conv_wgrad": [_i, _fp, _fp, _fp, _fp] + [_i] * 10 + [_fp, _fp, _i, _fp, _fp, _i, _fp, _fp, _fp, _i, _fp, _sz, _vp],
     "ctvae_conv_backward": [_i, _fp, _fp, _fp, _fp, _fp, _fp] + [_i] * 10 + [_fp, _i, _fp, _fp, _fp, _fp, _fp, _fp, _i, _fp, _i,
                             _fp, _fp, _fp, _i, _fp, _fp, _i, _fp, _fp, _i, _fp, _fp, _sz, _vp],
+    "ctvae_conv_backward_nodx": [_i, _fp, _fp, _fp, _fp, _fp] + [_i] * 10 + [_fp, _fp, _fp, _fp, _fp, _i, _fp, _i, _fp, _fp, _fp, _i,
+                                 _fp, _fp, _i, _fp, _sz, _vp],
+    "ctvae_conv_backward_recompute": [_i, _fp, _fp, _fp, _fp, _fp, _fp, _fp] + [_i] * 10 + [_fp, _fp, _fp, _fp, _fp, _i, _fp, _i, _fp,
+                                      _fp, _fp, _i, _fp, _fp, _i, _fp, _fp, _i, _fp] + [_i] * 6 + [_fp, _sz, _vp],
+    "ctvae_conv_wgrad_recompute": [_i, _fp, _fp, _fp, _fp, _fp] + [_i] * 10 + [_fp, _fp, _i, _fp, _fp, _i, _fp] + [_i] * 6
+                                   + [_fp, _sz, _vp],
     "ctvae_conv_backward_lazy": [_i, _fp, _fp, _fp, _fp, _fp, _fp] + [_i] * 10 + [_fp, _fp, _i, _i, _fp, _sz, _vp],
     "ctvae_bn_backward_fused": [_fp, _i] + [_i] * 10 + [_fp, _fp, _fp, _fp, _fp, _i, _fp, _fp, _fp, _i, _vp],
     "ctvae_bn_forward": [_fp, _i, _i, _fp, _fp, _fp, _fp, _f, _f, _i, _i, _fp, _fp, _fp, _fp, _fp, _sz, _vp],
@@ -172,6 +178,7 @@ _RESTYPES = {
     "ctvae_glinear_wgrad_ws_bytes": _c.c_size_t,
     "ctvae_conv_input_transform_supported": _c.c_int,
     "ctvae_conv_wgrad_bn_apply_supported": _c.c_int,
+    "ctvae_conv_recompute_supported": _c.c_int,
 }
 EXPORTS = sorted(list(SIGNATURES) + list(_RESTYPES))
 
@@ -218,7 +225,8 @@ def load():
                        "ctvae_glinear_wgrad_ws_bytes": [_c.c_int] * 5,
                        "ctvae_conv_wino_filter_floats": [_c.c_int] * 10 + [_c.c_size_t],
                        "ctvae_conv_input_transform_supported": [_c.c_int] * 10,
-                       "ctvae_conv_wgrad_bn_apply_supported": [_c.c_int] * 10}.get(name, [])
+                       "ctvae_conv_wgrad_bn_apply_supported": [_c.c_int] * 10,
+                       "ctvae_conv_recompute_supported": [_c.c_int] * 16}.get(name, [])
     if lib.ctvae_arch() != b"gfx950":
         raise RuntimeError("libctvae_hip.so was not built for gfx950")
     _lib = lib

@@ -182,6 +182,41 @@ int ctvae_bn_backward_fused(const float* g_a_slices, int slices, int kind, int B
 int ctvae_conv_wgrad_bn_apply_supported(int kind, int B, int H, int W, int Ci, int Co, int k, int stride, int pad,
                                         int out_pad);
 
+/* The final block (vanilla_vae.py:64-75: ConvTranspose2d 32->32 s2, BatchNorm2d, LeakyReLU, Conv2d 32->3 k3 p1, Tanh) without
+ * the tensor g_a between its two convolutions.  g_a [B,2H,2W,32] is the picture-side conv's data gradient: a K = 27 dot product
+ * of its 3-channel gradient g_pre with its weights w2 per element, written once and read once.  Instead:
+ * ctvae_conv_backward_nodx: ctvae_conv_backward of the picture-side conv in its one-kernel form (x == bn_y, in_scale / in_shift of
+ * that BatchNorm: image.hip img_bwd_fused_kernel) with no dx -- weight and bias gradient, the BatchNorm's backward sums in
+ * bn_part and the finalize rider (bn_coef_out, bn_dgamma / bn_dbeta) as there, the same values in the same order; kErrBadArg
+ * for every layer that is not that form.
+ * ctvae_conv_backward_recompute / ctvae_conv_wgrad_recompute: ctvae_conv_backward / ctvae_conv_wgrad of the transposed conv
+ * with dy_bn_y / dy_bn_coef / gy_out (all required) where dy is absent: the weight-gradient kernel stages g_pre [B,2H,2W,3]
+ * per tile and forms g_a itself with w2 [9][32][3] (same K order as the picture-side kernel: bit-identical g_a, hence g_y, dw,
+ * dbias and dx).  kind2, Co2, k2, stride2, pad2, out_pad2: the picture-side conv (its input is this layer's output).
+ * Only where ctvae_conv_recompute_supported says 1 (this layer 32->32 k3 s2 p1 op1 with H % 8 == 0, W % 32 == 0; that conv 32->3
+ * k3 s1 p1), else kErrBadArg. */
+int ctvae_conv_recompute_supported(int kind, int B, int H, int W, int Ci, int Co, int k, int stride, int pad, int out_pad, int kind2,
+                                   int Co2, int k2, int stride2, int pad2, int out_pad2);
+int ctvae_conv_backward_nodx(int kind, const float* x, const float* dy, const float* w, float* dw, float* dbias, int B, int H,
+                             int W, int Ci, int Co, int k, int stride, int pad, int out_pad, int accumulate, const float* bn_y,
+                             const float* bn_mean, const float* bn_invstd, const float* bn_gamma, const float* bn_beta, int bn_act,
+                             float* bn_part, int bn_part_rows, float* bn_coef_out, float* bn_dgamma, float* bn_dbeta,
+                             int bn_accumulate, const float* in_scale, const float* in_shift, int in_act, float* ws, size_t ws_bytes,
+                             void* stream);
+int ctvae_conv_backward_recompute(int kind, const float* x, const float* g_pre, const float* w2, const float* w, float* dw,
+                                  float* dbias, float* dx, int B, int H, int W, int Ci, int Co, int k, int stride, int pad, int out_pad,
+                                  int accumulate, const float* bn_y, const float* bn_mean, const float* bn_invstd,
+                                  const float* bn_gamma, const float* bn_beta, int bn_act, float* bn_part, int bn_part_rows,
+                                  float* bn_coef_out, float* bn_dgamma, float* bn_dbeta, int bn_accumulate, const float* in_scale,
+                                  const float* in_shift, int in_act, const float* dy_bn_y, const float* dy_bn_coef, int dy_bn_act,
+                                  float* gy_out, int kind2, int Co2, int k2, int stride2, int pad2, int out_pad2, float* ws,
+                                  size_t ws_bytes, void* stream);
+int ctvae_conv_wgrad_recompute(int kind, const float* x, const float* g_pre, const float* w2, float* dw, float* dbias, int B, int H,
+                               int W, int Ci, int Co, int k, int stride, int pad, int out_pad, int accumulate, const float* in_scale,
+                               const float* in_shift, int in_act, const float* dy_bn_y, const float* dy_bn_coef, int dy_bn_act,
+                               float* gy_out, int kind2, int Co2, int k2, int stride2, int pad2, int out_pad2, float* ws,
+                               size_t ws_bytes, void* stream);
+
 /* Train/eval BatchNorm2d + activation on an [R=B*H*W][C] matrix (vanilla_vae.py:30-31,56-57,71-72).
  * training: batch statistics (biased var, eps), running stats updated with `momentum` and the unbiased
  * variance; save_mean/save_invstd [C] are written for the backward pass; num_batches_tracked (may be NULL) is
