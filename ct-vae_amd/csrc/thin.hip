@@ -230,16 +230,49 @@ static int max_taps(const ConvGeom& g) {
   return m;
 }
 
-static bool thin_shape_ok(const ConvGeom& g) {
+// input patch of one TH x TW tile: extent of the taps' offsets, patch size, dynamic LDS of the launch
+struct ThinPatch {
+  int dmin_y, dmin_x, PH, PW;
+  size_t smem;
+};
+constexpr int kThinPatchMax = 900;            // pp / PW by multiplication (ThinArgs::inv_PW) is exact below this
+constexpr size_t kThinLdsMax = 160 * 1024;
+
+static ThinPatch thin_patch(const ConvGeom& g, bool wgrad) {
+  const int TH = 8, TW = g.gC == 32 ? 32 : 16;
+  int dmin_y = 1 << 20, dmax_y = -(1 << 20), dmin_x = 1 << 20, dmax_x = -(1 << 20);
+  for (int c = 0; c < g.ncls; ++c)
+    for (int t = 0; t < g.ntaps[c]; ++t) {
+      const Tap& tp = g.taps[c][t];
+      dmin_y = tp.dy < dmin_y ? tp.dy : dmin_y; dmax_y = tp.dy > dmax_y ? tp.dy : dmax_y;
+      dmin_x = tp.dx < dmin_x ? tp.dx : dmin_x; dmax_x = tp.dx > dmax_x ? tp.dx : dmax_x;
+    }
+  ThinPatch p{};
+  p.dmin_y = dmin_y; p.dmin_x = dmin_x;
+  p.PH = (TH - 1) * g.is + (dmax_y - dmin_y) + 1;
+  p.PW = (TW - 1) * g.is + (dmax_x - dmin_x) + 1;
+  const int LDP = g.gC + 4;
+  p.smem = (size_t)p.PH * p.PW * LDP * 4 + (wgrad ? (size_t)TH * TW * 16 : 0);
+  const size_t merge = wgrad ? (size_t)4 * (max_taps(g) <= 4 ? 4 : 9) * 4 * 3 * (g.gC / 4) * 4 : 0;
+  if (merge > p.smem) p.smem = merge;
+  return p;
+}
+
+// everything launch_thin needs of a geometry, so that the plan, ctvae_conv_input_transform_supported and launch_wgrad send a
+// shape here only if the launch will take it (a stride-2 conv's patch is (TH-1)*2 + k rows: 32 -> 3 at stride 2 is past the
+// patch limit, 64 -> 3 k4 s2 past the LDS) -- the others fall back to the tile kernels
+static bool thin_shape_ok(const ConvGeom& g, bool wgrad) {
   if (!packed_weights(g) || g.wT != 0 || g.sC != 3) return false;
   if (!(g.gC == 32 || g.gC == 64)) return false;
   const int TH = 8, TW = g.gC == 32 ? 32 : 16;
   if (g.Qh % TH != 0 || g.Qw % TW != 0) return false;
-  return max_taps(g) <= 9;
+  if (max_taps(g) < 1 || max_taps(g) > 9) return false;
+  const ThinPatch p = thin_patch(g, wgrad);
+  return p.PH * p.PW < kThinPatchMax && p.smem <= kThinLdsMax;
 }
 
-bool thin_forward_supported(const ConvGeom& g) { return thin_shape_ok(g); }
-bool thin_wgrad_supported(const ConvGeom& g) { return thin_shape_ok(g); }
+bool thin_forward_supported(const ConvGeom& g) { return thin_shape_ok(g, false); }
+bool thin_wgrad_supported(const ConvGeom& g) { return thin_shape_ok(g, true); }
 int thin_bn_parts(const ConvGeom&) { return 0; }
 
 constexpr int kThinWgs = 768;   // persistent workgroups per class (wgrad partial slabs): 3 per CU hide the LDS/VALU latency
@@ -254,17 +287,10 @@ template <bool WGRAD>
 static int launch_thin(ThinArgs& a, int nwg, hipStream_t st, const char* pname) {
   const ConvGeom& g = a.g;
   const int TH = 8, TW = g.gC == 32 ? 32 : 16;
-  int dmin_y = 1 << 20, dmax_y = -(1 << 20), dmin_x = 1 << 20, dmax_x = -(1 << 20);
-  for (int c = 0; c < g.ncls; ++c)
-    for (int t = 0; t < g.ntaps[c]; ++t) {
-      const Tap& tp = g.taps[c][t];
-      dmin_y = tp.dy < dmin_y ? tp.dy : dmin_y; dmax_y = tp.dy > dmax_y ? tp.dy : dmax_y;
-      dmin_x = tp.dx < dmin_x ? tp.dx : dmin_x; dmax_x = tp.dx > dmax_x ? tp.dx : dmax_x;
-    }
-  a.dmin_y = dmin_y; a.dmin_x = dmin_x;
-  a.PH = (TH - 1) * g.is + (dmax_y - dmin_y) + 1;
-  a.PW = (TW - 1) * g.is + (dmax_x - dmin_x) + 1;
-  if (a.PH * a.PW >= 900) return kErrBadArg;
+  if (!thin_shape_ok(g, WGRAD)) return kErrBadArg;
+  const ThinPatch tp_ = thin_patch(g, WGRAD);
+  a.dmin_y = tp_.dmin_y; a.dmin_x = tp_.dmin_x;
+  a.PH = tp_.PH; a.PW = tp_.PW;
   a.inv_PW = (65536u + a.PW - 1) / a.PW;
   a.tiles_y = g.Qh / TH; a.tiles_x = g.Qw / TW;
   a.ntiles = g.B * a.tiles_y * a.tiles_x;
@@ -272,11 +298,7 @@ static int launch_thin(ThinArgs& a, int nwg, hipStream_t st, const char* pname) 
   for (int c = 0; c < g.ncls; ++c) taps += g.ntaps[c];
   a.rows_total = taps * g.gC;
   const int T = max_taps(g);
-  const int LDP = g.gC + 4;
-  size_t smem = (size_t)a.PH * a.PW * LDP * 4 + (WGRAD ? (size_t)TH * TW * 16 : 0);
-  const size_t merge = WGRAD ? (size_t)4 * (T <= 4 ? 4 : 9) * 4 * 3 * (g.gC / 4) * 4 : 0;
-  if (merge > smem) smem = merge;
-  if (smem > 160 * 1024) return kErrBadArg;
+  const size_t smem = tp_.smem;
   dim3 grid(nwg < a.ntiles ? nwg : a.ntiles, g.ncls), block(256);
   const double macs = (double)g.B * g.Qh * g.Qw * g.sC * g.gC * taps;
   const double bytes = 4.0 * ((double)g.B * g.gH * g.gW * g.gC + (double)g.B * g.sH * g.sW * g.sC);

@@ -7,6 +7,7 @@ coarser check:
   vector quantiser                      tests/test_vq_ops_gpu.py            (tests/vq_checks.py)
   causal-transition kernels             tests/test_ct_ops_gpu.py            (tests/ct_ops_checks.py)
   BatchNorm                             tests/test_bn_ops_gpu.py            (tests/bn_checks.py)
+  weight gradients (ctvae_conv_wgrad)   tests/test_wgrad_ops_gpu.py         (tests/wgrad_checks.py)
   loss.hip, reparam_* / gauss_latent_* / act_* of pointwise.hip, ladder.hip, tcvae.hip, vamp.hip, swd.hip, gamma.hip,
   dip.hip, catlatent.hip, mmd.hip, iwloss.hip, ssim.hip
                                         tests/test_loss_ops_gpu.py          (tests/loss_checks.py)
@@ -64,6 +65,10 @@ CASES = [
     (False, 3, 32, 48, 3, 2, 1, 0, 2),     # encoder.0-like with a 24 x 24 output -> masked tap-GEMM
     (True, 32, 32, 12, 3, 2, 1, 1, 2),     # final_layer.0-like with H % 8 != 0 -> tap-GEMM classes
     (True, 32, 32, 64, 3, 2, 1, 1, 1),     # upconv.hip with 8 x 2 tiles, B = 1
+    # 3-channel outputs at tile-aligned sizes that the thin kernel cannot take (stride-2 patch past its limits, 16 taps): tap-GEMM
+    (False, 32, 3, 64, 3, 2, 1, 0, 2),     # patch 17 x 65 >= 900 pixels
+    (False, 32, 3, 64, 4, 2, 1, 0, 2),
+    (False, 64, 3, 32, 4, 2, 1, 0, 2),     # patch 18 x 34 x 68 floats > 160 KB
 ]
 
 
