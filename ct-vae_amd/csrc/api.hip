@@ -290,6 +290,9 @@ int ctvae_conv_forward(int kind, const float* x, const float* w, const float* bi
                        size_t ws_bytes, void* stream) {
   if (!x || !w || !y || !conv_kind_ok(kind)) return kErrBadArg;
   if ((in_scale != nullptr) != (in_shift != nullptr)) return kErrBadArg;
+  // the transform on load exists where the header says so and nowhere else: a shape whose weight gradient (or whose Winograd
+  // forward) cannot apply it is refused here, not run by whichever kernel happens to take the operand
+  if (in_scale != nullptr && !ctvae_conv_input_transform_supported(kind, B, H, W, Ci, Co, k, stride, pad, out_pad)) return kErrBadArg;
   ConvGeom g;
   if (conv_geom(g, kind, 0, B, H, W, Ci, Co, k, stride, pad, out_pad)) return kErrBadArg;
   if ((wino_dgrad_filters_out != nullptr || wino_fwd_filters != nullptr) &&
@@ -776,6 +779,9 @@ int ctvae_conv_forward_lazy_slices(int kind, int B, int H, int W, int Ci, int Co
 int ctvae_conv_forward_lazy(int kind, const float* x, const float* w, float* y_slices, int B, int H, int W, int Ci, int Co, int k,
                             int stride, int pad, int out_pad, float* ws, size_t ws_bytes, void* stream) {
   if (!x || !w || !y_slices || !ws || !conv_kind_ok(kind)) return kErrBadArg;
+  // only the split tile kernel writes slices; every other launch (unsplit, thin, dedicated, Winograd) would store through the
+  // null output pointer handed down below, so a shape the query answers with 0 is refused before anything is launched
+  if (ctvae_conv_forward_lazy_slices(kind, B, H, W, Ci, Co, k, stride, pad, out_pad, ws_bytes) <= 1) return kErrBadArg;
   ConvGeom g;
   if (conv_geom(g, kind, 0, B, H, W, Ci, Co, k, stride, pad, out_pad)) return kErrBadArg;
   SplitKRaw raw{y_slices, 0, 1};

@@ -83,6 +83,10 @@ struct WinoArgs {
 // W packed [9][wCi][wCo].  Effective filter g[ky][kx] (k = gathered channel, n = produced channel) =
 //   wT == 0: W[tap[ky][kx]][k][n]     wT == 1: W[tap[ky][kx]][n][k]
 // Ut[f = 4i+j][k/8][n][k%8] = (G g G^T)[i][j].  thread = (n fastest, k).
+// The two middle rows of G add the outer taps first, (g0 + g2) +- g1: float32 addition commutes, so the transform of the mirrored
+// filter (the data gradient's) is the forward transform with rows / columns 0 <-> 3 swapped BIT FOR BIT, and a data gradient fed
+// the filters wino_weight2_kernel derived that way equals one that transforms its own (summed left to right, g0 + g1 + g2
+// against g2 + g1 + g0, the two differed in the last bit).
 struct WTaps { int t[9]; };
 
 __global__ __launch_bounds__(256) void wino_weight_kernel(const float* __restrict__ Wp, float* __restrict__ Ut, int K, int N,
@@ -102,15 +106,15 @@ __global__ __launch_bounds__(256) void wino_weight_kernel(const float* __restric
 #pragma unroll
   for (int j = 0; j < 3; ++j) {
     t[0][j] = g[0][j];
-    t[1][j] = 0.5f * (g[0][j] + g[1][j] + g[2][j]);
-    t[2][j] = 0.5f * (g[0][j] - g[1][j] + g[2][j]);
+    t[1][j] = 0.5f * ((g[0][j] + g[2][j]) + g[1][j]);   // outer taps first: the same bits for a mirrored filter (see below)
+    t[2][j] = 0.5f * ((g[0][j] + g[2][j]) - g[1][j]);
     t[3][j] = g[2][j];
   }
   float* dst = Ut + (((long)(k >> 3)) * N + n) * 8 + (k & 7);
   const long fs = (long)(K >> 3) * N * 8;
 #pragma unroll
   for (int i = 0; i < 4; ++i) {
-    const float u0 = t[i][0], u1 = 0.5f * (t[i][0] + t[i][1] + t[i][2]), u2 = 0.5f * (t[i][0] - t[i][1] + t[i][2]), u3 = t[i][2];
+    const float u0 = t[i][0], u1 = 0.5f * ((t[i][0] + t[i][2]) + t[i][1]), u2 = 0.5f * ((t[i][0] + t[i][2]) - t[i][1]), u3 = t[i][2];
     dst[(long)(4 * i + 0) * fs] = u0;
     dst[(long)(4 * i + 1) * fs] = u1;
     dst[(long)(4 * i + 2) * fs] = u2;
@@ -141,16 +145,16 @@ __device__ __forceinline__ void wino_weight2_body(const float* __restrict__ Wp, 
 #pragma unroll
       for (int j = 0; j < 3; ++j) {
         t[0][j] = g[0][j];
-        t[1][j] = 0.5f * (g[0][j] + g[1][j] + g[2][j]);
-        t[2][j] = 0.5f * (g[0][j] - g[1][j] + g[2][j]);
+        t[1][j] = 0.5f * ((g[0][j] + g[2][j]) + g[1][j]);
+        t[2][j] = 0.5f * ((g[0][j] + g[2][j]) - g[1][j]);
         t[3][j] = g[2][j];
       }
       float* dst = sW2 + ci_l * W2_LD + co_l;
 #pragma unroll
       for (int i = 0; i < 4; ++i) {
         dst[(4 * i + 0) * 32 * W2_LD] = t[i][0];
-        dst[(4 * i + 1) * 32 * W2_LD] = 0.5f * (t[i][0] + t[i][1] + t[i][2]);
-        dst[(4 * i + 2) * 32 * W2_LD] = 0.5f * (t[i][0] - t[i][1] + t[i][2]);
+        dst[(4 * i + 1) * 32 * W2_LD] = 0.5f * ((t[i][0] + t[i][2]) + t[i][1]);
+        dst[(4 * i + 2) * 32 * W2_LD] = 0.5f * ((t[i][0] + t[i][2]) - t[i][1]);
         dst[(4 * i + 3) * 32 * W2_LD] = t[i][2];
       }
     }

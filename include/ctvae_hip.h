@@ -44,6 +44,9 @@ size_t ctvae_workspace_bytes(void); /* scratch size that is sufficient for every
  * Conv2d:          vanilla_vae.py:28-29,73-74; mcq_vae.py:170-171,178-179,189-190,205-209; vq_vae.py:63-67
  * ConvTranspose2d: vanilla_vae.py:50-55,65-70; mcq_vae.py:223-236        Linear: vanilla_vae.py:36-37,43
  * x [B,H,W,Ci], y [B,Ho,Wo,Co]; bias/add may be NULL (add has y's layout: ResidualLayer skip, vq_vae.py:69-70).
+ * add is NOT taken on the thin shapes (3 output channels, 32 or 64 input channels, output a multiple of 8 x 32 resp. 8 x 16
+ * pixels per parity class -- the image-side convs): kErrBadArg there, nothing launched.  The dedicated kernels of the other
+ * image-side shapes (3 -> 32 k3 s2, 32 -> 32 transposed k3 s2) hand a call with add, or with tanh, to the general tile kernels.
  * ws: scratch for the split-K partial sums of small-grid layers (may be NULL: no split-K).
  * in_scale/in_shift [Ci] (both or neither; NULL = plain x): the layer reads x' = act_in(x*scale[c] + shift[c]) instead
  * of x, i.e. the BatchNorm2d + LeakyReLU in front of it (vanilla_vae.py:71-74) is applied while loading and its
@@ -100,6 +103,7 @@ int ctvae_conv_bn_act_forward(int kind, const float* x, const float* w, const fl
 
 /* dx = (dgrad(dy, w) + add) * act'(mask)      (autograd of the ops above)
  * add / mask (saved post-activation output of the PREVIOUS layer, layout of dx) may be NULL.
+ * Stride 2, CTVAE_CONV: H and W must be even (dx is written per output-parity class); an odd size is kErrBadArg, nothing launched.
  * wino_filters: NULL, or what ctvae_conv_forward left in wino_dgrad_filters_out for these weights. */
 int ctvae_conv_dgrad(int kind, const float* dy, const float* w, const float* add, const float* mask, int mask_act,
                      float* dx, int B, int H, int W, int Ci, int Co, int k, int stride, int pad, int out_pad,
@@ -394,7 +398,8 @@ int ctvae_gauss_latent_backward(const float* g_mu, const float* g_logvar, const 
  * g_z_slices > 0: g_z is that many slices [S][B][L] of decoder_input's data gradient (ctvae_conv_backward_lazy, pixel_major).
  * ctvae_conv_forward_lazy_slices / ctvae_conv_forward_lazy: the number of K slices a forward conv of this geometry would run
  * (0: not split / not the general tile kernel) and the launch that leaves them, without bias or activation, in
- * y_slices [S][B*Ho*Wo][Co].  ctvae_splitk_permute: out[b][c][p] = sum_s slices[s][(b*P+p)*C+c] -- the slice sum of an NHWC
+ * y_slices [S][B*Ho*Wo][Co]; where _slices answers 0 there is nothing to write and ctvae_conv_forward_lazy returns kErrBadArg before
+ * any launch.  ctvae_splitk_permute: out[b][c][p] = sum_s slices[s][(b*P+p)*C+c] -- the slice sum of an NHWC
  * data gradient and the NHWC -> NCHW change behind it (the .view(-1,512,2,2) of vanilla_vae.py:102, backward) in one launch. */
 int ctvae_conv_forward_lazy_slices(int kind, int B, int H, int W, int Ci, int Co, int k, int stride, int pad, int out_pad,
                                    size_t ws_bytes);

@@ -8,6 +8,8 @@ coarser check:
   causal-transition kernels             tests/test_ct_ops_gpu.py            (tests/ct_ops_checks.py)
   BatchNorm                             tests/test_bn_ops_gpu.py            (tests/bn_checks.py)
   weight gradients (ctvae_conv_wgrad)   tests/test_wgrad_ops_gpu.py         (tests/wgrad_checks.py)
+  conv forward and data gradient (ctvae_conv_forward / _dgrad / _forward_lazy, ctvae_linear_pixmajor_forward)
+                                        tests/test_conv_ops_gpu.py          (tests/conv_checks.py)
   loss.hip, reparam_* / gauss_latent_* / act_* of pointwise.hip, ladder.hip, tcvae.hip, vamp.hip, swd.hip, gamma.hip,
   dip.hip, catlatent.hip, mmd.hip, iwloss.hip, ssim.hip
                                         tests/test_loss_ops_gpu.py          (tests/loss_checks.py)
