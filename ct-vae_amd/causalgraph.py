@@ -14,7 +14,7 @@ are accumulated PER GROUP -- group 0: no intervention (base mode), group 1 + a: 
 * ``collect_graphs`` -- the base- and action-mode batches of an iterable through a model; ``summarize`` -- the result as a
   JSON-ready dict per group.
 
-Every model call runs under ``metrics._eval_mode`` and ``experiment.seeded_torch_rng`` (rollout.py).  There is no CPU path.
+Every model call runs under ``evalrun.eval_mode`` and ``evalrun.seeded_torch_rng`` (rollout.py).  There is no CPU path.
 """
 from typing import Iterable, Optional, Sequence
 
@@ -22,8 +22,7 @@ import numpy as np
 import torch
 
 from . import imagegrid, native
-from .experiment import seeded_torch_rng
-from .metrics import _eval_mode
+from .evalrun import batch_mode, eval_mode, seeded_torch_rng, unpack_batch
 from .rollout import _need_ct, _need_gpu, factor_names
 
 # (index, (R, G, B)): black - purple - red - orange - white.  No channel ever falls, and in every segment one channel climbs by at
@@ -224,14 +223,10 @@ def collect_graphs(model, batches: Iterable, seed: int = 0, threshold: float = 0
     ct = model.ct_layer
     prev, ct.graph_observer = ct.graph_observer, stats.observe
     try:
-        with _eval_mode(model), seeded_torch_rng(seed, dev):
+        with eval_mode(model), seeded_torch_rng(seed, dev):
             for batch in batches:
-                x, labels, *rest = batch
-                opts = rest[0] if rest and isinstance(rest[0], dict) else {}
-                mode = opts.get("mode", "base")
-                if isinstance(mode, (list, tuple)):
-                    mode = mode[0] if len(mode) else None
-                if mode not in ("base", "action"):
+                x, labels, opts = unpack_batch(batch)
+                if batch_mode(opts, "base") not in ("base", "action"):
                     continue
                 model(_need_gpu(x, "collect_graphs"), labels=labels, **opts)
     finally:

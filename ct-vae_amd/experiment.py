@@ -163,15 +163,15 @@ import time
 
 import torch
 
-from . import imagegrid
+from . import causalgraph, imagegrid
 from . import kernels as K
 from .ddp import GradBucketAllReduce
+from .evalrun import eval_mode, seeded_torch_rng, unpack_batch
 from .klcontrol import KLControl, kl_settings, needs_served_model, serves as kl_serves
 from .latentprior import (PRIOR_DIR, CodeBuffer, GaussianMixturePrior, draw_codes, needs_supported_model, prior_setting,
                           prior_supported)
 from .latentstats import (LATENT_DIR, LatentStats, has_gaussian_posterior, latent_stats_setting, needs_gaussian_posterior,
                           record as latent_record, write_files as write_latent_files)
-from .metrics import _eval_mode as eval_mode
 from .reconstats import (RECON_DIR, ReconStats, recon_settings, record as recon_record, refuses_model as recon_refuses_model,
                          summarize as recon_summarize, write_files as write_recon_files)
 from .optim import (CodebookEMA, CodebookUsage, ExponentialLR, FlatAdam, GradientTracker, WeightEMA, absent_grad_setting,
@@ -274,24 +274,6 @@ class _GraphedTrainStep:
         return losses
 
 
-@contextlib.contextmanager
-def seeded_torch_rng(seed: int, device):
-    """torch's CPU generator and ``device``'s generator seeded with ``seed`` inside; both states come back afterwards."""
-    cuda = device is not None and torch.device(device).type == "cuda"
-    cpu_state = torch.get_rng_state()
-    dev_state = torch.cuda.get_rng_state(device) if cuda else None
-    try:
-        torch.default_generator.manual_seed(seed)
-        if cuda:
-            with torch.cuda.device(device):
-                torch.cuda.manual_seed(seed)
-        yield
-    finally:
-        torch.set_rng_state(cpu_state)
-        if cuda:
-            torch.cuda.set_rng_state(dev_state, device)
-
-
 class VAEXperiment:
 
     SAMPLE_DIRS = ("Inputs", "Reconstructions", "Samples")
@@ -388,13 +370,8 @@ class VAEXperiment:
         return self.model(input, **kwargs)
 
     # -- steps (experiment.py:44-74) ---------------------------------------------------------------------
-    def _unpack(self, batch):
-        real_img, labels, *args = batch
-        kwargs = {} if len(args) < 1 or type(args[0]) != dict else args[0]
-        return real_img, labels, kwargs
-
     def training_step(self, batch, batch_idx, optimizer_idx=0):
-        real_img, labels, kwargs = self._unpack(batch)
+        real_img, labels, kwargs = unpack_batch(batch)
         self.curr_device = real_img.device
         results = self.forward(real_img, labels=labels, **kwargs)
         self.write_kl_weight()
@@ -418,7 +395,7 @@ class VAEXperiment:
         return {"M_N": self.kl.tensor, "free_bits": self.kl.floor}
 
     def validation_step(self, batch, batch_idx, optimizer_idx=0):
-        real_img, labels, kwargs = self._unpack(batch)
+        real_img, labels, kwargs = unpack_batch(batch)
         self.curr_device = real_img.device
         with torch.no_grad():
             results = self.forward(real_img, labels=labels, **kwargs)
@@ -466,7 +443,7 @@ class VAEXperiment:
     def sample_images(self, test_batch, epoch: int) -> list:
         """experiment.py:114-150 on one test batch ``(input, labels, *options)``: the input, ``model.generate`` and
         ``model.sample`` grids of this epoch under ``sample_dir`` (module docstring).  Returns the paths written."""
-        test_input, test_label, kwargs = self._unpack(test_batch)
+        test_input, test_label, kwargs = unpack_batch(test_batch)
         dev = next(self.model.parameters()).device
         test_input = test_input.to(dev)
         if torch.is_tensor(test_label):
@@ -501,7 +478,6 @@ class VAEXperiment:
         """What ``val_graphs`` leaves of one validation epoch (module docstring): the two sheets under ``sample_dir`` (when there
         is one, and only for groups that had rows) and the ``val_graph_edges_<group>`` scalars, which also go to the JSONL
         log.  One device -> host copy."""
-        from . import causalgraph
         res = stats.result()
         summary = causalgraph.summarize(res)
         rec = {f"val_graph_edges_{k}": v["edges"] for k, v in summary.items() if v["edges"] is not None}
@@ -972,7 +948,6 @@ class VAEXperiment:
     # -- validation reports: contexts armed around the validation steps, each yielding what writes its part of the epoch record --
     @contextlib.contextmanager
     def _graph_report(self, epoch):
-        from . import causalgraph
         ct = self.model.ct_layer
         stats = causalgraph.GraphStats(ct.action_dim + 1, causalgraph.model_nodes(self.model), next(self.model.parameters()).device)
         ct.graph_observer = stats.observe
@@ -1062,7 +1037,7 @@ class VAEXperiment:
             if first is not None:
                 self.sample_images(first, epoch)
                 if self.val_prior is not None:
-                    self.sample_mixture_images(min(32, self._unpack(first)[0].size(0)), epoch)
+                    self.sample_mixture_images(min(32, unpack_batch(first)[0].size(0)), epoch)
         return rec
 
     def fit(self, train_batches, val_batches=None, max_epochs=1, on_epoch_end=None, start_epoch=0, test_batches=None):
@@ -1096,7 +1071,7 @@ class VAEXperiment:
         """The training batches of one epoch of ``fit()``: ``stream`` yields (batch, ends_window); returns the images seen."""
         n = 0
         for i, (batch, ends) in enumerate(stream):
-            real_img, _labels, kwargs = self._unpack(batch)
+            real_img, _labels, kwargs = unpack_batch(batch)
             # graph_safe = False: the model's step depends on host state that changes per call (e.g. BetaVAE type 'B':
             # the capacity C follows the loss-call counter), so a captured step would freeze it
             if getattr(self.model, 'uses_labels', False) and torch.is_tensor(_labels):

@@ -1,9 +1,9 @@
 """Fit a Gaussian-mixture latent prior to a trained Gaussian model and sample from it:
 ``python -m ctvae_amd.fit_prior -c configs/vae.yaml --checkpoint <path>``.
 
-Builds the model of ``model_params`` and loads a checkpoint the way ``latent_stats.py`` does, encodes the training split
-(``--rows N`` caps the rows; default all), fits ``latentprior.GaussianMixturePrior`` (``--components 10``, ``--covariance full|diag``,
-``--max-iter 100``, ``--tol 1e-3``, ``--reg-covar 1e-6``; ``--codes mean`` fits on the posterior means, ``--codes sample`` on
+Builds the model of ``model_params`` and loads a checkpoint as every checkpoint command does (``tool.py``), encodes the
+training split (``--rows N`` caps the rows; default all), fits ``latentprior.GaussianMixturePrior`` (``--components 10``,
+``--covariance full|diag``, ``--max-iter 100``, ``--tol 1e-3``, ``--reg-covar 1e-6``; ``--codes mean`` fits on the posterior means, ``--codes sample`` on
 ``mu + exp(0.5 log_var) * eps`` with eps from a generator of its own) and writes under ``--out`` (default
 ``<save_dir>/<name>/fit_prior``):
 
@@ -17,30 +17,33 @@ Builds the model of ``model_params`` and loads a checkpoint the way ``latent_sta
 * ``samples_mixture.png``   the same eps through the mixture, ``mu_k + L_k eps``
 
 Models other than ``latentprior.PRIOR_MODELS`` are refused by name before a device is touched.  Seeded with
-``exp_params.manual_seed``.  ``--ema`` loads the checkpoint's averaged weights (``ema_state_dict``) in place of ``state_dict``; a
-checkpoint without them is refused.  Bad input ends with a SystemExit that says why.
+``exp_params.manual_seed``; the model runs in eval mode and the torch generators come back as they were.  ``--ema`` loads the
+checkpoint's averaged weights (``ema_state_dict``) in place of ``state_dict``; a checkpoint without them is refused.  Bad input
+ends with a SystemExit that says why.
 """
 import argparse
 import json
 import os
 
 import torch
-import yaml
+
+from . import imagegrid, latentprior, tool
+from .evalrun import eval_mode, seeded_torch_rng, unpack_batch
 
 FILES = ("latent_prior.npz", "latent_prior.json", "samples_standard.png", "samples_mixture.png")
+_fail = tool.fail("fit_prior")
 
 
-def _fail(msg: str):
-    raise SystemExit(f"fit_prior: {msg}")
+def _accept(cls, name):
+    if cls is None or not latentprior.prior_supported(cls):
+        return f"model_params.name is {name!r}: " + latentprior.needs_supported_model(cls, name=repr(name))
 
 
 def _encode(model, batches, codes, generator, cap):
     """The codes of ``batches`` [rows, latent_dim] on the device, at most ``cap`` rows (None: all)."""
-    from . import latentprior
     buf = latentprior.CodeBuffer(model.latent_dim, next(model.parameters()).device)
     for batch in batches:
-        x, labels, *rest = batch
-        opts = rest[0] if rest and isinstance(rest[0], dict) else {}
+        x, labels, opts = unpack_batch(batch, model)           # the label column: a no-op, no model of PRIOR_MODELS uses labels
         z = latentprior.draw_codes(*model.gaussian_posterior(model(x, labels=labels, **opts)), codes, generator)
         buf.append(z if cap is None else z[:cap - buf.rows])
         if cap is not None and buf.rows >= cap:
@@ -50,10 +53,7 @@ def _encode(model, batches, codes, generator, cap):
 
 def main(argv=None):
     ap = argparse.ArgumentParser(description="fit a Gaussian-mixture prior to the latent codes of a trained Gaussian model; sample from it")
-    ap.add_argument('--config', '-c', dest="filename", metavar='FILE', default='configs/vae.yaml')
-    ap.add_argument('--checkpoint', default=None, help="default: trainer_params.resume_from_checkpoint")
-    ap.add_argument('--out', default=None, help="default: <save_dir>/<name>/fit_prior")
-    ap.add_argument('--ema', action='store_true', help="load the checkpoint's averaged weights (ema_state_dict) in place of state_dict")
+    tool.add_arguments(ap, "fit_prior", 'configs/vae.yaml')
     ap.add_argument('--components', type=int, default=10, metavar='K', help="mixture components, 1..64")
     ap.add_argument('--covariance', default="full", help="full or diag")
     ap.add_argument('--max-iter', type=int, default=100)
@@ -63,16 +63,7 @@ def main(argv=None):
     ap.add_argument('--rows', type=int, default=None, metavar='N', help="a cap on the training rows encoded (default: all)")
     ap.add_argument('--samples', type=int, default=32, help="images per sample sheet")
     args = ap.parse_args(argv)
-    with open(args.filename) as f:
-        config = yaml.safe_load(f)
-
-    from . import latentprior
-    from .models import vae_models
-    mp = dict(config['model_params'])
-    cls = vae_models.get(mp.get('name'))
-    if cls is None or not latentprior.prior_supported(cls):
-        _fail(f"model_params.name is {mp.get('name')!r}: " + latentprior.needs_supported_model(cls, name=repr(mp.get('name'))))
-    dp, tp, lp = config.get('data_params', {}), config.get('trainer_params', {}) or {}, config.get('logging_params', {}) or {}
+    configured = tool.configure(args, "fit_prior", _accept)
     try:
         latentprior.check_options(args.components, args.covariance, args.max_iter, args.tol, args.reg_covar, args.codes, what="--")
     except ValueError as e:
@@ -81,37 +72,12 @@ def main(argv=None):
         _fail(f"--rows must be at least 2, got {args.rows}")
     if args.samples < 1:
         _fail(f"--samples must be at least 1, got {args.samples}")
-    ckpt_path = args.checkpoint or tp.get('resume_from_checkpoint')
-    if not ckpt_path:
-        _fail("no checkpoint: give --checkpoint or set trainer_params.resume_from_checkpoint")
-    if not os.path.isfile(ckpt_path):
-        _fail(f"checkpoint {ckpt_path} does not exist")
-    ckpt = None
-    if args.ema:          # (asked for by name: a checkpoint without the average is refused before anything is built)
-        ckpt = torch.load(ckpt_path, map_location="cpu", weights_only=True)
-        if 'ema_state_dict' not in ckpt:
-            _fail(f"--ema: checkpoint {ckpt_path} holds no ema_state_dict (it was written without exp_params.ema_decay)")
-    if not torch.cuda.is_available():
-        _fail("ctvae_amd runs on MI355X GPUs only: the hot path has no CPU fallback")
-
-    from . import imagegrid
-    from .experiment import seeded_torch_rng
-    from .metrics import _eval_mode
-    from .run import HbmData, SyntheticData
-    dev = torch.device("cuda", torch.cuda.current_device())
-    seed = int(config.get('exp_params', {}).get('manual_seed', 0) or 0)
-    torch.manual_seed(seed)
-    model = cls(**mp).to(dev)
-    if ckpt is None:
-        ckpt = torch.load(ckpt_path, map_location="cpu", weights_only=True)
-    weights = ckpt['ema_state_dict' if args.ema else 'state_dict']
-    model.load_state_dict({k[6:]: v for k, v in weights.items() if k.startswith("model.")}, strict=True)
-    data = HbmData(dp, mp, dev, 0, 1, seed) if dp.get('hbm_images') else SyntheticData(dp, mp, dev, 0, 1, seed=seed)
+    model, data, dev, seed, out_dir = tool.load(args, "fit_prior", configured)
 
     gen = torch.Generator(device=dev)                  # what --codes sample and the sample sheets draw from: no other stream moves
     gen.manual_seed(seed)
     prior = latentprior.GaussianMixturePrior(model.latent_dim, args.components, args.covariance, args.reg_covar, dev)
-    with _eval_mode(model), seeded_torch_rng(seed, dev):
+    with eval_mode(model), seeded_torch_rng(seed, dev):
         train = _encode(model, data.train(), args.codes, gen, args.rows)
         try:
             fit = prior.fit(train, seed=seed, max_iter=args.max_iter, tol=args.tol)
@@ -129,7 +95,6 @@ def main(argv=None):
         eps = torch.randn(args.samples, model.latent_dim, generator=gen, device=dev)
         u = torch.rand(args.samples, generator=gen, device=dev)
         z, _ = prior.sample(args.samples, u=u, eps=eps)
-        out_dir = args.out or os.path.join(lp.get('save_dir', 'logs/'), lp.get('name', mp['name']), "fit_prior")
         os.makedirs(out_dir, exist_ok=True)
         imagegrid.save_image(model.decode(eps), os.path.join(out_dir, "samples_standard.png"), normalize=True, nrow=12)
         imagegrid.save_image(model.decode(z), os.path.join(out_dir, "samples_mixture.png"), normalize=True, nrow=12)

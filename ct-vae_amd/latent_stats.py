@@ -1,7 +1,7 @@
 """The latent usage of a trained Gaussian model: ``python -m ctvae_amd.latent_stats -c configs/vae.yaml --checkpoint <path>``.
 
-Builds the model of ``model_params`` and loads a checkpoint the way ``causal_graph.py`` does, runs the test split through it
-(``latentstats.LatentStats`` on the ``mu`` / ``log_var`` of every batch) and writes under ``--out`` (default
+Builds the model of ``model_params`` and loads a checkpoint as every checkpoint command does (``tool.py``), runs the test split
+through it (``latentstats.LatentStats`` on the ``mu`` / ``log_var`` of every batch) and writes under ``--out`` (default
 ``<save_dir>/<name>/latent_stats``):
 
 * ``latent_stats.json``  the scalars of ``latentstats.summarize`` (``kl_total``, ``active_units``, ``collapsed``, ``mean_abs_corr``,
@@ -14,46 +14,38 @@ Builds the model of ``model_params`` and loads a checkpoint the way ``causal_gra
   test image ``--image-index`` (default 0)
 
 The traversal needs a ``decode`` that takes [N, L] latents: the VanillaVAE family and BetaTCVAE.  For ConditionalVAE and JointVAE
-it is refused by name -- after the statistics, which do not need it, are written.  Seeded with ``exp_params.manual_seed``.  ``--ema``
-loads the checkpoint's averaged weights (``ema_state_dict``) in place of ``state_dict``; a checkpoint without them is refused.
-Bad input ends with a SystemExit that says why.
+it is refused by name -- after the statistics, which do not need it, are written.  Seeded with ``exp_params.manual_seed``; the
+model runs in eval mode and the torch generators come back as they were.  ``--ema`` loads the checkpoint's averaged weights
+(``ema_state_dict``) in place of ``state_dict``; a checkpoint without them is refused.  Bad input ends with a SystemExit that says
+why.
 """
 import argparse
 import json
 import os
 
 import numpy as np
-import torch
-import yaml
+
+from . import latentstats, tool
+from .evalrun import eval_mode, seeded_torch_rng, unpack_batch
 
 FILES = ("latent_stats.json", "latent_stats.npz", "latent_corr.png", "traversal.png")
+_fail = tool.fail("latent_stats")
 
 
-def _fail(msg: str):
-    raise SystemExit(f"latent_stats: {msg}")
+def _accept(cls, name):
+    if cls is None or not latentstats.has_gaussian_posterior(cls):
+        return f"model_params.name is {name!r}: " + latentstats.needs_gaussian_posterior(cls, name=repr(name))
 
 
 def main(argv=None):
     ap = argparse.ArgumentParser(description="per-dimension KL, active units, correlation and a traversal of a trained Gaussian model")
-    ap.add_argument('--config', '-c', dest="filename", metavar='FILE', default='configs/vae.yaml')
-    ap.add_argument('--checkpoint', default=None, help="default: trainer_params.resume_from_checkpoint")
-    ap.add_argument('--out', default=None, help="default: <save_dir>/<name>/latent_stats")
-    ap.add_argument('--ema', action='store_true', help="load the checkpoint's averaged weights (ema_state_dict) in place of state_dict")
+    tool.add_arguments(ap, "latent_stats", 'configs/vae.yaml')
     ap.add_argument('--traverse', type=int, default=10, metavar='K', help="rows of traversal.png: the K highest-KL dimensions (0: off)")
     ap.add_argument('--steps', type=int, default=11, metavar='S', help="columns of traversal.png")
     ap.add_argument('--span', type=float, default=3.0, help="the traversed dimension runs over linspace(-span, span, S)")
     ap.add_argument('--image-index', type=int, default=0, help="the test image whose posterior mean the traversal starts from")
     args = ap.parse_args(argv)
-    with open(args.filename) as f:
-        config = yaml.safe_load(f)
-
-    from . import latentstats
-    from .models import vae_models
-    mp = dict(config['model_params'])
-    cls = vae_models.get(mp.get('name'))
-    if cls is None or not latentstats.has_gaussian_posterior(cls):
-        _fail(f"model_params.name is {mp.get('name')!r}: " + latentstats.needs_gaussian_posterior(cls, name=repr(mp.get('name'))))
-    dp, tp, lp = config.get('data_params', {}), config.get('trainer_params', {}) or {}, config.get('logging_params', {}) or {}
+    configured = tool.configure(args, "latent_stats", _accept)
     if args.traverse < 0:
         _fail(f"--traverse must be at least 0, got {args.traverse}")
     if args.steps < 1:
@@ -62,41 +54,15 @@ def main(argv=None):
         _fail(f"--span must be a positive number, got {args.span}")
     if args.image_index < 0:
         _fail(f"--image-index must be at least 0, got {args.image_index}")
-    ckpt_path = args.checkpoint or tp.get('resume_from_checkpoint')
-    if not ckpt_path:
-        _fail("no checkpoint: give --checkpoint or set trainer_params.resume_from_checkpoint")
-    if not os.path.isfile(ckpt_path):
-        _fail(f"checkpoint {ckpt_path} does not exist")
-    ckpt = None
-    if args.ema:          # (asked for by name: a checkpoint without the average is refused before anything is built)
-        ckpt = torch.load(ckpt_path, map_location="cpu", weights_only=True)
-        if 'ema_state_dict' not in ckpt:
-            _fail(f"--ema: checkpoint {ckpt_path} holds no ema_state_dict (it was written without exp_params.ema_decay)")
-    if not torch.cuda.is_available():
-        _fail("ctvae_amd runs on MI355X GPUs only: the hot path has no CPU fallback")
-
-    from .experiment import seeded_torch_rng
-    from .metrics import _eval_mode
-    from .run import HbmData, SyntheticData
-    dev = torch.device("cuda", torch.cuda.current_device())
-    seed = int(config.get('exp_params', {}).get('manual_seed', 0) or 0)
-    torch.manual_seed(seed)
-    model = cls(**mp).to(dev)
-    if ckpt is None:
-        ckpt = torch.load(ckpt_path, map_location="cpu", weights_only=True)
-    weights = ckpt['ema_state_dict' if args.ema else 'state_dict']
-    model.load_state_dict({k[6:]: v for k, v in weights.items() if k.startswith("model.")}, strict=True)
-    data = HbmData(dp, mp, dev, 0, 1, seed) if dp.get('hbm_images') else SyntheticData(dp, mp, dev, 0, 1, seed=seed)
+    model, data, dev, seed, out_dir = tool.load(args, "latent_stats", configured)
+    mp = configured[2]
 
     stats = latentstats.LatentStats(model.latent_dim, dev)
     stats.zero()
     image, seen = None, 0
-    with _eval_mode(model), seeded_torch_rng(seed, dev):
+    with eval_mode(model), seeded_torch_rng(seed, dev):
         for batch in data.test():
-            x, labels, *rest = batch
-            opts = rest[0] if rest and isinstance(rest[0], dict) else {}
-            if getattr(model, 'uses_labels', False) and torch.is_tensor(labels) and labels.dim() == 1:
-                labels = labels.reshape(-1, 1)            # one label per image is one class column
+            x, labels, opts = unpack_batch(batch, model)
             stats.observe(*model.gaussian_posterior(model(x, labels=labels, **opts)))
             if image is None and seen <= args.image_index < seen + x.size(0):
                 image = x[args.image_index - seen].clone()
@@ -104,7 +70,6 @@ def main(argv=None):
     res = stats.result()
     if res["rows"] < 2:
         _fail(f"the test split has {res['rows']} rows: the statistics need at least two")
-    out_dir = args.out or os.path.join(lp.get('save_dir', 'logs/'), lp.get('name', mp['name']), "latent_stats")
     os.makedirs(out_dir, exist_ok=True)
 
     ranked = latentstats.rank_dims(res["kl"], len(res["kl"]))

@@ -20,6 +20,7 @@ import numpy as np
 import torch
 
 from . import kernels as K
+from .evalrun import npz_bytes
 
 PRIOR_DIR = "Priors"
 PRIOR_MODELS = ("VanillaVAE", "BetaVAE", "LogCoshVAE", "DIPVAE", "MSSIMVAE", "TwoStageVAE", "InfoVAE", "VampVAE", "BetaTCVAE")
@@ -356,7 +357,6 @@ class GaussianMixturePrior:
         self.rows, self.iterations, self.converged = int(one("rows")), int(one("iterations")), bool(one("converged"))
 
     def save(self, path) -> None:
-        from .causal_graph import npz_bytes
         with open(path, "wb") as f:
             f.write(npz_bytes(self.state_dict()))
 

@@ -18,7 +18,10 @@ There is no CPU path for the device parts.
 import numpy as np
 import torch
 
+from . import imagegrid
 from . import kernels as K
+from .causalgraph import save_heatmaps
+from .evalrun import eval_mode, npz_bytes, seeded_torch_rng
 
 ACTIVE_VAR = 0.01            # a unit is active when the variance of its posterior mean over the data exceeds it (Burda et al. 2016)
 COLLAPSED_KL = 0.01          # a dimension counts as collapsed below this mean KL, in nats
@@ -205,9 +208,6 @@ def save_traversal(model, x_row, dims, values, path) -> tuple:
     ``traversal_latents`` and the rows are decoded, at most ``DECODE_ROWS`` per ``decode`` call, into one sheet with a row per
     dimension (``imagegrid.save_image(normalize=True, nrow=len(values))``).  Eval mode and ``no_grad``: BatchNorm statistics and
     training flags stay as found, and so does every random stream.  Returns the sheet's (rows, columns)."""
-    from . import imagegrid
-    from .experiment import seeded_torch_rng
-    from .metrics import _eval_mode
     if not traversal_supported(model):
         raise TypeError(f"save_traversal needs a model whose decode takes [N, L] latents (the VanillaVAE family, BetaTCVAE), got "
                         f"{type(model).__name__}")
@@ -219,7 +219,7 @@ def save_traversal(model, x_row, dims, values, path) -> tuple:
     dims, values = list(dims), [float(v) for v in values]
     if not dims or not values:
         raise ValueError("save_traversal needs at least one dimension and one value")
-    with _eval_mode(model), seeded_torch_rng(0, x.device):
+    with eval_mode(model), seeded_torch_rng(0, x.device):
         mu = model.encode(x)[0].reshape(-1)
         z = traversal_latents(mu, dims, values)
         imgs = torch.cat([model.decode(z[i:i + DECODE_ROWS].contiguous()) for i in range(0, z.size(0), DECODE_ROWS)])
@@ -231,8 +231,6 @@ def save_traversal(model, x_row, dims, values, path) -> tuple:
 def write_files(result: dict, npz_path, png_path) -> None:
     """``summarize``'s arrays as an ``.npz`` (``kl``, ``mu_mean``, ``mu_var``, ``sigma2_mean``, ``cov``, ``rows``; bytes that
     depend on the arrays alone) and |corr| as a heat map over [0, 1].  Needs n >= 2 rows."""
-    from .causal_graph import npz_bytes
-    from .causalgraph import save_heatmaps
     arrays = {k: result[k] for k in ("kl", "mu_mean", "mu_var", "sigma2_mean", "cov")}
     arrays["rows"] = np.asarray([result["rows"]], dtype=np.int64)
     with open(npz_path, "wb") as f:

@@ -22,13 +22,13 @@ column, not by the position among the active columns (the accuracies are the sam
 refused by name.  The hot arithmetic runs in three HIP kernels (csrc/disent.hip); the top-2, the entropies, the vote table and
 the classifier stay on the host.  There is no CPU fallback: codes must be device tensors.
 """
-import contextlib
 from typing import Callable, List, Sequence
 
 import numpy as np
 import torch
 
 from . import native
+from .evalrun import eval_mode
 
 METRICS = {"MIG": "mig", "FactorVaeScore": "factor_vae", "": None}
 UNSUPPORTED = {"DCI": "it fits gradient-boosted trees (a CPU-library algorithm with no kernel here)",
@@ -250,23 +250,6 @@ def metric_factor_vae(dataset: FactorData, repr_func: Callable, plan: dict, batc
 _COMPUTE = {"MIG": metric_mig, "FactorVaeScore": metric_factor_vae}
 
 
-@contextlib.contextmanager
-def _eval_mode(model):
-    """eval() + no_grad() for the evaluation; the previous training flag of every module comes back afterwards."""
-    if model is None:
-        with torch.no_grad():
-            yield
-        return
-    was = [(m, m.training) for m in model.modules()]
-    model.eval()
-    try:
-        with torch.no_grad():
-            yield
-    finally:
-        for m, t in was:
-            m.training = t
-
-
 class Metric:
     """One metric over a ``FactorData`` (metrics/metric.py:17-46, with the reference's argument handling: MIG drops
     ``num_test``; FactorVaeScore turns it into ``num_eval`` and uses ``num_variance_estimate = 512``)."""
@@ -309,7 +292,7 @@ class Metric:
         if model is None:                      # exp.metric_func: the harness's model is the module behind it
             model = getattr(getattr(repr_func, "__self__", None), "model", None)
         plan = self.plan(seed)
-        with _eval_mode(model):
+        with eval_mode(model):
             return _COMPUTE[self.name](self.dataset, repr_func, plan, self.args["batch_size"])
 
 

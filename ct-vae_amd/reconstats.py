@@ -20,7 +20,9 @@ There is no CPU path for the device parts.
 import numpy as np
 import torch
 
+from . import imagegrid
 from . import kernels as K
+from .evalrun import npz_bytes
 
 RECON_DIR = "Recon"
 DEFAULT_RANGE = 1.0
@@ -200,8 +202,6 @@ def write_files(result: dict, npz_path, png_path=None) -> None:
     ``worst_rows`` as an ``.npz`` whose bytes depend on the arrays alone, and -- with ``png_path`` and at least one worst image --
     the worst targets (top row) over their reconstructions (bottom row), worst first, through ``imagegrid.save_image`` with the
     arguments ``sample_images`` uses and one column per image."""
-    from . import imagegrid
-    from .causal_graph import npz_bytes
     rec = result["records"]
     arrays = {name: np.ascontiguousarray(rec[:, i]) for i, name in enumerate(K.RECON_COLUMNS)}
     arrays["nonfinite"] = np.asarray(result["flags"], dtype=np.int32)

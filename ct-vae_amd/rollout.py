@@ -10,8 +10,8 @@ The model reports ``causal_acc`` / ``causal_nodir_acc`` only as batch means; the
 ``ActionHits`` over csrc/acteval.hip, which accumulates on the device with no host synchronisation per batch.  Action index
 ``i`` of ``A = 2 V`` means factor ``i % V``, direction ``+`` for ``i < V`` and ``-`` otherwise (cells 5-7).
 
-Every model call runs under ``metrics._eval_mode`` (eval + no_grad, training flags restored) and
-``experiment.seeded_torch_rng``: no BatchNorm statistic, no parameter epoch and no torch generator of the caller's run moves.
+Every model call runs under ``evalrun.eval_mode`` (eval + no_grad, training flags restored) and
+``evalrun.seeded_torch_rng``: no BatchNorm statistic, no parameter epoch and no torch generator of the caller's run moves.
 There is no CPU path: tensors must be on the GPU.
 """
 from typing import Iterable, List, Optional, Sequence
@@ -20,8 +20,7 @@ import numpy as np
 import torch
 
 from . import imagegrid, native
-from .experiment import seeded_torch_rng
-from .metrics import _eval_mode
+from .evalrun import batch_mode, eval_mode, seeded_torch_rng, unpack_batch
 from .models.ct_mcq_vae import CTMCQVAE
 
 
@@ -47,6 +46,21 @@ def factor_names(A: int, names: Optional[Sequence[str]] = None) -> List[str]:
     names = [str(n) for n in names]
     if len(names) != V:
         raise ValueError(f"{A} actions are {V} factors in two directions, but {len(names)} names were given: {names}")
+    return names
+
+
+def configured_factor_names(mp: dict, dp: dict, given: Optional[str] = None) -> Optional[List[str]]:
+    """The factor names a command hands ``factor_names``: ``given`` (its comma-separated ``--factor-names``), else
+    ``data_params.hbm_factor_names``, else None.  A ValueError names an odd ``model_params.action_dim`` or a wrong count."""
+    A = int(mp.get('action_dim', 0))
+    if A < 2 or A % 2:
+        raise ValueError(f"model_params.action_dim must be even and at least 2, got {mp.get('action_dim')!r}")
+    if given is not None:
+        names, src = [n.strip() for n in given.split(",")], "--factor-names"
+    else:
+        names, src = dp.get('hbm_factor_names'), "data_params.hbm_factor_names"
+    if names is not None and len(names) != A // 2:
+        raise ValueError(f"{src} has {len(names)} names, but action_dim {A} means {A // 2} factors")
     return names
 
 
@@ -129,7 +143,7 @@ def action_rollout(model, image: torch.Tensor, steps: int = 5, seed: int = 0) ->
     dev = image.device
     frames = [image.detach().float().expand(A, -1, -1, -1).contiguous()]
     eye = torch.eye(A, device=dev)
-    with _eval_mode(model), seeded_torch_rng(seed, dev):
+    with eval_mode(model), seeded_torch_rng(seed, dev):
         for _ in range(int(steps)):
             cur = frames[-1]
             frames.append(model(cur, labels=None, mode=["action"] * A, action=eye, input_y=cur)[0].detach())
@@ -160,7 +174,7 @@ def rollout_accuracy(model, x: torch.Tensor, steps: int = 1, names: Optional[Seq
     dev, B = x.device, x.size(0)
     cur = [x] * A
     hits = [ActionHits(A, dev) for _ in range(int(steps))]
-    with _eval_mode(model), seeded_torch_rng(seed, dev):
+    with eval_mode(model), seeded_torch_rng(seed, dev):
         for s in range(int(steps)):
             for a in range(A):
                 action = _one_hot_rows(a, B, A, dev)
@@ -180,14 +194,10 @@ def split_accuracy(model, batches: Iterable, names: Optional[Sequence[str]] = No
     if dev.type != "cuda":
         raise RuntimeError("split_accuracy runs on the GPU only: there is no CPU fallback")
     hits = ActionHits(A, dev)
-    with _eval_mode(model), seeded_torch_rng(seed, dev):
+    with eval_mode(model), seeded_torch_rng(seed, dev):
         for batch in batches:
-            x, labels, *rest = batch
-            opts = rest[0] if rest and isinstance(rest[0], dict) else {}
-            mode = opts.get("mode")
-            if isinstance(mode, (list, tuple)):
-                mode = mode[0] if len(mode) else None
-            if mode != "causal":
+            x, labels, opts = unpack_batch(batch)
+            if batch_mode(opts) != "causal":
                 continue
             out = model(_need_gpu(x, "split_accuracy"), labels=labels, **opts)
             hits.update(out[0], out[1])

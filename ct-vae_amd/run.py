@@ -207,6 +207,11 @@ class HbmData:
         return self._loader("test", self.p["val_batch_size"], True)
 
 
+def model_weights(state: dict) -> dict:
+    """A checkpoint's ``state_dict`` / ``ema_state_dict`` (keys ``model.<name>``, as ``on_epoch_end`` writes them) as the model's own."""
+    return {k[6:]: v for k, v in state.items() if k.startswith("model.")}
+
+
 def build_val_metric(config, data):
     """``exp_params.metrics`` -> a MetricSet over the whole store (the reference hands it ``_full_data``), sized as run.py:72-76;
     None without the key.  A metric that cannot run is a SystemExit with the reason."""
@@ -485,7 +490,7 @@ def main(argv=None):
             check_codebook_ema_checkpoint(ckpt, ckpt_path, cb_ema_decay, cb_ema_eps)
         if (kl_schedule is not None or kl_free_bits is not None) and not weights_only:
             check_kl_checkpoint(ckpt, ckpt_path, kl_schedule, kl_free_bits)
-        model.load_state_dict({k[6:]: v for k, v in ckpt['state_dict'].items() if k.startswith("model.")}, strict=not weights_only)
+        model.load_state_dict(model_weights(ckpt['state_dict']), strict=not weights_only)
     ddp = GradBucketAllReduce(model) if world > 1 else None
     log_dir = os.path.join(config['logging_params'].get('save_dir', 'logs/'), config['logging_params'].get('name', mp['name']))
     os.makedirs(os.path.join(log_dir, "checkpoints"), exist_ok=True)
@@ -523,7 +528,7 @@ def main(argv=None):
                              "set trainer_params.load_weights_only to start a new run from its weights")
         exp.load_state_dict(ckpt["trainer"])
         if exp.ema is not None:                                       # the average's buffer travels as weights
-            exp.load_ema_model_state_dict({k[6:]: v for k, v in ckpt['ema_state_dict'].items() if k.startswith("model.")})
+            exp.load_ema_model_state_dict(model_weights(ckpt['ema_state_dict']))
         start_epoch = int(ckpt["epoch"]) + 1
         if hasattr(data, "epoch"):
             data.epoch = start_epoch                                  # the shuffling order follows the epoch

@@ -234,8 +234,11 @@ def test_causal_graph_command_end_to_end(dev, tmp_path):
     path = tmp_path / "ct.yaml"
     path.write_text(yaml.safe_dump(cfg))
     runs = []
+    torch.manual_seed(123)
+    before = (torch.get_rng_state(), torch.cuda.get_rng_state(dev))
     for out in (None, str(tmp_path / "again")):
         summary = causal_graph.main(["-c", str(path), "--factor-names", "hue,size"] + (["--out", out] if out else []))
+        assert torch.equal(torch.get_rng_state(), before[0]) and torch.equal(torch.cuda.get_rng_state(dev), before[1])
         d = out or str(tmp_path / "logs" / "CTMCQVAE" / "causal_graph")
         assert sorted(os.listdir(d)) == sorted(causal_graph.FILES) and len(causal_graph.FILES) == 5
         runs.append({f: open(os.path.join(d, f), "rb").read() for f in causal_graph.FILES})

@@ -209,14 +209,3 @@ def test_command_refuses_with_a_reason(tmp_path):
     with pytest.raises(SystemExit, match="2 names.*6 factors"):
         causal_graph.main(["-c", _config(tmp_path, "ct_mcq_vae.yaml"), "--checkpoint", missing, "--factor-names", "a,b"])
     assert not os.path.exists(tmp_path / "logs")                    # nothing was written
-
-
-def test_npz_bytes_are_reproducible_and_load():
-    import io
-    from ctvae_amd import causal_graph
-    arrays = {"adjacency_mean": np.arange(8.0).reshape(2, 2, 2), "rows": np.array([3, 0])}
-    data = causal_graph.npz_bytes(arrays)
-    assert data == causal_graph.npz_bytes(arrays)
-    back = np.load(io.BytesIO(data))
-    assert sorted(back.files) == ["adjacency_mean", "rows"]
-    assert np.array_equal(back["adjacency_mean"], arrays["adjacency_mean"]) and back["rows"].tolist() == [3, 0]

@@ -274,7 +274,10 @@ def test_tool_writes_its_four_files(dev, tmp_path):
     assert not (tmp_path / "logs").exists()
     out = tmp_path / "out"
     args = ["--components", "2", "--covariance", "diag", "--max-iter", "20"]
+    torch.manual_seed(123)
+    before = (torch.get_rng_state(), torch.cuda.get_rng_state(dev))
     summary = fit_prior.main(["-c", cfg_path, "--checkpoint", str(both), "--out", str(out), "--samples", "14"] + args)
+    assert torch.equal(torch.get_rng_state(), before[0]) and torch.equal(torch.cuda.get_rng_state(dev), before[1])
     assert sorted(os.listdir(out)) == sorted(fit_prior.FILES)
     on_disk = json.load(open(out / "latent_prior.json"))
     assert on_disk == json.loads(json.dumps(summary))

@@ -64,8 +64,8 @@ def _ref_of(pairs, L):
 
 def _encoded(model, val):
     """(mu, log_var) of every validation batch by ``encode()``, in eval mode, with the weights the model holds now."""
-    from ctvae_amd.metrics import _eval_mode
-    with _eval_mode(model):
+    from ctvae_amd.evalrun import eval_mode
+    with eval_mode(model):
         return [tuple(t.clone() for t in model.encode(b[0])[:2]) for b in val]
 
 
@@ -273,8 +273,11 @@ def test_tool_writes_its_four_files(dev, tmp_path):
     with pytest.raises(SystemExit, match="--ema.*plain.ckpt holds no ema_state_dict"):
         latent_stats.main(["-c", cfg_path, "--checkpoint", str(plain), "--ema"])
     assert not (tmp_path / "logs").exists()
+    torch.manual_seed(123)
+    before = (torch.get_rng_state(), torch.cuda.get_rng_state(dev))
     out = tmp_path / "out"
     summary = latent_stats.main(["-c", cfg_path, "--checkpoint", str(both), "--out", str(out), "--traverse", "3", "--steps", "5"])
+    assert torch.equal(torch.get_rng_state(), before[0]) and torch.equal(torch.cuda.get_rng_state(dev), before[1])
     assert sorted(os.listdir(out)) == sorted(latent_stats.FILES)
     on_disk = json.load(open(out / "latent_stats.json"))
     assert on_disk["rows"] == 8 * 4 and len(on_disk["kl"]) == 128 and sorted(on_disk["ranked_dims"]) == list(range(128))

@@ -175,7 +175,7 @@ def test_mcqvae_record_without_files(dev):
 # ---- 4. ema_eval ---------------------------------------------------------------------------------------------
 def test_ema_eval_describes_the_averaged_weights(dev):
     from ctvae_amd.experiment import VAEXperiment
-    from ctvae_amd.metrics import _eval_mode
+    from ctvae_amd.evalrun import eval_mode
     train, val = _batches(dev, 3), _batches(dev, 2, seed=4900)
     got, want = {}, {}
     for ema_eval in (True, False):
@@ -187,7 +187,7 @@ def test_ema_eval_describes_the_averaged_weights(dev):
         got[ema_eval] = exp.fit(lambda: iter([]), lambda: iter(val), max_epochs=1)[0]["val_recon_psnr"]
         torch.manual_seed(7)               # the same draws for the forward passes below
         with exp.ema_weights() if ema_eval else torch.no_grad():
-            with _eval_mode(exp.model), torch.no_grad():
+            with eval_mode(exp.model), torch.no_grad():
                 pairs = [exp.model(b[0], labels=b[1])[:2] for b in val]
             want[ema_eval] = _ref_of(pairs)[0]["psnr"]
         assert not exp.ema.swapped

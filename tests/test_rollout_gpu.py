@@ -236,8 +236,11 @@ def test_apply_action_command_end_to_end(dev, tmp_path):
     path.write_text(yaml.safe_dump(cfg))
     files = ("rollout_input.png", "rollout_sheet.png", "action_accuracy.json")
     runs = []
+    torch.manual_seed(123)
+    before = (torch.get_rng_state(), torch.cuda.get_rng_state(dev))
     for out in (None, str(tmp_path / "again")):
         apply_action.main(["-c", str(path), "--steps", "2", "--image-index", "1"] + (["--out", out] if out else []))
+        assert torch.equal(torch.get_rng_state(), before[0]) and torch.equal(torch.cuda.get_rng_state(dev), before[1])
         d = out or str(tmp_path / "logs" / "CTMCQVAE" / "apply_action")
         assert sorted(os.listdir(d)) == sorted(files)
         runs.append({f: open(os.path.join(d, f), "rb").read() for f in files})
