@@ -213,6 +213,11 @@ int launch_recon_record(const float* a, const float* b, int B, int S, int C, con
 int launch_recon_worst(const double* old_ssim, const int* old_row, const float* old_a, const float* old_b, const double* rec,
                        const int* flag, int row0, int B, int capacity, const float* bat_a, const float* bat_b, int S, int C, int K,
                        double* new_ssim, int* new_row, float* new_a, float* new_b, int* src, hipStream_t st);
+int launch_loglik_latent(const float* mu, const float* lv, const float* eps, int B, int S, int L, float* z, double* a,
+                         hipStream_t st);
+int launch_loglik_rows(const float* xhat, const float* x, int B, int S, long P, const double* a, const double* consts, double* lw,
+                       hipStream_t st);
+int launch_loglik_merge(const double* lw, int B, int S, double* state, int* flag, int row0, int capacity, hipStream_t st);
 size_t freebits_workspace_bytes(int L);
 int launch_freebits_kl(const float* mu, long mu_pitch, const float* lv, long lv_pitch, int B, int L, const float* w_dev, float scale,
                        float lambda, float* out4, float* g_mu, float* g_lv, float* ws, size_t ws_bytes, hipStream_t st);
@@ -1254,6 +1259,20 @@ int ctvae_recon_worst(const double* old_ssim, const int32_t* old_row, const floa
                       int K, double* new_ssim, int32_t* new_row, float* new_a, float* new_b, int32_t* source, void* stream) {
   return launch_recon_worst(old_ssim, old_row, old_a, old_b, records, flags, row0, B, capacity, batch_a, batch_b, S, C, K, new_ssim,
                             new_row, new_a, new_b, source, (hipStream_t)stream);
+}
+
+int ctvae_loglik_latent(const float* mu, const float* logvar, const float* eps, int B, int S, int L, float* z, double* a,
+                        void* stream) {
+  return launch_loglik_latent(mu, logvar, eps, B, S, L, z, a, (hipStream_t)stream);
+}
+
+int ctvae_loglik_rows(const float* xhat, const float* x, int B, int S, long P, const double* a, const double* consts, double* lw,
+                      void* stream) {
+  return launch_loglik_rows(xhat, x, B, S, P, a, consts, lw, (hipStream_t)stream);
+}
+
+int ctvae_loglik_merge(const double* lw, int B, int S, double* state, int32_t* flags, int row0, int capacity, void* stream) {
+  return launch_loglik_merge(lw, B, S, state, flags, row0, capacity, (hipStream_t)stream);
 }
 
 size_t ctvae_freebits_workspace_bytes(int L) { return freebits_workspace_bytes(L); }

@@ -33,8 +33,8 @@ freeze; the dead list is formed on the host), and runs once per optimizer step, 
 
 The validation order.  ``_validate`` arms every report the run has (a context each: reset or rebuilt, then observing; disarmed
 in a ``finally``), runs the validation steps, and collects in the key order of the epoch record: the steps' means,
-``write_graphs``, ``write_codebook_stats``, ``write_latent_stats``, ``write_recon_stats``, ``write_prior``, ``validation_metrics``, and last
-``sample_images``.  The reports are eager like all of validation, make their one device-to-host copy behind the steps, are rank
+``write_graphs``, ``write_codebook_stats``, ``write_latent_stats``, ``write_recon_stats``, ``write_prior``, ``write_loglik``,
+``validation_metrics``, and last ``sample_images``.  The reports are eager like all of validation, make their one device-to-host copy behind the steps, are rank
 0's own rows (no collective) and, under ``ema_eval``, describe the averaged weights; a ``validation_step`` outside ``_validate``
 observes nothing.
 
@@ -155,6 +155,18 @@ out), and with a ``sample_dir`` writes ``Recon/recon_stats_<name>_Epoch_<e>.npz`
 draws nothing and writes no model state, so training is bit for bit the same with and without it.  Refused when the
 experiment is built: a bad value, a dependent key without the main one, and IWAE / MIWAE, whose ``forward`` hands out
 [B, S, C, H, W] samples.  Without the key there is no buffer, no launch, no file and no log key.
+``exp_params.val_loglik`` (a mapping with ``samples``, an int in 1..4096, ``sigma``, a float > 0, and the optional ``chunk``;
+``loglik.loglik_setting``): the marginal log-likelihood of every validation image by importance sampling under N(decode(z),
+sigma^2 I), for the models in ``loglik.LOGLIK_MODELS``, by ``loglik.ImportanceLogLik`` on rank 0, a report of ``_validate``.  Armed,
+it is reset and every ``validation_step`` hands it the batch's images (``results[1]``) and ``gaussian_posterior(results)``: per
+chunk one ``torch.randn`` from a generator of the report's own, seeded from ``epoch_seed(e)``, ``ctvae_loglik_latent``, the
+decoder on ``batch * chunk`` rows, ``ctvae_loglik_rows`` and ``ctvae_loglik_merge`` (csrc/loglik.hip), no host synchronisation;
+``write_loglik`` makes the one copy and adds ``val_loglik`` / ``_elbo`` / ``_gap`` / ``_ess`` / ``_rows`` / ``_nonfinite`` to the epoch
+record and the JSONL log (what has no image to stand on is left out) and, with a ``sample_dir``,
+``Loglik/loglik_<name>_Epoch_<e>.npz``.  The decoder runs in eval mode under ``no_grad``: it writes no model state, moves no other
+random stream and adds nothing to checkpoints, so training is bit for bit the same with and without it.  Refused when the
+experiment is built: a bad value, ``sigma: mse`` (the command's alone) and any other model.  Without the key there is no buffer,
+no launch, no file and no log key.
 """
 import contextlib
 import json
@@ -172,6 +184,7 @@ from .latentprior import (PRIOR_DIR, CodeBuffer, GaussianMixturePrior, draw_code
                           prior_supported)
 from .latentstats import (LATENT_DIR, LatentStats, has_gaussian_posterior, latent_stats_setting, needs_gaussian_posterior,
                           record as latent_record, write_files as write_latent_files)
+from . import loglik
 from .reconstats import (RECON_DIR, ReconStats, recon_settings, record as recon_record, refuses_model as recon_refuses_model,
                          summarize as recon_summarize, write_files as write_recon_files)
 from .optim import (CodebookEMA, CodebookUsage, ExponentialLR, FlatAdam, GradientTracker, WeightEMA, absent_grad_setting,
@@ -342,6 +355,16 @@ class VAEXperiment:
                 raise ValueError(needs_supported_model(vae_model))
             if self._rank0():
                 self.val_prior = CodeBuffer(vae_model.latent_dim, next(vae_model.parameters()).device)
+        # test log-likelihood by importance sampling (loglik.ImportanceLogLik): validated on every rank, built on rank 0 only
+        self.loglik_cfg = loglik.loglik_setting(params.get("val_loglik"))
+        self.val_loglik = None
+        if self.loglik_cfg is not None:
+            if not loglik.loglik_supported(vae_model):
+                raise ValueError("val_loglik: " + loglik.needs_supported_model(vae_model))
+            if self._rank0():
+                cfg = self.loglik_cfg      # (pixels None: the first batch says how many elements an image has)
+                self.val_loglik = loglik.ImportanceLogLik(vae_model.latent_dim, None, cfg["sigma"], cfg["samples"], cfg["chunk"],
+                                                          next(vae_model.parameters()).device)
         # reconstruction quality (reconstats.ReconStats): validated on every rank, built on rank 0 only; CT-MCQ-VAE gets one
         # accumulator per picture mode
         self.recon_stats, self.recon_range, self.recon_worst = recon_settings(params)
@@ -925,6 +948,19 @@ class VAEXperiment:
                                   os.path.join(d, f"worst_{self.run_name}{sfx}_Epoch_{epoch}.png") if acc.K > 0 else None)
         return self._write_epoch_record(rec)
 
+    def write_loglik(self, acc, epoch: int) -> dict:
+        """What ``val_loglik`` leaves of one validation epoch: one copy of the importance sampler's state, finished on the host in
+        float64; ``val_loglik`` (mean nats per image), ``val_loglik_elbo``, ``val_loglik_gap``, ``val_loglik_ess`` -- over the images
+        without a non-finite log-weight, left out when there is none -- ``val_loglik_rows`` and ``val_loglik_nonfinite``; also one
+        JSONL line, and with a ``sample_dir`` and at least one row ``Loglik/loglik_<name>_Epoch_<e>.npz``."""
+        res = acc.result()
+        rec = loglik.record(loglik.summarize(res, acc.P or 1))
+        if self.sample_dir is not None and len(res["nonfinite"]):
+            d = os.path.join(self.sample_dir, loglik.LOGLIK_DIR)
+            os.makedirs(d, exist_ok=True)
+            loglik.write_file(res, os.path.join(d, f"loglik_{self.run_name}_Epoch_{epoch}.npz"))
+        return self._write_epoch_record(rec)
+
     def _load_codebook_state(self, entry):
         """Full resume under ``codebook_restart_every``: the window's counts, the restart ordinal and the total come back, so a
         run resumed inside a window continues bit for bit; other ``every`` / ``min_count`` than the checkpoint's are refused."""
@@ -1008,11 +1044,27 @@ class VAEXperiment:
         with self._observing_results(observe):
             yield lambda: self.write_prior(self.val_prior, epoch)
 
+    @contextlib.contextmanager
+    def _loglik_report(self, epoch):
+        """Every validation batch's images and posteriors -- tensors the step already holds -- feed the importance sampler."""
+        acc = self.val_loglik
+        acc.reset()
+        g = torch.Generator(device=acc.device)         # a generator of the report's own: no other random stream moves
+        g.manual_seed(self.epoch_seed(epoch))
+        decode = loglik.decoder_of(self.model)
+
+        def observe(results):
+            mu, log_var = self.model.gaussian_posterior(results)
+            acc.add_batch(loglik.images_for(self.model, results[1]), mu, log_var, decode, g)
+
+        with self._observing_results(observe):
+            yield lambda: self.write_loglik(acc, epoch)
+
     def _val_reports(self):
         """The reports this run has on this rank, in the order of their keys in the epoch record."""
         reports = ((self._graph_report, self.val_graphs and self._rank0()), (self._codebook_report, self.val_codebook is not None),
                    (self._latent_report, self.val_latents is not None), (self._recon_report, self.val_recon is not None),
-                   (self._prior_report, self.val_prior is not None))
+                   (self._prior_report, self.val_prior is not None), (self._loglik_report, self.val_loglik is not None))
         return [report for report, on in reports if on]
 
     def _validate(self, epoch, val_batches, test_batches):

@@ -3375,3 +3375,118 @@ def gmm_sample(u, eps, cdf, mu, L, full=True):
         native.call("ctvae_gmm_sample", u.data_ptr(), eps.data_ptr(), n, D, K, 1 if full else 0, cdf.data_ptr(), mu.data_ptr(),
                     L.data_ptr(), z.data_ptr(), k.data_ptr())
     return z, k
+
+
+# ---------------------------------------------------------------------------------------------------
+# test log-likelihood by importance sampling (csrc/loglik.hip; loglik.ImportanceLogLik)
+# ---------------------------------------------------------------------------------------------------
+LOGLIK_STATE = ("m", "s", "s2", "t", "n")          # the columns of the merge state
+
+
+def loglik_consts(sigma, P, device=None):
+    """The two doubles ``ctvae_loglik_rows`` reads from device memory, computed on the host in float64: ``1 / (2 sigma^2)`` and
+    ``(P / 2) log(2 pi sigma^2)`` of the observation model N(decode(z), sigma^2 I) over P elements."""
+    import math
+    if isinstance(sigma, bool) or not isinstance(sigma, (int, float)) or not (sigma > 0 and sigma < float("inf")):
+        raise ValueError(f"loglik_consts: sigma must be a finite number > 0, got {sigma!r}")
+    if isinstance(P, bool) or not isinstance(P, int) or P < 1:
+        raise ValueError(f"loglik_consts: P must be an integer of at least 1, got {P!r}")
+    s2 = float(sigma) * float(sigma)
+    if not (s2 > 0 and 1.0 / (2.0 * s2) < float("inf")):
+        raise ValueError(f"loglik_consts: sigma^2 leaves float64 for sigma={sigma!r}")
+    return torch.tensor([1.0 / (2.0 * s2), 0.5 * P * math.log(2.0 * math.pi * s2)], dtype=torch.float64,
+                        device="cuda" if device is None else device)
+
+
+def loglik_latent(mu, log_var, eps):
+    """``ctvae_loglik_latent``: ``mu``, ``log_var`` fp32 [B, L] and ``eps`` fp32 [B, S, L], all contiguous.  Returns ``(z [B * S, L]
+    fp32, a [B * S] float64)``: ``z = mu + expf(0.5f * log_var) * eps`` and ``a = log p(z) - log q(z|x)``, formed in float64 from
+    the stored z.  One launch.  A CPU tensor is a RuntimeError; a wrong dtype or shape raises a ValueError that names it."""
+    what = "loglik_latent"
+    for name, t, rank in (("mu", mu, 2), ("log_var", log_var, 2), ("eps", eps, 3)):
+        _req_dense(what, name, t, torch.float32)
+        if t.dim() != rank:
+            raise ValueError(f"{what}: {name} must be {'[B, L]' if rank == 2 else '[B, S, L]'}, got {tuple(t.shape)}")
+    B, S, L = eps.shape
+    if tuple(mu.shape) != (B, L) or tuple(log_var.shape) != (B, L) or S < 1 or L < 1:
+        raise ValueError(f"{what}: mu {tuple(mu.shape)}, log_var {tuple(log_var.shape)} and eps {tuple(eps.shape)} must be [B, L], "
+                         f"[B, L] and [B, S, L] with S >= 1 and L >= 1")
+    _req_cuda(mu, log_var, eps)
+    z = torch.empty(B * S, L, dtype=torch.float32, device=eps.device)
+    a = torch.empty(B * S, dtype=torch.float64, device=eps.device)
+    if B:
+        native.call("ctvae_loglik_latent", mu.data_ptr(), log_var.data_ptr(), eps.data_ptr(), B, S, L, z.data_ptr(), a.data_ptr())
+    return z, a
+
+
+def loglik_memory_formats(t):
+    """The dense memory formats a logical [N, C, H, W] tensor lies in: a subset of ("nchw", "nhwc") -- both for C == 1 or
+    H * W == 1, none for anything strided."""
+    return tuple(name for name, v in (("nchw", t), ("nhwc", t.permute(0, 2, 3, 1))) if v.is_contiguous())
+
+
+def loglik_rows(xhat, x, S, a, consts):
+    """``ctvae_loglik_rows``: ``xhat`` logical [B * S, C, H, W] fp32 (the decoded rows), ``x`` logical [B, C, H, W] fp32 (the
+    images), read where they lie: both must be dense in the same memory format, NCHW-contiguous or channels-last (the decoder's
+    NCHW view over NHWC memory); any other pairing is a ValueError, nothing is copied.  ``a`` float64 [B * S] (``loglik_latent``'s)
+    or None for 0; ``consts``: ``loglik_consts(sigma, P)``.  Returns ``lw`` float64 [B * S].  One launch."""
+    what = "loglik_rows"
+    for name, t in (("xhat", xhat), ("x", x)):
+        if not torch.is_tensor(t) or t.dtype != torch.float32 or t.dim() != 4:
+            raise ValueError(f"{what}: {name} must be a torch.float32 [N, C, H, W] tensor, got "
+                             f"{getattr(t, 'dtype', type(t).__name__)} {tuple(getattr(t, 'shape', ()))}")
+    if isinstance(S, bool) or not isinstance(S, int) or S < 1:
+        raise ValueError(f"{what}: S must be an integer of at least 1, got {S!r}")
+    B = x.size(0)
+    if tuple(xhat.shape) != (B * S,) + tuple(x.shape[1:]) or x[0].numel() < 1:
+        raise ValueError(f"{what}: xhat {tuple(xhat.shape)} must be [B * S, C, H, W] for x {tuple(x.shape)} and S={S}")
+    xhat, x = xhat.detach(), x.detach()
+    fh, fx = loglik_memory_formats(xhat), loglik_memory_formats(x)
+    if not set(fh) & set(fx):
+        say = lambda f: " / ".join({"nchw": "NCHW-contiguous", "nhwc": "channels-last"}[k] for k in f) or "not dense"
+        raise ValueError(f"{what}: xhat is {say(fh)} and x is {say(fx)}: both must be dense in the same memory format "
+                         f"(NCHW-contiguous or channels-last); nothing is copied here")
+    R, P = B * S, x[0].numel()
+    if a is not None:
+        _req_dense(what, "a", a, torch.float64)
+        if tuple(a.shape) != (R,):
+            raise ValueError(f"{what}: a must be [{R}], got {list(a.shape)}")
+    _req_dense(what, "consts", consts, torch.float64)
+    if tuple(consts.shape) != (2,):
+        raise ValueError(f"{what}: consts must be loglik_consts(sigma, P), two doubles, got {list(consts.shape)}")
+    _req_cuda(xhat, x, a, consts)
+    lw = torch.empty(R, dtype=torch.float64, device=xhat.device)
+    if R:
+        native.call("ctvae_loglik_rows", xhat.data_ptr(), x.data_ptr(), B, S, P, native.ptr(a), consts.data_ptr(), lw.data_ptr())
+    return lw
+
+
+def loglik_state(capacity, device):
+    """An empty merge state: ``(state float64 [capacity, 5], flags int32 [capacity])``; the columns are ``LOGLIK_STATE`` -- m = -inf,
+    the rest 0."""
+    state = torch.zeros(int(capacity), len(LOGLIK_STATE), dtype=torch.float64, device=device)
+    state[:, 0] = float("-inf")
+    return state, torch.zeros(int(capacity), dtype=torch.int32, device=device)
+
+
+def loglik_merge(lw, S, state, flags, row0):
+    """``ctvae_loglik_merge``: the chunk's log-weights ``lw`` float64 [B * S] into rows [row0, row0 + B) of ``state`` (float64
+    [capacity, 5]) and ``flags`` (int32 [capacity]), one at a time in sample order.  One launch, no host synchronisation."""
+    what = "loglik_merge"
+    _req_dense(what, "lw", lw, torch.float64)
+    _req_dense(what, "state", state, torch.float64)
+    _req_dense(what, "flags", flags, torch.int32)
+    if isinstance(S, bool) or not isinstance(S, int) or S < 1:
+        raise ValueError(f"{what}: S must be an integer of at least 1, got {S!r}")
+    if lw.dim() != 1 or lw.numel() % S:
+        raise ValueError(f"{what}: lw must be [B * S] for S={S}, got {list(lw.shape)}")
+    cap = flags.numel()
+    if flags.dim() != 1 or tuple(state.shape) != (cap, len(LOGLIK_STATE)):
+        raise ValueError(f"{what}: state [capacity, {len(LOGLIK_STATE)}] and flags [capacity] do not fit: {tuple(state.shape)}, "
+                         f"{tuple(flags.shape)}")
+    B, row0 = lw.numel() // S, int(row0)
+    if row0 < 0 or row0 + B > cap:
+        raise ValueError(f"{what}: rows [{row0}, {row0 + B}) leave the capacity {cap}")
+    _req_cuda(lw, state, flags)
+    if B:
+        native.call("ctvae_loglik_merge", lw.data_ptr(), B, S, state.data_ptr(), flags.data_ptr(), row0, cap)

@@ -123,6 +123,9 @@ SIGNATURES = {
     "ctvae_gmm_sample": [_fp, _fp, _i, _i, _i, _i, _fp, _fp, _fp, _fp, _fp, _vp],
     "ctvae_recon_record": [_fp, _fp, _i, _i, _i, _fp, _fp, _fp, _i, _i, _vp],
     "ctvae_recon_worst": [_fp] * 6 + [_i] * 3 + [_fp] * 2 + [_i] * 3 + [_fp] * 5 + [_vp],
+    "ctvae_loglik_latent": [_fp, _fp, _fp, _i, _i, _i, _fp, _fp, _vp],
+    "ctvae_loglik_rows": [_fp, _fp, _i, _i, _l, _fp, _fp, _fp, _vp],
+    "ctvae_loglik_merge": [_fp, _i, _i, _fp, _fp, _i, _i, _vp],
     "ctvae_freebits_kl_forward_grad": [_fp, _l, _fp, _l, _i, _i, _fp, _f, _f, _fp, _fp, _fp, _fp, _sz, _vp],
     "ctvae_adam_step": [_fp, _fp, _fp, _fp, _fp, _l, _f, _vp],
     "ctvae_adam_step_clipped": [_fp, _fp, _fp, _fp, _fp, _l, _f, _i, _f, _fp, _fp, _vp],

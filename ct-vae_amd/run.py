@@ -78,6 +78,14 @@ their reconstructions) in the log directory (experiment.py, reconstats.py); CT-M
 under ``_base`` / ``_action``.  ``python -m ctvae_amd.recon_stats`` does the same for a checkpoint.  The top-k checkpoints are still
 chosen by ``val_Reconstruction_Loss``.  A bad value, a dependent key without ``recon_stats``, and IWAE / MIWAE are a SystemExit
 that names ``exp_params.recon_stats`` (or the dependent key).
+``exp_params.val_loglik: {samples: K, sigma: s}`` (``samples`` an int, 1..4096; ``sigma`` a float > 0, the observation model
+N(decode(z), sigma^2 I); optionally ``chunk``, an int in 1..K, default min(K, 64)) estimates the marginal log-likelihood of every
+validation image by importance sampling, K draws from its posterior (the IWAE bound; experiment.py, loglik.py, csrc/loglik.hip):
+``val_loglik`` (mean nats per image), ``val_loglik_elbo``, ``val_loglik_gap``, ``val_loglik_ess``, ``val_loglik_rows`` and
+``val_loglik_nonfinite`` in the epoch records and ``metrics_rank0.jsonl``, and ``Loglik/loglik_<name>_Epoch_<e>.npz`` (the per-image
+values) in the log directory.  It serves ``loglik.LOGLIK_MODELS``; ``python -m ctvae_amd.log_likelihood`` does the same for a
+checkpoint over the test split with up to 65536 samples, and alone knows ``sigma: mse``.  A refused value or model is a SystemExit
+that names ``exp_params.val_loglik``.
 """
 import argparse
 import json
@@ -373,6 +381,21 @@ def exp_sample_prior(config):
     return cfg
 
 
+def exp_val_loglik(config):
+    """``exp_params.val_loglik`` as None (absent: off) or the complete mapping (``loglik.loglik_setting``).  A refused value and a
+    model the estimate does not serve are a SystemExit that names the key."""
+    from . import loglik
+    try:
+        cfg = loglik.loglik_setting(config['exp_params'].get('val_loglik'))
+    except ValueError as e:
+        raise SystemExit(f"exp_params.{e}")
+    name = config['model_params'].get('name')
+    cls = vae_models.get(name)
+    if cfg is not None and (cls is None or not loglik.loglik_supported(cls)):
+        raise SystemExit(f"exp_params.val_loglik: {loglik.needs_supported_model(cls, name=repr(name))} (model_params.name)")
+    return cfg
+
+
 def exp_recon_stats(config) -> tuple:
     """``exp_params.recon_stats`` / ``recon_stats_range`` / ``recon_stats_worst`` as ``(on, R, K)``.  A refused value, a dependent key
     without the main one, and a model that hands out several reconstructions per image (IWAE, MIWAE) are a SystemExit that
@@ -451,6 +474,7 @@ def main(argv=None):
     kl_schedule, kl_free_bits = exp_kl(config)             # likewise
     recon_on, _, _ = exp_recon_stats(config)               # likewise
     exp_sample_prior(config)                               # likewise
+    exp_val_loglik(config)                                 # likewise
 
     rank =int(os.environ.get("RANK", "0"))
     world = int(os.environ.get("WORLD_SIZE", "1"))

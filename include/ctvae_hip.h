@@ -725,6 +725,37 @@ int ctvae_recon_worst(const double* old_ssim, const int32_t* old_row, const floa
                       const int32_t* flags, int row0, int B, int capacity, const float* batch_a, const float* batch_b, int S, int C,
                       int K, double* new_ssim, int32_t* new_row, float* new_a, float* new_b, int32_t* source, void* stream);
 
+/* Test log-likelihood by importance sampling (exp_params.val_loglik, python -m ctvae_amd.log_likelihood; loglik.py:
+ * ImportanceLogLik).  An image's K samples z_k ~ q(z|x) arrive in chunks of S: one chunk is R = B * S decoder rows, row r belongs
+ * to image r / S.  Three entry points, one launch each, no atomics, no host synchronisation; the finish is the host's, in
+ * float64 from one copy of the state: loglik = m + log s - log n, elbo = t / n, ess = s^2 / s2.
+ *
+ * Latent: mu, logvar fp32 [B][L], eps fp32 [B][S][L], any L >= 1.  Writes z fp32 [R][L], z = mu + expf(0.5f * logvar) * eps, and
+ * a double [R], a[r] = log p(z) - log q(z|x) = -0.5 * sum_d (z^2 - eps^2 - logvar) -- the log 2 pi terms cancel -- formed in
+ * double from the fp32 z that was stored.  One wave per row, a fixed shuffle tree.  B == 0 is a successful no-op; B < 0, S < 1,
+ * L < 1 or a NULL pointer returns -22 and launches nothing. */
+int ctvae_loglik_latent(const float* mu, const float* logvar, const float* eps, int B, int S, int L, float* z, double* a,
+                        void* stream);
+
+/* Rows: xhat fp32 [R][P] (the decoded rows), x fp32 [B][P] (the images), both dense and in ONE element order (the caller pairs
+ * NCHW with NCHW or NHWC with NHWC; the kernel sees P elements per row).  sse[r] = sum_i ((double)xhat[r][i] - (double)x[r / S][i])^2
+ * in a fixed order -- 16-byte loads when P % 4 == 0 and both base pointers are 16-byte aligned, scalar loads otherwise; the
+ * two orders differ in the last bits -- then lw[r] = -sse * consts[0] - consts[1] + a[r], double [R].  consts: two doubles in
+ * DEVICE memory, 1 / (2 sigma^2) and (P / 2) log(2 pi sigma^2); (1, 0) makes lw = -sse.  a: double [R], or NULL for 0.  One
+ * workgroup per row.  A row's bits do not depend on B, S or the other rows.  B == 0 is a successful no-op; B < 0, S < 1, P < 1
+ * or a NULL pointer (a excepted) returns -22 and launches nothing. */
+int ctvae_loglik_rows(const float* xhat, const float* x, int B, int S, long P, const double* a, const double* consts, double* lw,
+                      void* stream);
+
+/* Merge: image i of the batch owns row row0 + i of state [capacity][5] double -- m (the running maximum; -inf when empty), s =
+ * sum exp(lw - m), s2 = sum exp(2 (lw - m)), t = sum lw, n (the count) -- and of flags [capacity] int32.  ONE thread takes the
+ * chunk's S log-weights lw[i][0..S) one at a time, in sample order; when the maximum moves, s and s2 are rescaled by exp(m - lw)
+ * and its square.  No operation is contracted.  The state after K samples is therefore the same bits however they were cut
+ * into chunks.  A log-weight that is NaN or +-inf sets the image's flag and is not merged.  Rows outside [row0, row0 + B) are
+ * not written.  B == 0 is a successful no-op; B < 0, S < 1, row0 < 0, row0 + B > capacity or a NULL pointer returns -22 and
+ * launches nothing. */
+int ctvae_loglik_merge(const double* lw, int B, int S, double* state, int32_t* flags, int row0, int capacity, void* stream);
+
 /* The Gaussian KL term with free bits and a weight that lives in device memory (exp_params.kld_free_bits / kld_schedule;
  * klcontrol.py, kernels.FreeBitsKL).  mu and logvar are fp32 [B][L] with a row pitch each, as for ctvae_latent_accumulate.
  *   t_bd = 1 + lv - m^2 - e^lv in fp32 (ctvae_loss_forward's expression);  m_d = -0.5 * (sum_b t_bd) / B, the sum in double with
