@@ -8,10 +8,6 @@
 #include "pair.hpp"
 
 namespace ctvae {
-int launch_tapgemm(const ConvGeom& g, const float* G, const float* W, const float* bias, const float* add,
-                   const float* mask, int mask_act, float* S, int act, float* bn_part, float* ws, size_t ws_floats,
-                   hipStream_t st, const BnBwdFuse* bnb = nullptr, const InXform* xf = nullptr,
-                   const WinoFilters* wf = nullptr, SplitKRaw* raw = nullptr, int out_pix = 0);
 bool out_pix_supported(const ConvGeom& g, size_t ws_floats, int out_pix);
 bool wino_supported(const ConvGeom& g, size_t ws_floats);
 bool wino_enabled();
@@ -20,11 +16,7 @@ int launch_crop_resize_u8(const unsigned char* img, const long long* rows, float
                           int S, hipStream_t st);
 bool thin_forward_supported(const ConvGeom& g);
 bool thin_wgrad_supported(const ConvGeom& g);
-int tapgemm_bnb_rows(const ConvGeom& g, size_t ws_floats);
 bool img_dgrad_supported(const ConvGeom& g);
-void tapgemm_plan(const ConvGeom& g, size_t ws_floats, TapGemmPlan& p);
-int launch_wgrad(const ConvGeom& g, const float* X, const float* dY, float* dW, float* dbias, float* ws, size_t ws_bytes,
-                 int accumulate, hipStream_t st, const InXform* xf = nullptr, const DyXform* dyx = nullptr);
 int launch_bn_forward(const float* y, int R, int C, const float* gamma, const float* beta, float* running_mean,
                       float* running_var, float momentum, float eps, int training, int act, float* out, float* save_mean,
                       float* save_invstd, float* ws, size_t ws_bytes, long long* nbt, hipStream_t st,
@@ -46,8 +38,6 @@ bool img_conv_supported(const ConvGeom& g);
 int launch_img_backward_fused(const ConvGeom& g, const float* dY, const float* W, float* dX, const BnBwdFuse* bnb, float* ws,
                               float** part_out, float** pbias_out, int* nparts, bool want_bias, hipStream_t st);
 size_t img_backward_fused_ws_floats(const ConvGeom& g);
-int wgrad_finish_slabs(const float* part, float* dW, long n, int nparts, const float* pbias, float* dbias, long nb, int accumulate,
-                       hipStream_t st);
 int launch_permute(const float* in, float* out, int B, int C, int P, int to_nhwc, hipStream_t st);
 int launch_gat_score(int mode, const float* xl, const float* xr, const float* attr, const float* we, const float* att, float* out,
                      int B, int N, int H, int C, float slope, hipStream_t st);
@@ -352,7 +342,7 @@ int ctvae_conv_input_transform_supported(int kind, int B, int H, int W, int Ci, 
   if (img_enc_supported(g) || img_conv_supported(g)) return 0;
   if (wino_enabled() && wino_supported(g, (size_t)1 << 26)) return 0;
   TapGemmPlan pl;
-  tapgemm_plan(g, (size_t)1 << 26, pl);
+  tapgemm_plan(g, (size_t)1 << 26, pl, false);
   if (pl.thin || pl.BM == 0) return 0;
   return ((g.gC % KC) == 0 && (g.sC % 4) == 0 && g.wT == 0) ? 1 : 0;
 }
@@ -363,7 +353,7 @@ int ctvae_conv_bn_act_apply_is_separate(int kind, int B, int H, int W, int Ci, i
   ConvGeom g;
   if (conv_geom(g, kind, 0, B, H, W, Ci, Co, k, stride, pad, out_pad)) return 0;
   TapGemmPlan plan;
-  tapgemm_plan(g, ws_bytes / sizeof(float), plan);
+  tapgemm_plan(g, ws_bytes / sizeof(float), plan, false);
   return (plan.splitk > 1 && bn_fused_ok(g.B * g.sH * g.sW, Co)) ? 0 : 1;   // 0: the channel-owner launch writes a anyway
 }
 
@@ -387,7 +377,7 @@ int ctvae_conv_bn_act_forward(int kind, const float* x, const float* w, const fl
   if (conv_geom(g, kind, 0, B, H, W, Ci, Co, k, stride, pad, out_pad)) return kErrBadArg;
   const size_t wsf = ws_bytes / sizeof(float);
   TapGemmPlan plan;
-  tapgemm_plan(g, wsf, plan);
+  tapgemm_plan(g, wsf, plan, false);
   const int R = g.B * g.sH * g.sW;
   if (plan.splitk > 1 || !training) {
     // small layer run split-K (or eval mode).  Training, a few MB at most: the slices stay channel-major in the workspace and ONE
@@ -455,17 +445,8 @@ int ctvae_conv_backward_bn_rows(int kind, int B, int H, int W, int Ci, int Co, i
   if (!conv_kind_ok(kind)) return 0;
   ConvGeom g;
   if (conv_geom(g, kind, 2, B, H, W, Ci, Co, k, stride, pad, out_pad)) return 0;
-  PairCtx ctx;                      // plan as ctvae_conv_backward does
-  pair_ctx() = &ctx;
-  const int rows = tapgemm_bnb_rows(g, ((ws_bytes / 2) & ~(size_t)255) / sizeof(float));
-  pair_ctx() = nullptr;
-  return rows;
+  return tapgemm_bnb_rows(g, ((ws_bytes / 2) & ~(size_t)255) / sizeof(float), true);   // plan as ctvae_conv_backward does
 }
-
-static thread_local int g_lazy_pixel_major = 0;   // layout of the slices the next conv_backward_impl(dx_slices) leaves (set by its caller)
-// set by the callers of the next conv_backward_impl (and taken by it):
-static thread_local int g_no_dx = 0;                          // ctvae_conv_backward_nodx: the picture-side conv's g_a is not written
-static thread_local const DyRecompute* g_recompute = nullptr; // ctvae_conv_backward_recompute: dy is absent, formed in the kernel
 
 // the picture-side conv behind the transposed conv of geometry g1 (kind 0): its data-gradient taps for the recompute mode
 static bool recompute_geom(const ConvGeom& g1, int kind2, int Co2, int k2, int stride2, int pad2, int out_pad2, DyRecompute* rc) {
@@ -478,96 +459,101 @@ static bool recompute_geom(const ConvGeom& g1, int kind2, int Co2, int k2, int s
   return true;
 }
 
-// dx_slices != nullptr: the data gradient must run split-K and leaves its raw slices there, channel-major (SplitKRaw); dx is
-// not written (ctvae_conv_backward_lazy)
-static int conv_backward_impl(int kind, const float* x, const float* dy, const float* w, float* dw, float* dbias, float* dx, int B,
-                        int H, int W, int Ci, int Co, int k, int stride, int pad, int out_pad, int accumulate, const float* mask,
-                        int mask_act, const float* wino_filters, const float* bn_y, const float* bn_mean,
-                        const float* bn_invstd, const float* bn_gamma, const float* bn_beta, int bn_act, float* bn_part,
-                        int bn_part_rows, float* bn_coef_out, float* bn_dgamma, float* bn_dbeta, int bn_accumulate,
-                        const float* in_scale, const float* in_shift, int in_act,
-                        const float* dy_bn_y, const float* dy_bn_coef, int dy_bn_act, float* gy_out, float* ws, size_t ws_bytes,
-                        void* stream, float* dx_slices) {
-  const bool no_dx = g_no_dx != 0;
-  const DyRecompute* const recompute = g_recompute;
-  g_no_dx = 0;
-  g_recompute = nullptr;
-  if (!x || (!dy && !recompute) || !w || !dw || (!dx && !dx_slices && !no_dx) || !ws || !conv_kind_ok(kind)) return kErrBadArg;
-  if (recompute != nullptr && (dy_bn_y == nullptr || gy_out == nullptr)) return kErrBadArg;
-  const bool bn = bn_part != nullptr;
-  if (bn_coef_out != nullptr && !bn) return kErrBadArg;
-  if ((bn_dgamma != nullptr) != (bn_dbeta != nullptr) || (bn_dgamma != nullptr && bn_coef_out == nullptr)) return kErrBadArg;
-  if ((in_scale != nullptr) != (in_shift != nullptr)) return kErrBadArg;
-  if ((dy_bn_y != nullptr) != (dy_bn_coef != nullptr) || (dy_bn_y != nullptr) != (gy_out != nullptr)) return kErrBadArg;
-  if (bn && (!bn_y || !bn_mean || !bn_invstd || !bn_gamma || !bn_beta)) return kErrBadArg;
-  ConvGeom gw, gd;
-  if (conv_geom(gw, kind, 0, B, H, W, Ci, Co, k, stride, pad, out_pad)) return kErrBadArg;
-  if (conv_geom(gd, kind, 2, B, H, W, Ci, Co, k, stride, pad, out_pad)) return kErrBadArg;
-  // the two GEMMs run concurrently: each gets its own half of the workspace
-  const size_t half_bytes = (ws_bytes / 2) & ~(size_t)255, half_floats = half_bytes / sizeof(float);
-  float* ws_d = ws + half_floats;
-  if (wino_filters != nullptr && !ctvae_conv_wino_filter_floats(kind, B, H, W, Ci, Co, k, stride, pad, out_pad, half_bytes))
+// One paired backward call.  The five ctvae_conv_backward* entry points fill in what they have; the rest stays null / 0
+struct ConvShape {
+  int kind, B, H, W, Ci, Co, k, stride, pad, out_pad;
+};
+struct ConvBackwardCall {
+  ConvShape s;
+  const float *x, *dy, *w;      // dy is absent (null) with dyx.rc: formed in the kernel
+  float *dw, *dbias, *dx;
+  int accumulate;
+  const float* mask;
+  int mask_act;
+  const float* wino_filters;
+  BnBwdFuse bn;                 // bn.part != nullptr: the data gradient emits the backward sums of the BatchNorm below
+  int bn_part_rows;
+  float* bn_coef_out;           // that BatchNorm's finalize rides in the finishing launch,
+  float *bn_dgamma, *bn_dbeta;  // and commits its parameter gradients
+  int bn_accumulate;
+  InXform in;
+  DyXform dyx;                  // dyx.rc: ctvae_conv_backward_recompute
+  float* ws;
+  size_t ws_bytes;
+  bool no_dx;                   // ctvae_conv_backward_nodx: the picture-side conv's g_a is not written
+  float* dx_slices;             // ctvae_conv_backward_lazy: the data gradient must run split-K and leaves its raw slices here
+  int slices_pixel_major;       // (SplitKRaw), channel-major or pixel-major; dx is not written
+};
+
+static int conv_backward_impl(const ConvBackwardCall& c, hipStream_t st) {
+  const ConvShape& s = c.s;
+  const BnBwdFuse& f = c.bn;
+  const DyRecompute* const recompute = c.dyx.rc;
+  if (!c.x || (!c.dy && !recompute) || !c.w || !c.dw || (!c.dx && !c.dx_slices && !c.no_dx) || !c.ws || !conv_kind_ok(s.kind))
     return kErrBadArg;
-  const hipStream_t st = (hipStream_t)stream;
-  PairCtx ctx;
-  pair_ctx() = &ctx;
+  if (recompute != nullptr && (c.dyx.y == nullptr || c.dyx.gy_out == nullptr)) return kErrBadArg;
+  const bool bn = f.part != nullptr;
+  if (c.bn_coef_out != nullptr && !bn) return kErrBadArg;
+  if ((c.bn_dgamma != nullptr) != (c.bn_dbeta != nullptr) || (c.bn_dgamma != nullptr && c.bn_coef_out == nullptr)) return kErrBadArg;
+  if ((c.in.scale != nullptr) != (c.in.shift != nullptr)) return kErrBadArg;
+  if ((c.dyx.y != nullptr) != (c.dyx.coef != nullptr) || (c.dyx.y != nullptr) != (c.dyx.gy_out != nullptr)) return kErrBadArg;
+  if (bn && (!f.y || !f.mean || !f.invstd || !f.gamma || !f.beta)) return kErrBadArg;
+  ConvGeom gw, gd;
+  if (conv_geom(gw, s.kind, 0, s.B, s.H, s.W, s.Ci, s.Co, s.k, s.stride, s.pad, s.out_pad)) return kErrBadArg;
+  if (conv_geom(gd, s.kind, 2, s.B, s.H, s.W, s.Ci, s.Co, s.k, s.stride, s.pad, s.out_pad)) return kErrBadArg;
+  // the two GEMMs run concurrently: each gets its own half of the workspace
+  const size_t half_bytes = (c.ws_bytes / 2) & ~(size_t)255, half_floats = half_bytes / sizeof(float);
+  float* ws_d = c.ws + half_floats;
+  if (c.wino_filters != nullptr &&
+      !ctvae_conv_wino_filter_floats(s.kind, s.B, s.H, s.W, s.Ci, s.Co, s.k, s.stride, s.pad, s.out_pad, half_bytes))
+    return kErrBadArg;
   if (bn) {
-    const int rows = tapgemm_bnb_rows(gd, half_floats);
-    if (rows <= 0 || rows != bn_part_rows || (img_dgrad_supported(gd) && mask != nullptr)) {
-      pair_ctx() = nullptr;
-      return kErrBadArg;
-    }
+    const int rows = tapgemm_bnb_rows(gd, half_floats, true);
+    if (rows <= 0 || rows != c.bn_part_rows || (img_dgrad_supported(gd) && c.mask != nullptr)) return kErrBadArg;
   }
+  PairCtx ctx;
   {   // how much of the chip the data gradient fills on its own: the weight gradient that shares its launch is sized to match
     TapGemmPlan pl;
-    tapgemm_plan(gd, half_floats, pl);
+    tapgemm_plan(gd, half_floats, pl, true);
     ctx.dgrad_wgs = (long)pl.mtiles * pl.ntiles * gd.ncls * (pl.splitk > 1 ? pl.splitk : 1);
     int kmax = 0;
-    for (int c = 0; c < gd.ncls; ++c) kmax = gd.ntaps[c] * gd.gC / KC > kmax ? gd.ntaps[c] * gd.gC / KC : kmax;
+    for (int cl = 0; cl < gd.ncls; ++cl) kmax = gd.ntaps[cl] * gd.gC / KC > kmax ? gd.ntaps[cl] * gd.gC / KC : kmax;
     ctx.dgrad_chunks = pl.splitk > 1 ? (kmax + pl.splitk - 1) / pl.splitk : kmax;
   }
-  const InXform xf{in_scale, in_shift, in_act};
-  DyXform dyx{dy_bn_y, dy_bn_coef, gy_out, dy_bn_act};
-  dyx.rc = recompute;
   int rc;
-  const bool img_fused = bn && bn_act != ACT_TANH && x == bn_y && in_scale != nullptr && in_act == bn_act && mask == nullptr &&
-                         dy_bn_y == nullptr && img_conv_supported(gw) && img_dgrad_supported(gd) &&
+  const bool img_fused = bn && f.act != ACT_TANH && c.x == f.y && c.in.scale != nullptr && c.in.act == f.act && c.mask == nullptr &&
+                         c.dyx.y == nullptr && img_conv_supported(gw) && img_dgrad_supported(gd) &&
                          img_backward_fused_ws_floats(gd) <= half_floats;
-  if ((no_dx && !img_fused) || (recompute != nullptr && !upconv_wgrad_supported(gw))) {   // only the kernels that can do without
-    pair_ctx() = nullptr;
-    return kErrBadArg;
-  }
+  // only the kernels that can do without
+  if ((c.no_dx && !img_fused) || (recompute != nullptr && !upconv_wgrad_supported(gw))) return kErrBadArg;
   if (img_fused) {
     // picture-side conv behind BatchNorm + activation (final_layer.1-3): the data gradient's pass over y also forms the
     // weight gradient (image.hip img_bwd_fused_kernel) -- x of the weight gradient is act(BN(y)), which that pass computes
     float *part = nullptr, *pb = nullptr;
     int np = 0;
-    const BnBwdFuse f{bn_y, bn_mean, bn_invstd, bn_gamma, bn_beta, bn_act, bn_part};
-    rc = launch_img_backward_fused(gd, dy, w, dx, &f, ws, &part, &pb, &np, dbias != nullptr, st);
-    if (!rc) rc = wgrad_finish_slabs(part, dw, 9L * 32 * 3, np, pb, dbias, 3L, accumulate, st);
+    rc = launch_img_backward_fused(gd, c.dy, c.w, c.dx, &f, c.ws, &part, &pb, &np, c.dbias != nullptr, st);
+    if (!rc) rc = wgrad_finish_slabs(part, c.dw, 9L * 32 * 3, np, pb, c.dbias, 3L, c.accumulate, st, &ctx);
   } else {
     // (a finishing launch that carries the BatchNorm finalize of the layer below stays in the chain, without the reduction:
     // deferring it too measured 1.615 vs 1.611 ms, VanillaVAE)
-    float* wws = bn_coef_out == nullptr ? defer_wgrad_ws(ws, half_floats) : ws;
-    rc = launch_wgrad(gw, x, dy, dw, dbias, wws, half_bytes, accumulate, st, &xf, &dyx);
+    float* wws = c.bn_coef_out == nullptr ? defer_wgrad_ws(c.ws, half_floats) : c.ws;
+    rc = launch_wgrad(gw, c.x, c.dy, c.dw, c.dbias, wws, half_bytes, c.accumulate, st, &c.in, &c.dyx, &ctx);
     defer_wgrad_done();
     if (!rc) {
-    const WinoFilters wf{wino_filters, nullptr};
-    const BnBwdFuse f{bn_y, bn_mean, bn_invstd, bn_gamma, bn_beta, bn_act, bn_part};
-    // dy_bn_*: dy was g_a of the BatchNorm behind this layer; the weight-gradient kernel left g_y in gy_out for the data gradient
-      SplitKRaw raw{dx_slices, 0, g_lazy_pixel_major};
-      g_lazy_pixel_major = 0;
-      rc = launch_tapgemm(gd, gy_out != nullptr ? gy_out : dy, w, nullptr, nullptr, mask, mask_act, dx, ACT_NONE, nullptr, ws_d,
-                          half_floats, st, bn ? &f : nullptr, nullptr, &wf, dx_slices != nullptr ? &raw : nullptr);
-      if (!rc && dx_slices != nullptr && raw.splitk <= 1) rc = kErrBadArg;   // the caller asked ctvae_conv_backward_lazy_slices first
+      const WinoFilters wf{c.wino_filters, nullptr};
+      // dyx: dy was g_a of the BatchNorm behind this layer; the weight-gradient kernel left g_y in gy_out for the data gradient
+      SplitKRaw raw{c.dx_slices, 0, c.slices_pixel_major};
+      rc = launch_tapgemm(gd, c.dyx.gy_out != nullptr ? c.dyx.gy_out : c.dy, c.w, nullptr, nullptr, c.mask, c.mask_act, c.dx, ACT_NONE,
+                          nullptr, ws_d, half_floats, st, bn ? &f : nullptr, nullptr, &wf, c.dx_slices != nullptr ? &raw : nullptr, 0,
+                          &ctx);
+      if (!rc && c.dx_slices != nullptr && raw.splitk <= 1) rc = kErrBadArg;   // the caller asked ctvae_conv_backward_lazy_slices first
     }
   }
-  pair_ctx() = nullptr;
   if (rc) return rc;
-  if (bn_coef_out != nullptr) {   // the finalize of the BatchNorm below rides in the finishing launch
+  if (c.bn_coef_out != nullptr) {   // the finalize of the BatchNorm below rides in the finishing launch
     ctx.haveBF = true;
-    ctx.bf = BnFinJob{bn_part, bn_part_rows, Ci, (float)((long)B * H * W), bn_gamma, bn_mean, bn_invstd, bn_beta, bn_coef_out,
-                      bn_dgamma, bn_dbeta, bn_accumulate};
+    ctx.bf = BnFinJob{f.part, c.bn_part_rows, s.Ci, (float)((long)s.B * s.H * s.W), f.gamma, f.mean, f.invstd, f.beta, c.bn_coef_out,
+                      c.bn_dgamma, c.bn_dbeta, c.bn_accumulate};
   }
   return pair_flush(ctx, st);
 }
@@ -580,10 +566,17 @@ int ctvae_conv_backward(int kind, const float* x, const float* dy, const float* 
                         const float* in_scale, const float* in_shift, int in_act,
                         const float* dy_bn_y, const float* dy_bn_coef, int dy_bn_act, float* gy_out, float* ws, size_t ws_bytes,
                         void* stream) {
-  return conv_backward_impl(kind, x, dy, w, dw, dbias, dx, B, H, W, Ci, Co, k, stride, pad, out_pad, accumulate, mask, mask_act,
-                            wino_filters, bn_y, bn_mean, bn_invstd, bn_gamma, bn_beta, bn_act, bn_part, bn_part_rows, bn_coef_out,
-                            bn_dgamma, bn_dbeta, bn_accumulate, in_scale, in_shift, in_act, dy_bn_y, dy_bn_coef, dy_bn_act, gy_out, ws,
-                            ws_bytes, stream, nullptr);
+  ConvBackwardCall c{};
+  c.s = ConvShape{kind, B, H, W, Ci, Co, k, stride, pad, out_pad};
+  c.x = x; c.dy = dy; c.w = w; c.dw = dw; c.dbias = dbias; c.dx = dx; c.accumulate = accumulate;
+  c.mask = mask; c.mask_act = mask_act; c.wino_filters = wino_filters;
+  c.bn = BnBwdFuse{bn_y, bn_mean, bn_invstd, bn_gamma, bn_beta, bn_act, bn_part};
+  c.bn_part_rows = bn_part_rows; c.bn_coef_out = bn_coef_out;
+  c.bn_dgamma = bn_dgamma; c.bn_dbeta = bn_dbeta; c.bn_accumulate = bn_accumulate;
+  c.in = InXform{in_scale, in_shift, in_act};
+  c.dyx = DyXform{dy_bn_y, dy_bn_coef, gy_out, dy_bn_act};
+  c.ws = ws; c.ws_bytes = ws_bytes;
+  return conv_backward_impl(c, (hipStream_t)stream);
 }
 
 int ctvae_conv_backward_nodx(int kind, const float* x, const float* dy, const float* w, float* dw, float* dbias, int B, int H,
@@ -592,11 +585,16 @@ int ctvae_conv_backward_nodx(int kind, const float* x, const float* dy, const fl
                              float* bn_part, int bn_part_rows, float* bn_coef_out, float* bn_dgamma, float* bn_dbeta,
                              int bn_accumulate, const float* in_scale, const float* in_shift, int in_act, float* ws, size_t ws_bytes,
                              void* stream) {
-  g_no_dx = 1;
-  return conv_backward_impl(kind, x, dy, w, dw, dbias, nullptr, B, H, W, Ci, Co, k, stride, pad, out_pad, accumulate, nullptr, 0,
-                            nullptr, bn_y, bn_mean, bn_invstd, bn_gamma, bn_beta, bn_act, bn_part, bn_part_rows, bn_coef_out,
-                            bn_dgamma, bn_dbeta, bn_accumulate, in_scale, in_shift, in_act, nullptr, nullptr, 0, nullptr, ws, ws_bytes,
-                            stream, nullptr);
+  ConvBackwardCall c{};
+  c.s = ConvShape{kind, B, H, W, Ci, Co, k, stride, pad, out_pad};
+  c.x = x; c.dy = dy; c.w = w; c.dw = dw; c.dbias = dbias; c.accumulate = accumulate;
+  c.bn = BnBwdFuse{bn_y, bn_mean, bn_invstd, bn_gamma, bn_beta, bn_act, bn_part};
+  c.bn_part_rows = bn_part_rows; c.bn_coef_out = bn_coef_out;
+  c.bn_dgamma = bn_dgamma; c.bn_dbeta = bn_dbeta; c.bn_accumulate = bn_accumulate;
+  c.in = InXform{in_scale, in_shift, in_act};
+  c.ws = ws; c.ws_bytes = ws_bytes;
+  c.no_dx = true;
+  return conv_backward_impl(c, (hipStream_t)stream);
 }
 
 int ctvae_conv_recompute_supported(int kind, int B, int H, int W, int Ci, int Co, int k, int stride, int pad, int out_pad, int kind2,
@@ -620,11 +618,17 @@ int ctvae_conv_backward_recompute(int kind, const float* x, const float* g_pre, 
   DyRecompute rc{g_pre, w2, {}, {}, {}};
   if (conv_geom(g, kind, 0, B, H, W, Ci, Co, k, stride, pad, out_pad)) return kErrBadArg;
   if (!recompute_geom(g, kind2, Co2, k2, stride2, pad2, out_pad2, &rc)) return kErrBadArg;
-  g_recompute = &rc;
-  return conv_backward_impl(kind, x, nullptr, w, dw, dbias, dx, B, H, W, Ci, Co, k, stride, pad, out_pad, accumulate, nullptr, 0,
-                            nullptr, bn_y, bn_mean, bn_invstd, bn_gamma, bn_beta, bn_act, bn_part, bn_part_rows, bn_coef_out,
-                            bn_dgamma, bn_dbeta, bn_accumulate, in_scale, in_shift, in_act, dy_bn_y, dy_bn_coef, dy_bn_act, gy_out, ws,
-                            ws_bytes, stream, nullptr);
+  ConvBackwardCall c{};
+  c.s = ConvShape{kind, B, H, W, Ci, Co, k, stride, pad, out_pad};
+  c.x = x; c.w = w; c.dw = dw; c.dbias = dbias; c.dx = dx; c.accumulate = accumulate;
+  c.bn = BnBwdFuse{bn_y, bn_mean, bn_invstd, bn_gamma, bn_beta, bn_act, bn_part};
+  c.bn_part_rows = bn_part_rows; c.bn_coef_out = bn_coef_out;
+  c.bn_dgamma = bn_dgamma; c.bn_dbeta = bn_dbeta; c.bn_accumulate = bn_accumulate;
+  c.in = InXform{in_scale, in_shift, in_act};
+  c.dyx = DyXform{dy_bn_y, dy_bn_coef, gy_out, dy_bn_act};
+  c.dyx.rc = &rc;
+  c.ws = ws; c.ws_bytes = ws_bytes;
+  return conv_backward_impl(c, (hipStream_t)stream);
 }
 
 int ctvae_conv_wgrad_recompute(int kind, const float* x, const float* g_pre, const float* w2, float* dw, float* dbias, int B, int H,
@@ -654,11 +658,8 @@ int ctvae_conv_backward_lazy_slices(int kind, int B, int H, int W, int Ci, int C
   if (conv_geom(g, kind, 2, B, H, W, Ci, Co, k, stride, pad, out_pad)) return 0;
   const size_t half_floats = ((ws_bytes / 2) & ~(size_t)255) / sizeof(float);
   if (img_dgrad_supported(g) || (wino_enabled() && wino_supported(g, half_floats))) return 0;
-  PairCtx ctx;                      // plan as ctvae_conv_backward does
-  pair_ctx() = &ctx;
   TapGemmPlan pl;
-  tapgemm_plan(g, half_floats, pl);
-  pair_ctx() = nullptr;
+  tapgemm_plan(g, half_floats, pl, true);   // plan as ctvae_conv_backward does
   const long Mc = (long)g.B * g.Qh * g.Qw;
   if (pl.thin || pl.splitk <= 1) return 0;
   if (for_bn && (Mc % 4 != 0 || !bn_fused_ok(B * H * W, Ci))) return 0;   // channel-major slices for the BatchNorm's channel owners
@@ -670,10 +671,13 @@ int ctvae_conv_backward_lazy(int kind, const float* x, const float* dy, const fl
                              const float* in_scale, const float* in_shift, int in_act, int pixel_major, float* ws, size_t ws_bytes,
                              void* stream) {
   if (!dx_slices) return kErrBadArg;
-  g_lazy_pixel_major = pixel_major;
-  return conv_backward_impl(kind, x, dy, w, dw, dbias, nullptr, B, H, W, Ci, Co, k, stride, pad, out_pad, accumulate, nullptr, 0,
-                            nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 0, nullptr, 0, nullptr, nullptr, nullptr, 0, in_scale,
-                            in_shift, in_act, nullptr, nullptr, 0, nullptr, ws, ws_bytes, stream, dx_slices);
+  ConvBackwardCall c{};
+  c.s = ConvShape{kind, B, H, W, Ci, Co, k, stride, pad, out_pad};
+  c.x = x; c.dy = dy; c.w = w; c.dw = dw; c.dbias = dbias; c.accumulate = accumulate;
+  c.in = InXform{in_scale, in_shift, in_act};
+  c.ws = ws; c.ws_bytes = ws_bytes;
+  c.dx_slices = dx_slices; c.slices_pixel_major = pixel_major;
+  return conv_backward_impl(c, (hipStream_t)stream);
 }
 
 int ctvae_bn_backward_fused(const float* g_a_slices, int slices, int kind, int B, int H, int W, int Ci, int Co, int k, int stride,
@@ -777,7 +781,7 @@ int ctvae_conv_forward_lazy_slices(int kind, int B, int H, int W, int Ci, int Co
   const size_t wsf = ws_bytes / sizeof(float);
   if (img_enc_supported(g) || img_conv_supported(g) || upconv_wgrad_supported(g) || (wino_enabled() && wino_supported(g, wsf))) return 0;
   TapGemmPlan pl;
-  tapgemm_plan(g, wsf, pl);
+  tapgemm_plan(g, wsf, pl, false);
   return (pl.thin || pl.splitk <= 1) ? 0 : pl.splitk;
 }
 

@@ -1,13 +1,10 @@
-// Paired backward launch (ctvae_conv_backward): while a PairCtx is installed for the calling thread, the data-gradient
+// Paired backward launch (ctvae_conv_backward): handed the call's PairCtx (their `pc` argument), the data-gradient
 // launcher (tapgemm_fast.hip, 64x64 or 128x32 pipelined tile kernel) and the weight-gradient launcher (wgrad.hip, lean 64x64
 // kernel or plain-load 128x32 kernel) RECORD their main launch instead of issuing it, and every finishing launch behind them (split-K finish, slab
 // reduction) is queued; pair_flush() then issues ONE conv_bwd_pair_kernel for both GEMMs (or the single recorded kernel,
 // if only one side took its pairable path) followed by the queued launches in order.  Launches of any other path are
 // issued immediately as usual -- the two GEMMs are independent and work in disjoint halves of the workspace.
 #pragma once
-#include <functional>
-#include <vector>
-
 #include "finish.hpp"
 #include "tapgemm.hpp"
 #include "wgrad_fast.hpp"
@@ -37,10 +34,13 @@ struct PairCtx {
   // finishing launch when there is one, else pair_flush() issues it on its own
   bool haveBF = false;
   BnFinJob bf;
-  std::vector<std::function<int()>> later;
 };
 
-PairCtx*& pair_ctx();                                    // tapgemm_fast.hip (thread-local, null = not pairing)
+// wgrad.hip: pc = the paired call these belong to (null = not pairing: everything is issued at once)
+int launch_wgrad(const ConvGeom& g, const float* X, const float* dY, float* dW, float* dbias, float* ws, size_t ws_bytes,
+                 int accumulate, hipStream_t st, const InXform* xf = nullptr, const DyXform* dyx = nullptr, PairCtx* pc = nullptr);
+int wgrad_finish_slabs(const float* part, float* dW, long n, int nparts, const float* pbias, float* dbias, long nb, int accumulate,
+                       hipStream_t st, PairCtx* pc);
 int pair_flush(PairCtx& c, hipStream_t st);              // tapgemm_fast.hip
 int launch_wgrad_recorded(const PairCtx& c, hipStream_t st);        // wgrad.hip: the recorded weight-gradient kernel on its own
 int launch_finish_recorded(const PairCtx& c, hipStream_t st);       // wgrad.hip: recorded reduction (+ split-K finish) in one launch

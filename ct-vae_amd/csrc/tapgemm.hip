@@ -549,7 +549,7 @@ int launch_thin_forward(const ConvGeom& g, const float* G, const float* W, const
                         const InXform* xf);
 
 // tile shape and split-K factor a launch will use (mirrored by the BN-statistics consumers)
-void tapgemm_plan(const ConvGeom& g, size_t ws_floats, TapGemmPlan& p) {
+void tapgemm_plan(const ConvGeom& g, size_t ws_floats, TapGemmPlan& p, bool paired) {
   const int Mc = g.B * g.Qh * g.Qw, N = g.sC;
   p.thin = 0;
   if (img_enc_supported(g)) {   // picture-side stride-2 conv: dedicated kernel, one statistics row per workgroup
@@ -600,7 +600,7 @@ void tapgemm_plan(const ConvGeom& g, size_t ws_floats, TapGemmPlan& p) {
   // sums in its epilogue (no bn_bwd_partial pass)
   constexpr int pair_target = 256;   // sweep, ms per step: 768 1.804, 512 1.798, 384 1.800, 256 1.796, 128 1.813, no split 1.847
   constexpr int pair_maxwgs = 384;
-  const bool paired = pair_ctx() != nullptr && g.wT != 0;
+  paired = paired && g.wT != 0;
   const int tgt = paired ? pair_target : sk_target, maxw = paired ? pair_maxwgs : sk_maxwgs;
   // paired with a reduction of fewer than 16 chunks (K < 512: the Linear heads' data gradient): splitting saves ~1 us of a
   // launch the weight gradient fills anyway and would cost the fused BatchNorm-backward sums of the layer below
@@ -623,10 +623,10 @@ int launch_img_dgrad(const ConvGeom& g, const float* dY, const float* W, float* 
 
 // rows of the fused BN-backward partial table a dgrad launch of this geometry writes (0: this configuration cannot
 // fuse -- split-K keeps its epilogue in splitk_finish_kernel, the thin path has none)
-int tapgemm_bnb_rows(const ConvGeom& g, size_t ws_floats) {
+int tapgemm_bnb_rows(const ConvGeom& g, size_t ws_floats, bool paired) {
   if (img_dgrad_supported(g)) return img_dgrad_rows(g);
   TapGemmPlan plan;
-  tapgemm_plan(g, ws_floats, plan);
+  tapgemm_plan(g, ws_floats, plan, paired);
   if (plan.thin || plan.splitk > 1) return 0;
   return plan.bn_parts;
 }
@@ -642,13 +642,14 @@ bool out_pix_supported(const ConvGeom& g, size_t ws_floats, int out_pix) {
   if (out_pix <= 1 || g.os != 1 || g.ncls != 1 || g.ntaps[0] != 1 || g.sH * g.sW != 1 || g.sC % out_pix != 0 || g.wT != 0) return false;
   if ((g.gC % KC) != 0 || (g.sC % 4) != 0) return false;
   TapGemmPlan plan;
-  tapgemm_plan(g, ws_floats, plan);
+  tapgemm_plan(g, ws_floats, plan, false);
   return !plan.thin && plan.BM != 0 && plan.splitk <= 1;
 }
 
 int launch_tapgemm(const ConvGeom& g, const float* G, const float* W, const float* bias, const float* add,
                    const float* mask, int mask_act, float* S, int act, float* bn_part, float* ws, size_t ws_floats,
-                   hipStream_t st, const BnBwdFuse* bnb, const InXform* xf, const WinoFilters* wf, SplitKRaw* raw, int out_pix) {
+                   hipStream_t st, const BnBwdFuse* bnb, const InXform* xf, const WinoFilters* wf, SplitKRaw* raw, int out_pix,
+                   PairCtx* pc) {
   if (raw != nullptr) raw->splitk = 0;
   if (out_pix > 1) {   // TapGemmArgs::out_pix: the vector tile kernel's plain epilogue only (see out_pix_supported)
     if (!out_pix_supported(g, ws != nullptr ? ws_floats : 0, out_pix) || add != nullptr || mask != nullptr || bn_part != nullptr ||
@@ -708,7 +709,7 @@ int launch_tapgemm(const ConvGeom& g, const float* G, const float* W, const floa
   }
   // tile choice: N<=32 -> 128x32 (4x1 waves); big problems -> 128x64; small M -> 64x64 (+ split-K when the grid is small)
   TapGemmPlan plan;
-  tapgemm_plan(g, ws != nullptr ? ws_floats : 0, plan);
+  tapgemm_plan(g, ws != nullptr ? ws_floats : 0, plan, pc != nullptr);
   if (a.bnb_part != nullptr && (plan.thin || plan.splitk > 1)) return kErrBadArg;   // see tapgemm_bnb_rows()
   // transform on load: the thin kernels and the vector tile kernel in forward orientation (tapgemm_fast_body.inc XF)
   if (xf != nullptr && xf->scale != nullptr && !plan.thin && !(avec && bvec && !wt)) return kErrBadArg;
@@ -735,7 +736,7 @@ int launch_tapgemm(const ConvGeom& g, const float* G, const float* W, const floa
     const bool db = (long)plan.mtiles * plan.ntiles * g.ncls * plan.splitk <= pf_wgs;
     // measured (bench.py, VanillaVAE bs=256): pipelined double-buffer loop 2.35 ms vs 2.37 (plain double buffer) vs 2.42
     // when the large grids use it too (LDS doubling costs them occupancy)
-    rc = launch_tapgemm_fast(a, plan, db ? 3 : 0, st);
+    rc = launch_tapgemm_fast(a, plan, db ? 3 : 0, st, pc);
   }
   if (rc || plan.splitk <= 1) return rc;
   if (raw_T) {
@@ -746,7 +747,7 @@ int launch_tapgemm(const ConvGeom& g, const float* G, const float* W, const floa
   long blocks = (n4 + 255) / 256;
   if (blocks > 2048) blocks = 2048;
   const SplitKJob job{ws, plan.splitk, n, bias, add, mask, mask_act, act, S, n4, a.N, (int)blocks};
-  if (PairCtx* pc = pair_ctx()) {   // ctvae_conv_backward: behind the paired main launch (pair_flush)
+  if (pc != nullptr) {   // ctvae_conv_backward: behind the paired main launch (pair_flush)
     pc->haveSK = true;
     pc->sk = job;
     pc->bytesSK = 4.0 * (double)(plan.splitk + 1) * n;

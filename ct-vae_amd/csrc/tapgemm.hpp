@@ -66,6 +66,16 @@ __device__ __forceinline__ void decode_m_fast(const TapGemmArgs& a, int m, int& 
   }
 }
 
-int launch_tapgemm_fast(const TapGemmArgs& a, const TapGemmPlan& plan, int pf, hipStream_t st);
+struct PairCtx;   // pair.hpp: the paired backward call a launch belongs to (null = not pairing)
+
+// tapgemm.hip.  paired: the launch shares ctvae_conv_backward's pair launch (only a data gradient, g.wT != 0, plans differently)
+void tapgemm_plan(const ConvGeom& g, size_t ws_floats, TapGemmPlan& p, bool paired);
+int tapgemm_bnb_rows(const ConvGeom& g, size_t ws_floats, bool paired);
+int launch_tapgemm(const ConvGeom& g, const float* G, const float* W, const float* bias, const float* add,
+                   const float* mask, int mask_act, float* S, int act, float* bn_part, float* ws, size_t ws_floats,
+                   hipStream_t st, const BnBwdFuse* bnb = nullptr, const InXform* xf = nullptr,
+                   const WinoFilters* wf = nullptr, SplitKRaw* raw = nullptr, int out_pix = 0, PairCtx* pc = nullptr);
+// tapgemm_fast.hip
+int launch_tapgemm_fast(const TapGemmArgs& a, const TapGemmPlan& plan, int pf, hipStream_t st, PairCtx* pc);
 
 }  // namespace ctvae

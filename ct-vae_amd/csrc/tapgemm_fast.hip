@@ -132,7 +132,7 @@ __global__ __launch_bounds__(256) void conv_bwd_pair_kernel(const TapGemmArgs a,
 }
 
 template <int WM, int WN, int TM, int TN>
-static int launch_fast_cfg(const TapGemmArgs& a, int pf, hipStream_t st) {
+static int launch_fast_cfg(const TapGemmArgs& a, int pf, hipStream_t st, PairCtx* pc) {
   constexpr int BM = WM * TM * 32, BN = WN * TN * 32;
   TapGemmArgs args = a;
   args.mtiles = ceil_div(a.Mc, BM);
@@ -174,7 +174,6 @@ static int launch_fast_cfg(const TapGemmArgs& a, int pf, hipStream_t st) {
   double macs = 0;
   for (int c = 0; c < a.g.ncls; ++c) macs += (double)a.Mc * a.N * a.g.ntaps[c] * a.g.gC;
   if constexpr (TM == 1 && TN == 1) {   // 64 x 64 and 128 x 32 tiles
-    PairCtx* pc = pair_ctx();
     if (pc != nullptr && wt && pf == 3 && !pc->haveA) {   // ctvae_conv_backward: issued by pair_flush()
       pc->haveA = true;
       pc->wmA = WM;
@@ -205,11 +204,6 @@ static int launch_fast_cfg(const TapGemmArgs& a, int pf, hipStream_t st) {
   }
   CTVAE_LAUNCH_CHECK();
   return 0;
-}
-
-PairCtx*& pair_ctx() {
-  static thread_local PairCtx* ctx = nullptr;
-  return ctx;
 }
 
 int pair_flush(PairCtx& c, hipStream_t st) {
@@ -255,17 +249,13 @@ int pair_flush(PairCtx& c, hipStream_t st) {
       if (rc) return rc;
     }
   }
-  for (auto& f : c.later) {
-    const int rc = f();
-    if (rc) return rc;
-  }
   return 0;
 }
 
-int launch_tapgemm_fast(const TapGemmArgs& a, const TapGemmPlan& plan, int pf, hipStream_t st) {
-  if (plan.BN == 32) return launch_fast_cfg<4, 1, 1, 1>(a, pf, st);
-  if (plan.BM == 128) return launch_fast_cfg<2, 2, 2, 1>(a, pf, st);
-  return launch_fast_cfg<2, 2, 1, 1>(a, pf, st);
+int launch_tapgemm_fast(const TapGemmArgs& a, const TapGemmPlan& plan, int pf, hipStream_t st, PairCtx* pc) {
+  if (plan.BN == 32) return launch_fast_cfg<4, 1, 1, 1>(a, pf, st, pc);
+  if (plan.BM == 128) return launch_fast_cfg<2, 2, 2, 1>(a, pf, st, pc);
+  return launch_fast_cfg<2, 2, 1, 1>(a, pf, st, pc);
 }
 
 }  // namespace ctvae

@@ -8,6 +8,8 @@
 // ("split-M"), streams 32-pixel chunks of im2col(X) and dY through LDS and accumulates with
 // v_mfma_f32_32x32x2_f32; slices are combined by a second, deterministic pass (no float atomics:
 // bitwise reproducible, and atomics would be bound at ~1.3 TB/s on gfx950).
+#include <vector>
+
 #include "common.hpp"
 #include "prof.hpp"
 #include "finish.hpp"
@@ -309,9 +311,9 @@ static bool defer_record(const float* p1, float* d1, long n1, int S1, long st1, 
 // Slab reduction behind a weight-gradient kernel: issued now, or -- inside ctvae_conv_backward -- recorded so that it shares
 // the call's ONE finishing launch with the data gradient's split-K sum and the BatchNorm-backward finalize (pair.hpp)
 static int finish_reduce(const float* p1, float* d1, long n1, int S1, long st1, const float* p2, float* d2, long n2, int S2, long st2,
-                         int accumulate, hipStream_t st) {
+                         int accumulate, hipStream_t st, PairCtx* pc) {
   if (defer_record(p1, d1, n1, S1, st1, p2, d2, n2, S2, st2, accumulate, st)) return 0;
-  if (PairCtx* pc = pair_ctx(); pc != nullptr && !pc->haveRed) {
+  if (pc != nullptr && !pc->haveRed) {
     pc->j1 = ReduceJob{p1, d1, n1, S1, st1, 0, 0};
     pc->j2 = (p2 != nullptr && d2 != nullptr) ? ReduceJob{p2, d2, n2, S2, st2, 0, 0} : ReduceJob{nullptr, nullptr, 0, 0, 0, 0, 0};
     pc->nb1 = reduce_job_blocks(pc->j1);
@@ -330,8 +332,8 @@ static int finish_reduce(const float* p1, float* d1, long n1, int S1, long st1, 
 
 // for a kernel outside this file that produced weight-gradient slabs (image.hip img_bwd_fused_kernel)
 int wgrad_finish_slabs(const float* part, float* dW, long n, int nparts, const float* pbias, float* dbias, long nb, int accumulate,
-                       hipStream_t st) {
-  return finish_reduce(part, dW, n, nparts, n, pbias, dbias, nb, nparts, nb, accumulate, st);
+                       hipStream_t st, PairCtx* pc) {
+  return finish_reduce(part, dW, n, nparts, n, pbias, dbias, nb, nparts, nb, accumulate, st, pc);
 }
 
 size_t wgrad_workspace_floats(const ConvGeom& g, int S) {
@@ -381,7 +383,7 @@ int launch_wino_wgrad(const ConvGeom& g, const float* X, const float* dY, float*
 bool wino_enabled();
 
 int launch_wgrad(const ConvGeom& g, const float* X, const float* dY, float* dW, float* dbias, float* ws,
-                 size_t ws_bytes, int accumulate, hipStream_t st, const InXform* xf, const DyXform* dyx) {
+                 size_t ws_bytes, int accumulate, hipStream_t st, const InXform* xf, const DyXform* dyx, PairCtx* pc) {
   // 3x3 / stride 1 / same-padding layers: Winograd F(3x3,2x2), see wino.hip
   if ((xf == nullptr || xf->scale == nullptr) && (dyx == nullptr || dyx->y == nullptr) && wino_enabled() &&
       wino_wgrad_supported(g, ws_bytes / sizeof(float), nullptr)) {
@@ -390,7 +392,7 @@ int launch_wgrad(const ConvGeom& g, const float* X, const float* dY, float* dW, 
     int rc = launch_wino_wgrad(g, X, dY, ws, ws_bytes / sizeof(float), &np, dbias != nullptr, &pb, st);
     if (rc) return rc;
     const long n = 9L * g.gC * g.sC;
-    return finish_reduce(ws, dW, n, np, n, pb, dbias, (long)g.sC, np, (long)g.sC, accumulate, st);
+    return finish_reduce(ws, dW, n, np, n, pb, dbias, (long)g.sC, np, (long)g.sC, accumulate, st, pc);
   }
   const bool up = upconv_wgrad_supported(g) && ws_bytes / sizeof(float) >= (size_t)512 * (9 * 32 * 32 + 32);
   const bool enc = img_enc_supported(g) && (xf == nullptr || xf->scale == nullptr) &&
@@ -405,7 +407,7 @@ int launch_wgrad(const ConvGeom& g, const float* X, const float* dY, float* dW, 
     int rc = launch_upconv_wgrad(g, X, dY, ws, &part, &pb, &np, dbias != nullptr, st, dyx, xf);
     if (rc) return rc;
     const long n = 9L * 32 * 32;
-    return finish_reduce(part, dW, n, np, n, pb, dbias, 32L, np, 32L, accumulate, st);
+    return finish_reduce(part, dW, n, np, n, pb, dbias, 32L, np, 32L, accumulate, st, pc);
   }
   if (enc) {
     float *part = nullptr, *pb = nullptr;
@@ -413,7 +415,7 @@ int launch_wgrad(const ConvGeom& g, const float* X, const float* dY, float* dW, 
     int rc = launch_img_enc_wgrad(g, X, dY, ws, &part, &pb, &np, dbias != nullptr, st, dyx);
     if (rc) return rc;
     const long n = 27L * 32;
-    return finish_reduce(part, dW, n, np, n, pb, dbias, 32L, np, 32L, accumulate, st);
+    return finish_reduce(part, dW, n, np, n, pb, dbias, 32L, np, 32L, accumulate, st, pc);
   }
   const bool thin = thin_wgrad_supported(g) && thin_wgrad_workspace_floats(g) <= ws_bytes / sizeof(float);
   const bool has_xf = xf != nullptr && xf->scale != nullptr;
@@ -428,7 +430,7 @@ int launch_wgrad(const ConvGeom& g, const float* X, const float* dY, float* dW, 
     int taps = 0;
     for (int c = 0; c < g.ncls; ++c) taps += g.ntaps[c];
     const long n = (long)taps * g.gC * g.sC;
-    return finish_reduce(part, dW, n, nw, n, pb, dbias, (long)g.sC, nb, (long)g.sC, accumulate, st);
+    return finish_reduce(part, dW, n, nw, n, pb, dbias, (long)g.sC, nb, (long)g.sC, accumulate, st, pc);
   }
   WgradArgs a{};
   a.g = g;
@@ -464,10 +466,9 @@ int launch_wgrad(const ConvGeom& g, const float* X, const float* dY, float* dW, 
   // The narrow layers' 128 x 32 plain-load kernel shares the launch only next to a data gradient of less than one round of
   // workgroups (VanillaVAE decoder.3 at bs = 64: 0.733 -> 0.712 ms with encoder.1's pair); beside the 1024 workgroups of the
   // bs = 256 data gradient the pair is two rounds and lost, 1.485 -> 1.490 ms
-  const PairCtx* pcw = pair_ctx();
-  const bool will_pair = pcw != nullptr && !pcw->haveB && xvec && dvec && !big &&
-                         (!narrow || (pcw->dgrad_wgs > 0 && pcw->dgrad_wgs < 1024));
-  const bool coarse = will_pair && pcw->dgrad_wgs > 0 && pcw->dgrad_wgs < 1024 && pcw->dgrad_chunks >= 12;
+  const bool will_pair = pc != nullptr && !pc->haveB && xvec && dvec && !big &&
+                         (!narrow || (pc->dgrad_wgs > 0 && pc->dgrad_wgs < 1024));
+  const bool coarse = will_pair && pc->dgrad_wgs > 0 && pc->dgrad_wgs < 1024 && pc->dgrad_chunks >= 12;
   const int S = choose_splits(g, KT, NT, ws_floats, big ? 512 : (coarse ? 768 : 1024));
   if (wgrad_workspace_floats(g, S) > ws_floats) return kErrWorkspace;
   a.S = S;
@@ -484,7 +485,7 @@ int launch_wgrad(const ConvGeom& g, const float* X, const float* dY, float* dW, 
   a.ntiles = ceil_div(a.N, NT);
   dim3 grid(kt * a.ntiles, S), block(256);
   bool recorded = false;
-  if (PairCtx* pc = pair_ctx(); will_pair) {
+  if (will_pair) {
     // ctvae_conv_backward: the lean 64x64 / plain-load 128x32 kernel shares a launch with the data-gradient kernel (pair_flush())
     auto lg2 = [](int v) { int l = 0; while ((1 << l) < v) ++l; return (1 << l) == v ? l : -1; };
     const int lw = lg2(g.Qw), lh2 = lg2(g.Qh);
@@ -537,7 +538,7 @@ int launch_wgrad(const ConvGeom& g, const float* X, const float* dY, float* dW, 
   const float* pbias = a.pbias;
   const int ncls = g.ncls, N_ = a.N;
   // deferred (ctvae_defer_*), recorded for the call's finishing launch (ctvae_conv_backward), or issued now
-  return finish_reduce(part, dW, n, S, n, dbias ? pbias : nullptr, dbias, (long)N_, S * ncls, (long)N_, accumulate, st);
+  return finish_reduce(part, dW, n, S, n, dbias ? pbias : nullptr, dbias, (long)N_, S * ncls, (long)N_, accumulate, st, pc);
 }
 
 int launch_finish_recorded(const PairCtx& c, hipStream_t st) {

@@ -453,6 +453,16 @@ def _bn_commit_args(bn_commit):
     return (bn_commit[0].data_ptr(), bn_commit[1].data_ptr(), bn_commit[2]) if bn_commit is not None else (None, None, 0)
 
 
+def _bn_rider_args(bn, part, rows, coef, bn_commit):
+    """The paired backward's BatchNorm rider: bn_y, bn_mean, bn_invstd, bn_gamma, bn_beta, bn_act of the BNLink ``bn`` below the
+    layer, its bn_part / bn_part_rows sums table, bn_coef_out and _bn_commit_args.  bn None: no rider, nothing commits."""
+    cg, cb, cacc = _bn_commit_args(bn_commit)
+    if bn is None:
+        return (None, None, None, None, None, 0, None, rows, None, None, None, cacc)
+    return (native.ptr(bn.y), native.ptr(bn.mean), native.ptr(bn.invstd), native.ptr(bn.gamma), native.ptr(bn.beta), bn.act,
+            part.data_ptr(), rows, coef.data_ptr(), cg, cb, cacc)
+
+
 def conv_wgrad_raw(x, dy, w_param, b_param, spec: ConvSpec, in_coef=None, in_act=ACT_NONE, dy_bn=None, bn_commit=None,
                    recompute=None):
     """dy_bn = (y, coef[5][Co], act, gy_out): dy is g_a of the BatchNorm behind this layer; g_y is formed on load and
@@ -531,26 +541,16 @@ def conv_backward_raw(x, dy, w_param, b_param, spec: ConvSpec, link=None, mask=N
             part = torch.empty(rows * spec.ci * 2, dtype=torch.float32, device=dy.device)
     bn = link if part is not None else None
     coef = torch.empty(7 * spec.ci, dtype=torch.float32, device=dy.device) if bn is not None else None   # the finalize rides along
-    cg, cb, cacc = _bn_commit_args(bn_commit)
-    if coef is None:
-        cg = cb = None        # no rider, nothing commits
+    rider = _bn_rider_args(bn, part, rows, coef, bn_commit)
     if recompute is not None:
         native.call("ctvae_conv_backward_recompute", g[0], x.data_ptr(), dy.data_ptr(), recompute[0].data_ptr(), w_param.data_ptr(),
-                    gw.data_ptr(), native.ptr(gb), dx.data_ptr(), *g[1:], acc,
-                    native.ptr(bn.y if bn else None), native.ptr(bn.mean if bn else None), native.ptr(bn.invstd if bn else None),
-                    native.ptr(bn.gamma if bn else None), native.ptr(bn.beta if bn else None), bn.act if bn else 0,
-                    native.ptr(part), rows, native.ptr(coef), cg, cb, cacc,
+                    gw.data_ptr(), native.ptr(gb), dx.data_ptr(), *g[1:], acc, *rider,
                     *_coef_ptrs(in_coef, spec.ci), in_act, *_dy_bn_args(dy_bn), *_conv2_args(recompute[1]),
                     ws.data_ptr(), ws.numel() * 4)
-        if bn is not None:
-            bn.publish(dx, part, rows, coef)
-        return dx
-    native.call("ctvae_conv_backward", g[0], x.data_ptr(), dy.data_ptr(), w_param.data_ptr(), gw.data_ptr(), native.ptr(gb),
-                dx.data_ptr(), *g[1:], acc, native.ptr(mask), mask_act, native.ptr(wino_filters),
-                native.ptr(bn.y if bn else None), native.ptr(bn.mean if bn else None), native.ptr(bn.invstd if bn else None),
-                native.ptr(bn.gamma if bn else None), native.ptr(bn.beta if bn else None), bn.act if bn else 0,
-                native.ptr(part), rows, native.ptr(coef), cg, cb, cacc,
-                *_coef_ptrs(in_coef, spec.ci), in_act, *_dy_bn_args(dy_bn), ws.data_ptr(), ws.numel() * 4)
+    else:
+        native.call("ctvae_conv_backward", g[0], x.data_ptr(), dy.data_ptr(), w_param.data_ptr(), gw.data_ptr(), native.ptr(gb),
+                    dx.data_ptr(), *g[1:], acc, native.ptr(mask), mask_act, native.ptr(wino_filters), *rider,
+                    *_coef_ptrs(in_coef, spec.ci), in_act, *_dy_bn_args(dy_bn), ws.data_ptr(), ws.numel() * 4)
     if bn is not None:
         bn.publish(dx, part, rows, coef)
     return dx
@@ -581,8 +581,7 @@ def conv_backward_nodx_raw(x, dy, w_param, b_param, spec: ConvSpec, link, in_coe
     part = torch.empty(rows * spec.ci * 2, dtype=torch.float32, device=dy.device)
     coef = torch.empty(7 * spec.ci, dtype=torch.float32, device=dy.device)
     native.call("ctvae_conv_backward_nodx", g[0], x.data_ptr(), dy.data_ptr(), w_param.data_ptr(), gw.data_ptr(), native.ptr(gb),
-                *g[1:], acc, link.y.data_ptr(), link.mean.data_ptr(), link.invstd.data_ptr(), link.gamma.data_ptr(),
-                link.beta.data_ptr(), link.act, part.data_ptr(), rows, coef.data_ptr(), *_bn_commit_args(bn_commit),
+                *g[1:], acc, *_bn_rider_args(link, part, rows, coef, bn_commit),
                 *_coef_ptrs(in_coef, spec.ci), in_act, ws.data_ptr(), ws.numel() * 4)
     return coef
 
