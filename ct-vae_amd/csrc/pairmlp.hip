@@ -468,14 +468,19 @@ __global__ __launch_bounds__(64 * WPB) __attribute__((amdgpu_waves_per_eu(4, 4))
 int launch_pair_mlp_forward(const float* u, const float* v, int ld, const float* w2, const float* b2, float* out, int B, int N,
                             int H, float slope, int per_sample, const int* row_of, hipStream_t st) {
   if (B <= 0 || N <= 0 || H <= 0 || ld < H) return kErrBadArg;
-  ProfScope ps((N == 64 && H % 4 == 0 && ld % 4 == 0) ? "pair_mlp_fwd64_kernel" : "pair_mlp_fwd_kernel", st, 3.0 * B * (double)N * N * H, 4.0 * B * (2.0 * N * H + (double)N * N));
-  if (N == 64 && H % 4 == 0 && ld % 4 == 0 && (reinterpret_cast<uintptr_t>(w2) & 15) == 0) {   // w2 rows are read as float4
+  auto al16 = [](const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; };
+  // the 64-node kernels read u / v rows and write out rows as float4: H, ld multiples of 4 and 16-byte aligned bases
+  const bool vec = N == 64 && H % 4 == 0 && ld % 4 == 0 && al16(u) && al16(v) && al16(out);
+  const bool blocked = vec && al16(w2);                                                       // w2 rows are read as float4
+  ProfScope ps(blocked ? "pair_mlp_fwd64b_kernel" : vec ? "pair_mlp_fwd64_kernel" : "pair_mlp_fwd_kernel", st,
+               3.0 * B * (double)N * N * H, 4.0 * B * (2.0 * N * H + (double)N * N));
+  if (blocked) {
     hipLaunchKernelGGL(pair_mlp_fwd64b_kernel, dim3(4, B), dim3(256), 0, st, u, v, w2, b2, out, H, ld, slope, per_sample ? H : 0,
                        per_sample ? 1 : 0, per_sample ? row_of : nullptr);
     CTVAE_LAUNCH_CHECK();
     return 0;
   }
-  if (N == 64 && H % 4 == 0 && ld % 4 == 0) {   // unaligned w2: the (i, 4 j) kernel
+  if (vec) {   // unaligned w2: the (i, 4 j) kernel
     hipLaunchKernelGGL(pair_mlp_fwd64_kernel, dim3(4, B), dim3(256), 0, st, u, v, w2, b2, out, H, ld, slope, per_sample ? H : 0,
                        per_sample ? 1 : 0, per_sample ? row_of : nullptr);
     CTVAE_LAUNCH_CHECK();

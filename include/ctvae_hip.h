@@ -253,7 +253,9 @@ int ctvae_bn_backward(const float* g_a, const float* beta, const float* y, int R
  * ONE launch, ct_mcq_vae.py:149-151); the partials then ARE the gradients of those rows.
  * row_of [B] (per_sample only, may be NULL = the sample's own row): the row of the w2 / b2 bank sample b uses -- the bank of
  * all discoverers is then read in place, indexed by the sample's action.
- * u / v rows have stride ld (>= H), d_u / d_v rows stride ldd: they may be column blocks of one wider GEMM output / gradient. */
+ * u / v rows have stride ld (>= H), d_u / d_v rows stride ldd: they may be column blocks of one wider GEMM output / gradient.
+ * No alignment is required: the N == 64 forward kernels that move float4s run only for H % 4 == 0, ld % 4 == 0 and 16-byte
+ * aligned u, v and out (w2 aligned or not selects between two of them); every other call takes the any-N forward kernel. */
 int ctvae_pair_mlp_forward(const float* u, const float* v, int ld, const float* w2, const float* b2, float* out, int B, int N,
                            int H, float slope, int per_sample, const int32_t* row_of, void* stream);
 int ctvae_pair_mlp_backward(const float* u, const float* v, int ld, const float* w2, const float* out, const float* g_out,

@@ -620,3 +620,194 @@ def pair_mlp_ref(u, v, w2, b2, row_of, slope, g=None):
         out.backward(d(g))
         res.update(d_u=u.grad, d_v=v.grad, d_w2=w.grad, d_b2=b.grad)
     return res
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# pair scorer, the 64-node kernels: dispatch mirror, cases, analytic float64 reference with its |.| sums, rounding chains
+# ---------------------------------------------------------------------------------------------------------------------
+FWD64B, FWD64, FWD, BWD64, BWD = ("pair_mlp_fwd64b_kernel", "pair_mlp_fwd64_kernel", "pair_mlp_fwd_kernel", "pair_mlp_bwd64_kernel",
+                                  "pair_mlp_bwd_kernel")
+SLOPE_PAIR32 = float(np.float32(SLOPE_PAIR))     # the slope as the kernels receive it: both sides see the same number
+STEP_MIN = 2.0 ** -60                            # satmath.hpp: [t > 0] = sat(t * 2^60) is exact for t <= 0 and t >= 2^-60
+
+
+def pair_kernels(N, H, ld, u_al=True, v_al=True, out_al=True, w2_al=True):
+    """(forward kernel, backward kernel or None = refused) as launch_pair_mlp_forward / _backward choose them; *_al: the pointer is
+    16-byte aligned.  Bank rows sit H floats apart, so with H % 4 == 0 every row is aligned as the bank is."""
+    vec = N == 64 and H % 4 == 0 and ld % 4 == 0 and u_al and v_al and out_al
+    fwd = (FWD64B if w2_al else FWD64) if vec else FWD
+    bwd = None if N > 64 else BWD64 if N == 64 else BWD
+    return fwd, bwd
+
+
+@dataclass(frozen=True)
+class Pair64Case:
+    id: str
+    B: int
+    N: int
+    H: int
+    fwd: str                     # the kernels the case is there to reach; the mirror and the launch log must both agree
+    bwd: Optional[str]           # None: the backward refuses (N > 64)
+    ld: int = 0                  # row stride of the buffer holding u | v (0: 2H)
+    dpad: int = 4                # d_u | d_v sit at the same columns of a buffer of row stride ldd = ld + dpad
+    ucol: int = 0                # u occupies columns ucol .. ucol + H - 1, v the H columns behind it
+    uvoff: int = 0               # the u | v buffer, the scorer bank and out start this many floats behind a 16-byte boundary
+    w2off: int = 0
+    outoff: int = 0
+    bias: bool = True            # False: b2 == NULL in the forward
+    row_of: Optional[Tuple[int, ...]] = None      # per-sample scorer rows (None: one shared scorer, row 0 of the bank)
+    G: int = 1
+
+    @property
+    def ld_(self):
+        return self.ld or 2 * self.H
+
+    @property
+    def ldd_(self):
+        return self.ld_ + self.dpad
+
+    def alignment(self):
+        """u, v, out, w2 16-byte aligned?"""
+        return ((self.uvoff + self.ucol) % 4 == 0, (self.uvoff + self.ucol + self.H) % 4 == 0, self.outoff % 4 == 0, self.w2off % 4 == 0)
+
+
+def _p64(H, **k):
+    return Pair64Case(k.pop("id", f"H{H}"), k.pop("B", 2), 64, H, k.pop("fwd", FWD64B), BWD64, **k)
+
+
+ROWS = dict(row_of=(2, 4, 2), G=5)               # a repeated row (2) and unused rows (0, 1, 3)
+PAIR64_CASES = [
+    # one partial chunk in both forwards; one live backward wave, ha lanes 4..15 and every hb lane clamped
+    _p64(4, B=1), _p64(4, id="H4-w2off", fwd=FWD64, w2off=1, B=1), _p64(4, id="H4-w2off-rows", fwd=FWD64, w2off=1, B=3, **ROWS),
+    # exactly one backward wave, half a 64b chunk, one full fwd64 chunk
+    _p64(32), _p64(32, id="H32-w2off", fwd=FWD64, w2off=1, B=1),
+    # second backward wave with 4 live ha lanes, every hb clamped
+    _p64(36, ld=2 * 36 + 8), _p64(36, id="H36-w2off", fwd=FWD64, w2off=1), _p64(36, id="H36-w2off-rows", fwd=FWD64, w2off=1, B=3, **ROWS),
+    # 64b chunk boundary / buffer swap: full, exactly full, nearly empty last chunk
+    _p64(60, B=1), _p64(64, B=1, dpad=0), _p64(68), _p64(68, id="H68-w2off", fwd=FWD64, w2off=1), _p64(68, id="H68-w2off-rows", fwd=FWD64, w2off=1, B=3, **ROWS),
+    # second backward workgroup whose waves 1..3 return behind the barriers; three 64b chunks
+    _p64(132, B=1),
+    # the model's layout uv = [u0 | v0 | ua | va]: pair 0 with the shared scorer (row 0), pair 1 with the rows of row_of
+    _p64(48, id="H48-model-pair0", B=3, ld=4 * 48, G=5), _p64(48, id="H48-model-pair1", B=3, ld=4 * 48, ucol=2 * 48, **ROWS),
+    # the generic forward in front of the 64-node backward
+    _p64(5, fwd=FWD, ld=2 * 5 + 1), _p64(33, fwd=FWD, ld=2 * 33 + 1, B=3, **ROWS), _p64(36, id="H36-ldodd", fwd=FWD, ld=2 * 36 + 3),
+    _p64(36, id="H36-uvoff", fwd=FWD, uvoff=1), _p64(36, id="H36-outoff", fwd=FWD, outoff=1, B=1), _p64(68, id="H68-ldodd", fwd=FWD, ld=2 * 68 + 3),
+    # b2 == NULL on each of the three forwards
+    _p64(36, id="H36-nobias", bias=False, B=1), _p64(36, id="H36-w2off-nobias", fwd=FWD64, w2off=1, bias=False, B=1),
+    _p64(33, id="H33-nobias", fwd=FWD, bias=False, B=1),
+    # the generic kernels at the register bound; the forward's j0 loop in front of a backward that must refuse
+    Pair64Case("N63-H33", 2, 63, 33, FWD, BWD, ld=2 * 33 + 3), Pair64Case("N65-H5", 1, 65, 5, FWD, None),
+]
+PAIR_SCALE_CASES = ("H68", "H68-w2off", "H68-ldodd")     # the power-of-two metamorphic case on every forward kernel
+PAIR_SCALE_K = (20, -20)
+
+
+def pair_chain(kernel, N, H):
+    """L of dot_bound: the longest chain of float32 roundings between an input and one output element, read off csrc/pairmlp.hip
+    (line numbers of that file).  Additions of staged zeros count: L depends on the shape only.  slope itself is given to the
+    reference as the float32 the kernel receives (SLOPE_PAIR32), so it adds nothing."""
+    if kernel == FWD64B:
+        # 216 oms = 1 - slope (1); 232 w2 * oms (1); 243 the clamped add t (1); 243-244 a wave's fmas, 16 per chunk of 64 (16 nch);
+        # 264 the merge of the four waves (3); 269 + slope * (...) + bias (2).  The linear part is one shorter: 225 a term's own
+        # product (1, none if contracted) and the adds behind it (16 nch in a thread), 248 quad (2), 269 al + ar, * slope, two adds (4).
+        nch = -(-H // 64)
+        return dict(out=16 * nch + 8)
+    if kernel == FWD64:
+        # 139 w2 * (1 - slope) (2); 150 t (1); 151-152 one thread's fmas over every h, 32 per chunk (32 nch); 169 two adds (2).
+        # linear part: 128 three roundings per j, four j per chunk (12 nch); 156-157 (2); 169 (4)
+        nch = -(-H // 32)
+        return dict(out=32 * nch + 5)
+    if kernel == FWD:
+        # 67 t (1); 68 t * slope (1); 69 a term's own product (1, none if contracted) and the adds behind it -- one packed half takes
+        # every other h: 16 per chunk of 32 (16 nch); 73 the two halves (1); 74 + bias (1)
+        nch = -(-H // 32)
+        return dict(out=16 * nch + 5)
+    if kernel == BWD64:
+        # G = g * s * (1 - s): 375 (3).  The step is exact (0 or 1), so g * step is exact and each fma rounds once.
+        # d_b2: 383 row sums (64), 386 wave_sum (6)
+        # d_u : 383 RS (64) or 428-429 A (64 fmas, one per column); 450 slope * RS (1); 402 oms (1); 451 fma (1); 453 * w (1)
+        # d_v : 392 CS (64) or 428-433 (8 fmas, 1 add, 2 quad); 434, 435 as for d_u (3); 440 * w (1)
+        # d_w2: the d_v chain up to 435 (3 + 64 + 3), then 436 dwj, 64 fmas (64), 460 the final add (1); 2^60 / 2^-60 are exact.
+        #       (the u side is shorter: 452 16 fmas, 457 quad 2)
+        return dict(d_b2=3 + 64 + 6, d_u=3 + 64 + 4, d_v=3 + 64 + 4, d_w2=3 + 64 + 3 + 64 + 1)
+    if kernel == BWD:
+        # gs: 293 (3).  d_b2: 296 16 adds per thread, block_sum_256 (6 + 3).
+        # d_u : 324 g * sl (1), 325 one add per column (N), 336 * w (1);  d_v: 324 (1), 326 32 adds per half (32), 330 (2)
+        # d_w2: 322 t (1), 324 (1), 327 a term's own product (1) and the adds behind it, 32 per column in a packed half (32 N), 332 (1)
+        return dict(d_b2=3 + 16 + 9, d_u=3 + 1 + N + 1, d_v=3 + 1 + 32 + 2, d_w2=3 + 3 + 32 * N + 1)
+    raise ValueError(kernel)
+
+
+def pair_terms(u, v, w2, b2, row_of, slope, g=None, out32=False, mutate=None, hdrop=0):
+    """The pair scorer written out in float64 with analytic gradients, and the sums of absolute values behind every result.
+    b2 None: no bias.  out32: G = g s (1 - s) is formed from this forward's out rounded to float32 -- what the backward kernel is
+    handed when it is tested alone -- instead of the float64 values.  `*_abs` are the |.| sums of the generic kernels, `*_abs_split`
+    those of the 64-node kernels, which take lrelu(t) = slope t + (1 - slope) relu(t) apart, and t = u + v with it.
+    mutate: a deliberately wrong variant for the host test --
+      "drop_tail"   hidden units H - hdrop .. H - 1 never arrive (forward: not summed; backward: their gradients stay 0)
+      "ignore_rows" row_of is ignored, sample b reads row b
+      "no_linear"   the forward omits slope * (al + ar)
+      "transpose_g" the backward reads G[j,i]
+      "step_ge"     the backward's step function is [t >= 0]
+      "double_last" d_w2 counts unit H - 1 twice"""
+    B, _, H = u.shape
+    u, v, w2 = d(u), d(v), d(w2)
+    rows = row_of.long() if row_of is not None else torch.zeros(B, dtype=torch.long)
+    if mutate == "ignore_rows":
+        rows = torch.arange(B)
+    w = w2[rows]                                                          # [B,H]
+    b = d(b2)[rows] if b2 is not None else torch.zeros(B, dtype=torch.float64)
+    live = torch.ones(H, dtype=torch.float64)
+    if mutate == "drop_tail":
+        live[H - hdrop:] = 0.0
+    t = u[:, :, None, :] + v[:, None, :, :]                               # [B,i,j,h]
+    pos = (t >= 0) if mutate == "step_ge" else (t > 0)
+    relu = t.clamp(min=0)
+    lr = torch.where(t > 0, t, slope * t)
+    wl = (w * live)[:, None, None, :]
+    pre = ((1 - slope) * relu * wl).sum(-1) + b[:, None, None]
+    if mutate != "no_linear":
+        pre = pre + slope * (t * wl).sum(-1)
+    res = dict(out=torch.sigmoid(pre), t=t)
+    mag = u.abs()[:, :, None, :] + v.abs()[:, None, :, :]
+    aw = w.abs()[:, None, None, :]
+    res["out_abs"] = b.abs()[:, None, None] + (aw * lr.abs()).sum(-1)
+    res["out_abs_split"] = b.abs()[:, None, None] + (aw * ((1 - slope) * relu + slope * mag)).sum(-1)
+    if g is None:
+        return res
+    s = res["out"].float().double() if out32 else res["out"]
+    G = d(g) * s * (1 - s)
+    if mutate == "transpose_g":
+        G = G.transpose(1, 2)
+    dl = torch.where(pos, torch.ones_like(t), torch.full_like(t, slope))
+    Ga = G.abs()
+    res["d_u"] = w[:, None, :] * torch.einsum("bij,bijh->bih", G, dl) * live
+    res["d_v"] = w[:, None, :] * torch.einsum("bij,bijh->bjh", G, dl) * live
+    res["d_w2"] = torch.einsum("bij,bijh->bh", G, torch.where(pos, t, slope * t)) * live
+    if mutate == "double_last":
+        res["d_w2"][:, H - 1] *= 2.0
+    res["d_b2"] = G.sum((1, 2))
+    res["d_u_abs"] = w.abs()[:, None, :] * Ga.sum(2)[:, :, None].expand(-1, -1, H)
+    res["d_v_abs"] = w.abs()[:, None, :] * Ga.sum(1)[:, :, None].expand(-1, -1, H)
+    res["d_w2_abs"] = torch.einsum("bij,bijh->bh", Ga, lr.abs())
+    res["d_w2_abs_split"] = torch.einsum("bij,bijh->bh", Ga, dl * mag)
+    res["d_b2_abs"] = Ga.sum((1, 2))
+    for k in ("d_u", "d_v", "d_b2"):
+        res[k + "_abs_split"] = res[k + "_abs"]
+    return res
+
+
+def pair_abs(res, name, kernel):
+    """The |.| sum behind result `name` as `kernel` forms it."""
+    return res[name + ("_abs" if kernel in (FWD, BWD) else "_abs_split")]
+
+
+def pair_out_tol(L, out_abs):
+    """|sigmoid'| <= 1/4 times the dot-product bound of the pre-activation, plus the 2e-6 the project allows __expf and the
+    division (test_ct_gpu.test_pair_mlp_kernel)."""
+    return 0.25 * dot_bound(L, out_abs) + 2e-6
+
+
+def pair_sums32(u, v):
+    """Every float32 sum u[b,i,h] + v[b,j,h], as the kernels form it."""
+    return u.float()[:, :, None, :] + v.float()[:, None, :, :]

@@ -234,4 +234,7 @@ def test_pixmajor_and_lazy_references():
     gen = torch.Generator().manual_seed(3)
     x, w, b = torch.randn(B, Ci, generator=gen), torch.randn(Ci, Cc * P, generator=gen), torch.randn(Cc * P, generator=gen)
     y = F.linear(x.double(), w.double().t(), b.double()).view(B, Cc, 2, 2)                  # .view(B, C, h, w): NCHW
-    assert torch.equal(C.pixmajor_ref(x, w, b, Cc, P), y.permute(0, 2, 3, 1).reshape(B, P, Cc))
+    # not torch.equal: F.linear adds the bias inside the GEMM, the reference behind it, and whether the two float64 results agree to
+    # the last bit depends on the host's BLAS path.  A wrong column-to-pixel map is off by O(1), not by 1e-12.
+    want = y.permute(0, 2, 3, 1).reshape(B, P, Cc)
+    assert float((C.pixmajor_ref(x, w, b, Cc, P) - want).abs().max()) <= 1e-12 * float(want.abs().max())

@@ -297,8 +297,9 @@ def test_clamp_kernels_hold_over_input_magnitudes(dev, scale):
 
 @pytest.mark.parametrize("B,N,Hh,C", [(2, 65, 13, 100), (3, 65, 13, 64), (2, 9, 3, 20)])
 def test_gat_score_kernel_and_layer(dev, B, N, Hh, C):
-    """ctvae_gat_score(+backward) against the head-by-head torch expression of DenseGATv2 (GATv2Conv attention logits,
-    ct_mcq_vae.py:103-114): the whole layer output and the gradients of x, adj and every parameter must agree."""
+    """DenseGATv2.forward (the head-by-head torch expression of the GATv2Conv attention, ct_mcq_vae.py:103-114; torch ops on
+    either device -- it no longer calls ctvae_gat_score) on the GPU against the same module on the CPU: the whole layer output
+    and the gradients of x, adj and every parameter must agree."""
     from ctvae_amd.models.causal import DenseGATv2
     torch.manual_seed(50 + N + C)
     layer = DenseGATv2(24, C, Hh)
@@ -314,7 +315,7 @@ def test_gat_score_kernel_and_layer(dev, B, N, Hh, C):
     layer_d = DenseGATv2(24, C, Hh).to(dev)
     layer_d.load_state_dict(layer.state_dict())
     xd, ad = x.detach().to(dev).requires_grad_(True), adj.detach().to(dev).requires_grad_(True)
-    out = layer_d(xd, ad)                                  # CUDA tensors -> HIP score kernels
+    out = layer_d(xd, ad)                                  # CUDA tensors -> the same torch ops on the device
     out.backward(go.to(dev))
     torch.cuda.synchronize()
     np.testing.assert_allclose(out.detach().cpu().numpy(), ref.detach().numpy(), atol=2e-5, rtol=1e-4)

@@ -696,3 +696,234 @@ def test_pair_mlp_strided_blocks_and_bank_rows(N, case):
     for name, g_, want in (("d_u", got["d_uv"][:, :H].reshape(B, Nn, H), ref["d_u"]), ("d_v", got["d_uv"][:, H:2 * H].reshape(B, Nn, H), ref["d_v"]),
                            ("d_w2", got["dw2p"], ref["d_w2"]), ("d_b2", got["db2p"], ref["d_b2"])):
         within(f"pair {case.id}/{name}", g_, want, tol_of(want, 1e-5, 1e-4, scaled=True))
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# pair scorer: the three 64-node kernels and every way into them
+# ---------------------------------------------------------------------------------------------------------------------
+def off_buf(n, off, fill=NAN):
+    """n floats that start `off` floats behind a 16-byte boundary, NaN around them."""
+    base = full((off + n + 4,), fill)
+    assert base.data_ptr() % 16 == 0
+    return base[off:off + n]
+
+
+_pair_refs = {}
+
+
+def pair64_ref(case):
+    """(inputs, float64 reference) of a case, computed once.  The backward is tested alone: G is formed from the reference's out
+    rounded to float32, which is what the kernel is handed."""
+    if case.id not in _pair_refs:
+        inp = V.pair_inputs(case)
+        _pair_refs[case.id] = (inp, V.pair_terms(inp["u"], inp["v"], inp["w2"], inp["b2"] if case.bias else None, inp["row_of"],
+                                                 V.SLOPE_PAIR32, inp["g"], out32=True))
+    return _pair_refs[case.id]
+
+
+class PairBufs:
+    """Device inputs of one Pair64Case in the layout the case asks for; forward() / backward() run one entry point into fresh
+    NaN-filled outputs with a guard row behind each.  k: u, v times 2^k and w2 times 2^-k."""
+
+    def __init__(self, case, inp, ref_out, k=0):
+        self.case = case
+        B, Nn, H = case.B, case.N, case.H
+        ld, c0 = case.ld_, case.ucol
+        s = 2.0 ** k
+        self.uv = off_buf(B * Nn * ld, case.uvoff).view(B * Nn, ld)
+        self.uv[:, c0:c0 + H] = (inp["u"] * s).reshape(-1, H).to(dev())
+        self.uv[:, c0 + H:c0 + 2 * H] = (inp["v"] * s).reshape(-1, H).to(dev())
+        self.u_ptr, self.v_ptr = self.uv.data_ptr() + 4 * c0, self.uv.data_ptr() + 4 * (c0 + H)
+        self.w2 = off_buf(case.G * H, case.w2off)
+        self.w2[:] = (inp["w2"] / s).reshape(-1).to(dev())
+        self.b2 = inp["b2"].to(dev()) if case.bias else None
+        self.ro = None if inp["row_of"] is None else inp["row_of"].to(dev())
+        self.per = 0 if self.ro is None else 1
+        self.out_in = ref_out.float().contiguous().to(dev())
+        self.g = inp["g"].contiguous().to(dev())
+
+    def new_out(self):
+        c = self.case
+        return off_buf((c.B * c.N + 1) * c.N, c.outoff).view(c.B * c.N + 1, c.N)
+
+    def aligned(self, out):
+        return tuple(p % 16 == 0 for p in (self.u_ptr, self.v_ptr, out.data_ptr(), self.w2.data_ptr()))
+
+    def fwd_args(self, native, out):
+        c = self.case
+        return [self.u_ptr, self.v_ptr, c.ld_, self.w2.data_ptr(), native.ptr(self.b2), out.data_ptr(), c.B, c.N, c.H, V.SLOPE_PAIR32,
+                self.per, native.ptr(self.ro)]
+
+    def new_grads(self):
+        c = self.case
+        return full((c.B * c.N + 1, c.ldd_)), full((c.B + 1, c.H)), full((c.B + 1,))
+
+    def bwd_args(self, native, d_uv, dw2p, db2p):
+        c = self.case
+        return [self.u_ptr, self.v_ptr, c.ld_, self.w2.data_ptr(), self.out_in.data_ptr(), self.g.data_ptr(),
+                d_uv.data_ptr() + 4 * c.ucol, d_uv.data_ptr() + 4 * (c.ucol + c.H), c.ldd_, dw2p.data_ptr(), db2p.data_ptr(), c.B, c.N,
+                c.H, V.SLOPE_PAIR32, self.per, native.ptr(self.ro)]
+
+    def forward(self, native):
+        out = self.new_out()
+        native.call("ctvae_pair_mlp_forward", *self.fwd_args(native, out))
+        torch.cuda.synchronize()
+        return dict(out=out.cpu())
+
+    def backward(self, native):
+        d_uv, dw2p, db2p = self.new_grads()
+        native.call("ctvae_pair_mlp_backward", *self.bwd_args(native, d_uv, dw2p, db2p))
+        torch.cuda.synchronize()
+        return dict(d_uv=d_uv.cpu(), dw2p=dw2p.cpu(), db2p=db2p.cpu())
+
+
+def pair_grad_views(case, got):
+    """The written parts of the backward's buffers; asserts that everything else still holds the fill."""
+    B, Nn, H, c0 = case.B, case.N, case.H, case.ucol
+    d_uv = got["d_uv"]
+    assert untouched(d_uv[:, :c0]) and untouched(d_uv[:, c0 + 2 * H:]), "columns beside d_u | d_v written"
+    assert untouched(d_uv[B * Nn:]) and untouched(got["dw2p"][B:]) and untouched(got["db2p"][B:]), "guard row written"
+    return dict(d_u=d_uv[:B * Nn, c0:c0 + H].reshape(B, Nn, H), d_v=d_uv[:B * Nn, c0 + H:c0 + 2 * H].reshape(B, Nn, H),
+                d_w2=got["dw2p"][:B], d_b2=got["db2p"][:B])
+
+
+@pytest.mark.parametrize("case", V.PAIR64_CASES, ids=lambda c: c.id)
+def test_pair64_each_kernel_alone(N, case):
+    """Forward and backward separately (the backward on the float32-rounded reference out) against the float64 reference, within
+    dot_bound(L, |.| sum) with L of ct_ops_checks.pair_chain; the launch log must name the kernels the mirror of the launcher
+    predicts from the actual pointers, which must be the ones the case table is there to reach."""
+    inp, ref = pair64_ref(case)
+    P = PairBufs(case, inp, ref["out"])
+    B, Nn, H = case.B, case.N, case.H
+    fk, bk = V.pair_kernels(Nn, H, case.ld_, *P.aligned(P.new_out()))
+    assert (fk, bk) == (case.fwd, case.bwd)
+    got, rep = logged(N, lambda: twice(lambda: P.forward(N)))
+    assert set(rep) == {fk} and rep[fk]["count"] == 2, sorted(rep)
+    assert untouched(got["out"][B * Nn:]), "guard row of out written"
+    L = V.pair_chain(fk, Nn, H)["out"]
+    within(f"pair64 {case.id}/out [{fk}, L={L}]", got["out"][:B * Nn].reshape(B, Nn, Nn), ref["out"], V.pair_out_tol(L, V.pair_abs(ref, "out", fk)))
+    if bk is None:                       # N > 64: refused, nothing launched, nothing written
+        bufs = P.new_grads()
+        _, rep = logged(N, lambda: fails(N, V.ERR_BAD_ARG, "ctvae_pair_mlp_backward", *P.bwd_args(N, *bufs)))
+        assert not rep and all(untouched(t.cpu()) for t in bufs)
+        return
+    got, rep = logged(N, lambda: twice(lambda: P.backward(N)))
+    assert set(rep) == {bk} and rep[bk]["count"] == 2, sorted(rep)
+    Ls = V.pair_chain(bk, Nn, H)
+    for name, g_ in pair_grad_views(case, got).items():
+        within(f"pair64 {case.id}/{name} [{bk}, L={Ls[name]}]", g_, ref[name], V.dot_bound(Ls[name], V.pair_abs(ref, name, bk)))
+
+
+@pytest.mark.parametrize("cid", V.PAIR_SCALE_CASES)
+def test_pair64_power_of_two_scaling_commutes(N, cid):
+    """(2^k u, 2^k v, 2^-k w2) gives the same out bit for bit on each forward kernel, and, for the same out and g, d_u and d_v times
+    2^-k, d_w2 times 2^k and the same d_b2 bit for bit: power-of-two scaling commutes with every operation of these kernels while
+    nothing leaves the normal range (asserted for these inputs in the host test), the clamps that stand for relu and the step
+    function included."""
+    case = V.case_of(V.PAIR64_CASES, cid)
+    inp, ref = pair64_ref(case)
+    base = PairBufs(case, inp, ref["out"])
+    (f0, b0), rep = logged(N, lambda: (base.forward(N), base.backward(N)))
+    assert set(rep) == {case.fwd, case.bwd}, sorted(rep)
+    g0 = pair_grad_views(case, b0)
+    for k in V.PAIR_SCALE_K:
+        P = PairBufs(case, inp, ref["out"], k=k)
+        (f, b), rep = logged(N, lambda: (P.forward(N), P.backward(N)))
+        assert set(rep) == {case.fwd, case.bwd}, sorted(rep)
+        assert same(f["out"], f0["out"]), f"k={k}: out differs"
+        g = pair_grad_views(case, b)
+        s = 2.0 ** k
+        assert same(g["d_u"], g0["d_u"] / s) and same(g["d_v"], g0["d_v"] / s), f"k={k}: d_u / d_v are not the 2^-k multiples"
+        assert same(g["d_w2"], g0["d_w2"] * s), f"k={k}: d_w2 is not the 2^k multiple"
+        assert same(g["d_b2"], g0["d_b2"]), f"k={k}: d_b2 differs"
+
+
+def test_pair64_refusals_write_nothing(N):
+    case = V.case_of(V.PAIR64_CASES, "H36")
+    inp, ref = pair64_ref(case)
+    P = PairBufs(case, inp, ref["out"])
+    out, grads = P.new_out(), P.new_grads()
+    fa, ba = P.fwd_args(N, out), P.bwd_args(N, *grads)
+
+    def bad(args, **at):
+        a = list(args)
+        for i, v in at.items():
+            a[int(i[1:])] = v
+        return a
+
+    def run():
+        # forward: u, v, ld, w2, b2, out, B, N, H, ...
+        for at in (dict(_2=case.H - 1), dict(_6=0), dict(_6=-1), dict(_7=0), dict(_7=-64), dict(_8=0), dict(_8=-4), dict(_0=None), dict(_1=None),
+                   dict(_3=None), dict(_5=None)):
+            fails(N, V.ERR_BAD_ARG, "ctvae_pair_mlp_forward", *bad(fa, **at))
+        # backward: u, v, ld, w2, out, g_out, d_u, d_v, ldd, d_w2_part, d_b2_part, B, N, H, ...
+        for at in (dict(_2=case.H - 1), dict(_8=case.H - 1), dict(_11=0), dict(_11=-1), dict(_12=0), dict(_12=-64), dict(_12=65), dict(_13=0),
+                   dict(_13=-4), *[{f"_{i}": None} for i in (0, 1, 3, 4, 5, 6, 7, 9, 10)]):
+            fails(N, V.ERR_BAD_ARG, "ctvae_pair_mlp_backward", *bad(ba, **at))
+
+    _, rep = logged(N, run)
+    assert not rep, sorted(rep)
+    assert untouched(out.cpu()) and all(untouched(t.cpu()) for t in grads)
+
+
+@pytest.mark.parametrize("nd", [1, 2])
+def test_pair_scores_wrapper_folds_partials_into_bank_rows(N, nd):
+    """kernels.PairScores as the model calls it, on plain tensors (no flat gradient buffer): column blocks of one GEMM output, the
+    scorer bank read in place through grp, per-sample partials folded into the bank's rows by ctvae_group_rowsum.  Reference:
+    float64 autograd of the written-out pre-activation; the sigmoid's derivative is taken at the out the forward saved (as the
+    wrapper's backward does), so that the gradients' bounds need no term for the forward's own error."""
+    from ctvae_amd import kernels as K
+    B, H, G = 3, 48, 5
+    gen = V.gen_of(f"pair-scores-nd{nd}", 17)
+    uv = torch.randn(B, 64, nd * 2 * H, generator=gen)
+    w2, b2 = torch.randn(G, H, generator=gen) / H ** 0.5, torch.randn(G, generator=gen)
+    g = torch.randn(nd, B, 64, 64, generator=gen)
+    grp = torch.tensor(V.ROWS["row_of"], dtype=torch.int32) if nd == 2 else None
+    rows = [torch.zeros(B, dtype=torch.long)] + ([grp.long()] if nd == 2 else [])
+
+    def run():
+        a, w, b = (t.to(dev()).requires_grad_(True) for t in (uv, w2, b2))
+        out = K.PairScores.apply(a, w, b, None if grp is None else grp.to(dev()), H)
+        ga, gw, gb = torch.autograd.grad(out, (a, w, b), g.to(dev()))
+        torch.cuda.synchronize()
+        assert all(t.data_ptr() % 16 == 0 for t in (a, w, out))
+        return dict(out=out.detach().cpu(), d_uv=ga.cpu(), d_w2=gw.cpu(), d_b2=gb.cpu())
+
+    got, rep = logged(N, lambda: twice(run))
+    assert set(rep) == {V.FWD64B, V.BWD64, "group_rowsum_kernel"}, sorted(rep)
+    assert rep[V.FWD64B]["count"] == 2 * nd and rep[V.BWD64]["count"] == 2 * nd
+    # float64: the same expression; per discoverer d the analytic terms give the |.| sums
+    uv64, w64, b64 = (V.d(t).requires_grad_(True) for t in (uv, w2, b2))
+    pre = []
+    for dd in range(nd):
+        u, v = uv64[..., 2 * dd * H:(2 * dd + 1) * H], uv64[..., (2 * dd + 1) * H:(2 * dd + 2) * H]
+        t = u[:, :, None, :] + v[:, None, :, :]
+        pre.append((torch.nn.functional.leaky_relu(t, V.SLOPE_PAIR32) * w64[rows[dd]][:, None, None, :]).sum(-1) + b64[rows[dd]][:, None, None])
+    pre = torch.stack(pre)
+    s = got["out"].double()
+    (pre * (V.d(g) * s * (1 - s))).sum().backward()
+    Lf, Lb = V.pair_chain(V.FWD64B, 64, H)["out"], V.pair_chain(V.BWD64, 64, H)
+    w_abs, b_abs, cnt = torch.zeros(G, H, dtype=torch.float64), torch.zeros(G, dtype=torch.float64), torch.zeros(G)
+    for dd in range(nd):
+        cu, cv = slice(2 * dd * H, (2 * dd + 1) * H), slice((2 * dd + 1) * H, (2 * dd + 2) * H)
+        terms = V.pair_terms(uv[..., cu], uv[..., cv], w2, b2, None if dd == 0 else grp, V.SLOPE_PAIR32)
+        within(f"PairScores nd={nd}/out[{dd}]", got["out"][dd], torch.sigmoid(pre[dd].detach()), V.pair_out_tol(Lf, terms["out_abs_split"]))
+        # the |.| sums with G from the saved out
+        Ga = (V.d(g[dd]) * s[dd] * (1 - s[dd])).abs()
+        wa = V.d(w2)[rows[dd]].abs()
+        within(f"PairScores nd={nd}/d_u[{dd}]", got["d_uv"][..., cu], uv64.grad[..., cu], V.dot_bound(Lb["d_u"], wa[:, None, :] * Ga.sum(2)[:, :, None]))
+        within(f"PairScores nd={nd}/d_v[{dd}]", got["d_uv"][..., cv], uv64.grad[..., cv], V.dot_bound(Lb["d_v"], wa[:, None, :] * Ga.sum(1)[:, :, None]))
+        tt = V.d(uv[..., cu])[:, :, None, :] + V.d(uv[..., cv])[:, None, :, :]
+        mag = V.d(uv[..., cu]).abs()[:, :, None, :] + V.d(uv[..., cv]).abs()[:, None, :, :]
+        dl = torch.where(tt > 0, torch.ones_like(tt), torch.full_like(tt, V.SLOPE_PAIR32))
+        w_abs.index_add_(0, rows[dd], torch.einsum("bij,bijh->bh", Ga, dl * mag))
+        b_abs.index_add_(0, rows[dd], Ga.sum((1, 2)))
+        cnt.index_add_(0, rows[dd], torch.ones(B))
+    # ctvae_group_rowsum: at most B adds per call and one more to accumulate the second call
+    Lw, Lbias = Lb["d_w2"] + B + 1, Lb["d_b2"] + B + 1
+    within(f"PairScores nd={nd}/d_w2", got["d_w2"], w64.grad, V.dot_bound(Lw, w_abs))
+    within(f"PairScores nd={nd}/d_b2", got["d_b2"], b64.grad, V.dot_bound(Lbias, b_abs))
+    unused = cnt == 0
+    assert unused.tolist() == ([False, True, False, True, False] if nd == 2 else [False, True, True, True, True]) and int(cnt[0]) == B
+    assert float(got["d_w2"][unused].abs().sum()) == 0.0 and float(got["d_b2"][unused].abs().sum()) == 0.0, "rows nobody uses must be 0"
+    assert float(w64.grad[unused].abs().sum()) == 0.0

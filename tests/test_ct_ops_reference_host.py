@@ -367,3 +367,124 @@ def test_bounds_catch_a_dropped_k_tail_a_skipped_slab_and_a_shifted_exclusive_pr
         V.reg_ref(**inp, ckl=rc.coef[0], cgs=rc.coef[1], cpt=rc.coef[2], g_loss=rc.g_loss, shift=1)
     err = float((bad["d_adj"] - ref["d_adj"]).abs().max())
     assert err > 1e2 * 2e-3 * float(ref["d_adj"].abs().max()), err              # the GPU test allows 2e-3 of the largest magnitude
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# pair scorer, the 64-node kernels
+# ---------------------------------------------------------------------------------------------------------------------
+def pair_case_terms(case, inp=None, **kw):
+    inp = inp or V.pair_inputs(case)
+    return V.pair_terms(inp["u"], inp["v"], inp["w2"], inp["b2"] if case.bias else None, inp["row_of"], V.SLOPE_PAIR32, inp["g"], **kw)
+
+
+@pytest.mark.parametrize("cid", ["H36-w2off-rows", "H33-nobias", "N63-H33", "H5"])
+def test_pair_terms_is_pair_mlp_ref(cid):
+    """The analytic float64 reference of the GPU cases against float64 autograd of the expression (pair_mlp_ref, itself pinned to
+    _pair_coeffs above)."""
+    case = V.case_of(V.PAIR64_CASES, cid)
+    inp = V.pair_inputs(case)
+    b2 = inp["b2"] if case.bias else torch.zeros_like(inp["b2"])
+    want = V.pair_mlp_ref(inp["u"], inp["v"], inp["w2"], b2, inp["row_of"], V.SLOPE_PAIR32, inp["g"])
+    got = pair_case_terms(case, inp)
+    for k in ("out", "d_u", "d_v", "d_w2", "d_b2"):
+        assert_pinned(got[k], want[k], f"{cid}/{k}")
+    for k in ("out", "d_u", "d_v", "d_w2", "d_b2"):                        # the |.| sums dominate what they bound, split above plain
+        assert bool((got[k + "_abs_split"] >= got[k + "_abs"] * (1 - 1e-12)).all())
+        if k != "out":
+            assert bool((got[k + "_abs"] >= got[k].abs() * (1 - 1e-12)).all())
+    # out32: only G changes, by the rounding of s
+    r32 = pair_case_terms(case, inp, out32=True)
+    assert torch.equal(r32["out"], got["out"]) and float((r32["d_b2"] - got["d_b2"]).abs().max()) <= 64 * 64 * 2.0 ** -24 * float(inp["g"].abs().max())
+
+
+def test_pair64_mirror_matches_the_case_table():
+    for c in V.PAIR64_CASES:
+        assert V.pair_kernels(c.N, c.H, c.ld_, *c.alignment()) == (c.fwd, c.bwd), c.id
+        assert c.ld_ >= c.ucol + 2 * c.H and (c.row_of is None or (len(c.row_of) == c.B and max(c.row_of) < c.G))
+    assert len({c.id for c in V.PAIR64_CASES}) == len(V.PAIR64_CASES)
+    by = lambda k: {(c.H, c.ld_ % 4, c.bias, c.row_of is not None) for c in V.PAIR64_CASES if c.fwd == k and c.N == 64}      # noqa: E731
+    hs = lambda k: {c.H for c in V.PAIR64_CASES if c.fwd == k and c.N == 64}                                                   # noqa: E731
+    assert hs(V.FWD64B) >= {4, 32, 36, 48, 60, 64, 68, 132} and hs(V.FWD64) >= {4, 32, 36, 68} and hs(V.FWD) >= {5, 33, 36}
+    for H in (4, 36, 68):                                                # the unaligned bank, shared and per sample
+        assert {r for (h, _, _, r) in by(V.FWD64) if h == H} == {False, True}
+    for k in (V.FWD64B, V.FWD64, V.FWD):
+        assert any(not b for (_, _, b, _) in by(k)), f"{k}: no case without b2"
+    assert any(c.fwd == V.FWD and c.H % 4 == 0 and c.ld_ % 4 and c.N == 64 for c in V.PAIR64_CASES)
+    assert any(c.fwd == V.FWD and c.H % 4 == 0 and c.ld_ % 4 == 0 and c.uvoff % 4 for c in V.PAIR64_CASES)
+    assert any(c.fwd == V.FWD and c.H % 4 == 0 and c.ld_ % 4 == 0 and c.outoff % 4 for c in V.PAIR64_CASES)
+    assert any(c.dpad == 0 for c in V.PAIR64_CASES) and any(c.dpad and c.ld_ > 2 * c.H for c in V.PAIR64_CASES)
+    model = [c for c in V.PAIR64_CASES if c.ld_ == 4 * c.H]
+    assert {c.ucol for c in model} == {0, 2 * 48} and all(c.G == 5 and c.B == 3 and c.ldd_ == c.ld_ + 4 for c in model)
+    assert len(set(V.ROWS["row_of"])) < len(V.ROWS["row_of"]) and len(set(V.ROWS["row_of"])) < V.ROWS["G"]
+    assert {(c.N, c.H, c.fwd, c.bwd) for c in V.PAIR64_CASES if c.N != 64} == {(63, 33, V.FWD, V.BWD), (65, 5, V.FWD, None)}
+    assert V.pair_kernels(37, 40, 88) == (V.FWD, V.BWD) and V.pair_kernels(64, 36, 72, w2_al=False)[0] == V.FWD64
+
+
+def test_pair64_sums_stay_clear_of_the_step_functions_blind_range():
+    """The step [t > 0] of the 64-node backward is sat(t * 2^60): exact unless 0 < t < 2^-60; and a float32 add has the sign of the
+    exact sum, so only an exact 0 could be taken for either side.  Also the range the power-of-two case needs: with u, v scaled by
+    2^k and w2 by 2^-k every staged operand (times 2^-64 in the forward, 2^60 in the backward), every sum of two of them and every
+    result stays a normal float32, and positive sums stay >= 2^-60."""
+    tiny, huge = 2.0 ** -126, 2.0 ** 127
+    for case in V.PAIR64_CASES:
+        inp = V.pair_inputs(case)
+        t = V.pair_sums32(inp["u"], inp["v"])
+        print(f"pair64 {case.id}: smallest float32 |u + v| {float(t.abs().min()):.3e} (blind range: 0 and (0, {V.STEP_MIN:.3e}))")
+        assert not bool(((t == 0) | ((t > 0) & (t < V.STEP_MIN))).any()), f"{case.id}: pick another seed"
+    for cid in V.PAIR_SCALE_CASES:
+        case = V.case_of(V.PAIR64_CASES, cid)
+        inp = V.pair_inputs(case)
+        ref = pair_case_terms(case, inp, out32=True)
+        t = V.pair_sums32(inp["u"], inp["v"]).double()
+        for k in V.PAIR_SCALE_K:
+            s = 2.0 ** k
+            ops = torch.cat([V.d(inp["u"]).flatten(), V.d(inp["v"]).flatten(), t.flatten()]).abs() * s
+            ops = ops[ops > 0]
+            assert float(ops.min()) * 2.0 ** -64 >= tiny and float(ops.max()) * 2.0 ** 60 < huge, (cid, k)
+            assert float(t[t > 0].min()) * s >= V.STEP_MIN, (cid, k)
+            print(f"pair64 {cid} k={k:+d}: scaled operands and sums in [{float(ops.min()):.3e}, {float(ops.max()):.3e}], "
+                  f"smallest positive sum {float(t[t > 0].min()) * s:.3e} >= {V.STEP_MIN:.3e}")
+            w = V.d(inp["w2"]).abs() / s
+            assert float(w[w > 0].min()) * (1 - V.SLOPE_PAIR32) >= tiny and float(w.max()) < huge
+            for name, f in (("d_u", 1 / s), ("d_v", 1 / s), ("d_w2", s)):     # results and the |.| sums that bound every partial sum
+                r = ref[name].abs() * f
+                assert float(r[r > 0].min()) >= 2.0 ** -100 and float(ref[name + "_abs_split"].max()) * f * 2.0 ** 60 < huge, (cid, k, name)
+
+
+def test_pair64_bounds_catch_subtly_wrong_kernels():
+    """Each mutation of the reference must leave the GPU test's bound by a factor of 10 on some element, else the inputs are too
+    tame for the test to notice that kernel."""
+    def factors(case, bad, ref, names):
+        fk, bk = case.fwd, case.bwd
+        L = {**V.pair_chain(fk, case.N, case.H), **V.pair_chain(bk, case.N, case.H)}
+        out = {}
+        for n in names:
+            tol = V.pair_out_tol(L[n], V.pair_abs(ref, n, fk)) if n == "out" else V.dot_bound(L[n], V.pair_abs(ref, n, bk))
+            out[n] = float(((bad[n] - ref[n]).abs() / tol.clamp(min=1e-300)).max())
+        return out
+
+    def check(what, case, names, inp=None, **kw):
+        ref, bad = pair_case_terms(case, inp, out32=True), pair_case_terms(case, inp, out32=True, **kw)
+        f = factors(case, bad, ref, names)
+        print(f"pair64 mutation {what} on {case.id}: bound exceeded by " + ", ".join(f"{n} x{v:.3g}" for n, v in f.items()))
+        assert all(v >= 10 for v in f.values()), (what, f)
+
+    c = lambda cid: V.case_of(V.PAIR64_CASES, cid)                         # noqa: E731
+    for cid in ("H68", "H132"):                                            # the last H % 64 units of the blocked forward
+        check("drop the forward's last partial chunk", c(cid), ["out"], mutate="drop_tail", hdrop=c(cid).H % 64)
+    check("drop the forward's last partial chunk", c("H36-w2off"), ["out"], mutate="drop_tail", hdrop=4)      # fwd64: H % 32
+    for cid in ("H4", "H36", "H68"):                                       # the backward's last H % 32 units
+        check("drop the backward's last partial wave", c(cid), ["d_u", "d_v", "d_w2"], mutate="drop_tail", hdrop=c(cid).H % 32)
+    for cid in ("H36-w2off-rows", "H48-model-pair1", "H33"):
+        check("ignore row_of", c(cid), ["out", "d_u", "d_v"], mutate="ignore_rows")
+    for cid in ("H4", "H68", "H68-w2off"):
+        check("omit slope * (al + ar)", c(cid), ["out"], mutate="no_linear")
+    check("transpose G", c("H36"), ["d_u", "d_v", "d_w2"], mutate="transpose_g")
+    for cid in ("H4", "H36", "H132"):
+        check("count unit H - 1 twice in d_w2", c(cid), ["d_w2"], mutate="double_last")
+    # the step at t >= 0: only an exact zero sum tells it from t > 0, and the GPU cases hold none (asserted above) -- plant one here
+    case = c("H36")
+    inp = V.pair_inputs(case)
+    inp["u"][0, 3, 7] = -inp["v"][0, 5, 7]
+    assert float(V.pair_sums32(inp["u"], inp["v"])[0, 3, 5, 7]) == 0.0
+    check("step function at t >= 0", case, ["d_u", "d_v"], inp=inp, mutate="step_ge")
