@@ -9,6 +9,7 @@
 // [A][3] histogram in LDS, and the workgroup ends with ONE global atomic add per non-zero histogram word.  Integer adds only:
 // the result does not depend on the order of workgroups or launches, and successive launches accumulate.
 #include "common.hpp"
+#include "ops.hpp"
 #include "prof.hpp"
 
 namespace ctvae {

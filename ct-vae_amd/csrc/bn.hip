@@ -9,8 +9,10 @@
 //           g_y = gamma*invstd * (g_bn - dbeta/R - xhat*dgamma/R)   (as k1*g_bn + k2*y + k3 per channel)
 // All of these are HBM-bound streaming kernels (roofline: bytes / 8 TB/s): 16-B loads, several in flight per lane.
 #include "common.hpp"
+#include "convpaths.hpp"
 #include "phase.hpp"
 #include "finish.hpp"
+#include "pair.hpp"
 #include "prof.hpp"
 
 namespace ctvae {

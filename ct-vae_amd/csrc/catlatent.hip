@@ -5,6 +5,7 @@
 // reductions inside the group, nothing goes through LDS except the per-workgroup partial of the KL sum.
 // HBM-bound: forward 12 B per element (logits, uniform draw, sample), backward 12 B, KL 4 B forward / 8 B backward.
 #include "common.hpp"
+#include "ops.hpp"
 #include "prof.hpp"
 
 namespace ctvae {

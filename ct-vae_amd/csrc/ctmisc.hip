@@ -11,6 +11,7 @@
 //   ct_blend_softmax_fwd/bwd     _compute_y's tail (:226-228): softmax_d( y0 * (1 - mask) + y1 * mask ), one wave per node
 //   ct_latent_ce_fwd/bwd         latent_CrossEntropy_loss (:306-311): cross_entropy(log(clamp(p, 1e-4)), target), one wave per node
 #include "common.hpp"
+#include "ops.hpp"
 #include "prof.hpp"
 
 namespace ctvae {

@@ -11,6 +11,7 @@
 //                       window edge, weights (1-l, l), rows combined after columns -- the order of ATen's
 //                       upsample_bilinear2d kernel, so results agree to rounding.
 #include "common.hpp"
+#include "ops.hpp"
 #include "prof.hpp"
 
 namespace ctvae {

@@ -8,6 +8,7 @@
 //   d/dlv[i][i] = dv * 2 exp(2 lv[i][i]) / min(B,D).
 // Sizes are latent-sized (B x 128, 128 x 128): three small launches forward (rows, covariance rows, finish), one backward.
 #include "common.hpp"
+#include "ops.hpp"
 #include "prof.hpp"
 
 namespace ctvae {

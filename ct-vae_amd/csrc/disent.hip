@@ -7,6 +7,7 @@
 //   mi_matrix_kernel           z, lo, hi, factors -> mi [L][F] (+ bins [N][L])       (bins live in LDS; counts are integers)
 //   group_var_argmin_kernel    z [G][B][L] -> per group arg-min of var / global_var  ((value, index) through wave shuffles)
 #include "common.hpp"
+#include "ops.hpp"
 #include "prof.hpp"
 
 namespace ctvae {

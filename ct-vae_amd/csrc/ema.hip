@@ -21,6 +21,7 @@
 #include <cmath>
 
 #include "common.hpp"
+#include "ops.hpp"
 #include "prof.hpp"
 
 namespace ctvae {

@@ -7,6 +7,7 @@
 //       I(a,b,c,d) = -c d / a - b log a - lgamma(b) + (b - 1)(digamma(d) + log c),   kld = sum_d I(c,d,c,d) - I(1/alpha, beta, c, d)
 //     with c = 1 / prior_alpha, d = prior_beta; mean over the batch.
 #include "common.hpp"
+#include "ops.hpp"
 #include "prof.hpp"
 
 namespace ctvae {

@@ -12,6 +12,7 @@
 //                        leave as per-sample partials.
 // Masked softmax over sources and the alpha-weighted aggregation stay as small torch ops on [B,H,N,N].
 #include "common.hpp"
+#include "ops.hpp"
 #include "prof.hpp"
 
 namespace ctvae {

@@ -17,6 +17,7 @@
 // three workgroups per CU.  P_k itself (64 KB at D = 128) is not kept in LDS whole: every workgroup walks all of it once per
 // component, 640 KB for K = 10, which stays in L2.
 #include "common.hpp"
+#include "ops.hpp"
 #include "prof.hpp"
 
 namespace ctvae {

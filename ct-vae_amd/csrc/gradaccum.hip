@@ -15,6 +15,7 @@
 // needs acc + head on a 16-byte boundary as well (FlatAdam allocates its accumulator that way); otherwise the whole range
 // runs float by float.  64-bit indices, no atomics, plain loads and stores, nothing outside [0, n) is read or written.
 #include "common.hpp"
+#include "ops.hpp"
 #include "prof.hpp"
 
 namespace ctvae {

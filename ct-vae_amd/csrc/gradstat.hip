@@ -27,6 +27,7 @@
 //
 // `g` is read only; every address is checked against n.  Writes go to the partials and to the caller's output arrays alone.
 #include "common.hpp"
+#include "ops.hpp"
 #include "prof.hpp"
 
 namespace ctvae {

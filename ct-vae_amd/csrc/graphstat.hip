@@ -13,6 +13,7 @@
 // do not depend on each other, only the adds do) and adds them in list order.  float -> double is exact and a double add
 // rounds once, so the result equals a numpy loop bit for bit.  Tile 0 of a group adds the row counts with plain stores.
 #include "common.hpp"
+#include "ops.hpp"
 #include "prof.hpp"
 
 namespace ctvae {

@@ -20,6 +20,7 @@
 #include <type_traits>
 
 #include "common.hpp"
+#include "convpaths.hpp"
 #include "prof.hpp"
 
 namespace ctvae {

@@ -15,6 +15,7 @@
 // NaN: fminf / fmaxf return their other operand, so the range skips it and the clamps turn it into lo, i.e. byte 0 (torch
 // would propagate it into the range and blank the picture); +-inf clamp to hi / lo.
 #include "common.hpp"
+#include "ops.hpp"
 #include "prof.hpp"
 
 namespace ctvae {

@@ -10,6 +10,7 @@
 // for the backward pass.  HBM-bound: forward 8 B per element of recons (the image re-read hits L2 for rep > 1),
 // backward 12 B per element.
 #include "common.hpp"
+#include "ops.hpp"
 #include "prof.hpp"
 
 namespace ctvae {

@@ -19,6 +19,7 @@
 // (klfloor_finish: 256 threads in column order, doubles, a fixed tree) runs at the end of the same launch when L <= 128 -- the
 // models' latent sizes -- and as a second launch of one workgroup otherwise; both give the same bits.
 #include "common.hpp"
+#include "ops.hpp"
 #include "prof.hpp"
 
 namespace ctvae {

@@ -7,6 +7,7 @@
 // As torch ops that is ~20 elementwise launches per rung and as many again in autograd; here one launch each way (a workgroup
 // per sample, the row sum by shuffles).
 #include "common.hpp"
+#include "ops.hpp"
 #include "prof.hpp"
 
 namespace ctvae {

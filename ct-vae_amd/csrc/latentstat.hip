@@ -26,6 +26,7 @@
 // counts the elements whose mu or logvar is NaN or +-inf (exponent bits all ones); such values still go into the sums.  Thread 0
 // of the first of these workgroups adds B to rows[0].
 #include "common.hpp"
+#include "ops.hpp"
 #include "prof.hpp"
 
 namespace ctvae {

@@ -17,6 +17,7 @@
 // state after K samples is the same bits for every cut.  Its arithmetic is not contracted (every operation rounds on its own),
 // so the host can restate it operation by operation.
 #include "common.hpp"
+#include "ops.hpp"
 #include "prof.hpp"
 
 #include <cstdint>

@@ -4,6 +4,7 @@
 // finishing workgroup that adds the partials in double and emits the scalars.  HBM-bound:
 // algorithmic bytes = 2 * 4 * n (recons + input) + 2 * 4 * B * L.
 #include "common.hpp"
+#include "ops.hpp"
 #include "prof.hpp"
 
 namespace ctvae {

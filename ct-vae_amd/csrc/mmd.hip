@@ -10,6 +10,7 @@
 // pass, so the backward pass is a scaling by the incoming gradient.  Partial sums are combined in a fixed order:
 // bit-reproducible.
 #include "common.hpp"
+#include "ops.hpp"
 #include "prof.hpp"
 
 namespace ctvae {

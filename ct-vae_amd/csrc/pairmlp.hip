@@ -13,6 +13,7 @@
 //           dw2 / db2 leave as per-sample partials reduced by the caller.
 // Both are VALU kernels (≈7 instructions per (pair, h)); nothing of size N*N*H ever touches memory.
 #include "common.hpp"
+#include "ops.hpp"
 #include "phase.hpp"
 #include "prof.hpp"
 #include "satmath.hpp"

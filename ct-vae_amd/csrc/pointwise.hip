@@ -2,6 +2,7 @@
 // activation backward, Gaussian reparameterisation (vanilla_vae.py:107-117) and the flat fused Adam
 // update (experiment.py:158-160).  Roofline for all of them: bytes moved / 8 TB/s.
 #include "common.hpp"
+#include "ops.hpp"
 #include "prof.hpp"
 
 namespace ctvae {

@@ -5,6 +5,8 @@
 #include <string>
 #include <vector>
 
+#include "../../include/ctvae_hip.h"
+
 #include "common.hpp"
 #include "prof.hpp"
 

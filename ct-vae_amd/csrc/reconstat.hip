@@ -23,6 +23,7 @@
 // evaluated WITHOUT contraction (ssim_point): with a == b numerator and denominator are then the same bits, the map is exactly
 // 1.0 and so is the mean.
 #include "common.hpp"
+#include "ops.hpp"
 #include "prof.hpp"
 
 namespace ctvae {

@@ -14,6 +14,7 @@
 // derivatives P, Q, R of (alpha ssim + beta cs) w.r.t. mu1, G*(a a), G*(a b); grad a = G*P + 2 a G*Q + b G*R (G is symmetric, zero
 // padding on both sides) plus a quarter of the coarser level's gradient of the pixel's 2x2 block.  Bit-reproducible.
 #include "common.hpp"
+#include "ops.hpp"
 #include "prof.hpp"
 
 namespace ctvae {

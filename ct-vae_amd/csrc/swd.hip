@@ -6,6 +6,7 @@
 // the rank-wise term goes straight back to the sample it came from -- and the direction's partial sum.  A second launch sums
 // the partials in a fixed order and forms d swd / d z = (d swd / d projections) . W.  Deterministic, no atomics.
 #include "common.hpp"
+#include "ops.hpp"
 #include "prof.hpp"
 
 namespace ctvae {

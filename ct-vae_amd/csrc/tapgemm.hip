@@ -17,6 +17,7 @@
 // (register prefetch) and occupancy (small accumulators) hides the rest.  Epilogue fuses bias,
 // residual add, forward activation, or the multiplication by the previous layer's activation
 // derivative (backward).
+#include "convpaths.hpp"
 #include "prof.hpp"
 #include "pair.hpp"
 #include "tapgemm.hpp"
@@ -534,20 +535,6 @@ static int launch_masked(const TapGemmArgs& a, bool wt, bool avec, bool bvec, hi
   return 0;
 }
 
-bool upconv_supported(const ConvGeom& g);
-int upconv_rows(const ConvGeom& g);
-int launch_upconv_forward(const ConvGeom& g, const float* X, const float* W, const float* bias, float* S, int act,
-                          float* bn_part, hipStream_t st, const InXform* xf);
-bool img_enc_supported(const ConvGeom& g);
-int img_enc_rows(const ConvGeom& g);
-int launch_img_enc_forward(const ConvGeom& g, const float* X, const float* W, const float* bias, float* S, int act,
-                           float* bn_part, hipStream_t st);
-bool thin_forward_supported(const ConvGeom& g);
-int thin_bn_parts(const ConvGeom& g);
-int launch_thin_forward(const ConvGeom& g, const float* G, const float* W, const float* bias, const float* add,
-                        const float* mask, int mask_act, float* S, int act, float* bn_part, hipStream_t st,
-                        const InXform* xf);
-
 // tile shape and split-K factor a launch will use (mirrored by the BN-statistics consumers)
 void tapgemm_plan(const ConvGeom& g, size_t ws_floats, TapGemmPlan& p, bool paired) {
   const int Mc = g.B * g.Qh * g.Qw, N = g.sC;
@@ -617,10 +604,6 @@ void tapgemm_plan(const ConvGeom& g, size_t ws_floats, TapGemmPlan& p, bool pair
   p.bn_parts = p.mtiles * g.ncls;
 }
 
-bool img_dgrad_supported(const ConvGeom& g);
-int img_dgrad_rows(const ConvGeom& g);
-int launch_img_dgrad(const ConvGeom& g, const float* dY, const float* W, float* dX, const BnBwdFuse* bnb, hipStream_t st);
-
 // rows of the fused BN-backward partial table a dgrad launch of this geometry writes (0: this configuration cannot
 // fuse -- split-K keeps its epilogue in splitk_finish_kernel, the thin path has none)
 int tapgemm_bnb_rows(const ConvGeom& g, size_t ws_floats, bool paired) {
@@ -630,12 +613,6 @@ int tapgemm_bnb_rows(const ConvGeom& g, size_t ws_floats, bool paired) {
   if (plan.thin || plan.splitk > 1) return 0;
   return plan.bn_parts;
 }
-
-bool wino_supported(const ConvGeom& g, size_t ws_floats);
-int launch_wino_conv(const ConvGeom& g, const float* X, const float* Wp, const float* bias, float* Y, int act, float* ws,
-                     size_t ws_floats, hipStream_t st, const float* filters_ready, float* bwd_out, const float* add);
-
-bool wino_enabled();
 
 // a 1 x 1 layer on a 1 x 1 image (an nn.Linear) that the vector tile kernel runs unsplit: the only launch that honours out_pix
 bool out_pix_supported(const ConvGeom& g, size_t ws_floats, int out_pix) {

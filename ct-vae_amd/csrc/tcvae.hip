@@ -9,6 +9,7 @@
 // (max, sum) pairs for the D + 1 logsumexps, merged by shuffles and once through LDS; the backward pass recomputes M and has
 // one producer per output element (blocks [0,B): d/dz_i; blocks [B,2B): d/dmu_j, d/dlv_j).  D <= 32, B <= 4096.
 #include "common.hpp"
+#include "ops.hpp"
 #include "prof.hpp"
 
 namespace ctvae {

@@ -13,6 +13,7 @@
 //   * optional on-the-fly input transform a = act(x*scale[c] + shift[c]) while staging (fused BatchNorm apply).
 // The 3-channel-INPUT side keeps the masked MFMA path: broadcasting 3 values per tap through vector loads is TA-bound.
 #include "common.hpp"
+#include "convpaths.hpp"
 #include "prof.hpp"
 
 namespace ctvae {
@@ -321,16 +322,6 @@ static int launch_thin(ThinArgs& a, int nwg, hipStream_t st, const char* pname) 
   CTVAE_LAUNCH_CHECK();
   return 0;
 }
-
-bool img_conv_supported(const ConvGeom& g);
-int launch_img_forward(const ConvGeom& g, const float* X, const float* W, const float* bias, float* S, int act,
-                       const InXform* xf, hipStream_t st);
-int launch_img_wgrad(const ConvGeom& g, const float* X, const float* dY, float* ws, float** part_out, float** pbias_out,
-                     int* nparts, bool want_bias, const InXform* xf, hipStream_t st);
-
-bool upimg_supported(const ConvGeom& g);
-int launch_upimg_forward(const ConvGeom& g, const float* X, const float* Wp, const float* bias, float* Y, int act,
-                         hipStream_t st);
 
 int launch_thin_forward(const ConvGeom& g, const float* G, const float* W, const float* bias, const float* add,
                         const float* mask, int mask_act, float* S, int act, float* bn_part, hipStream_t st,

@@ -13,6 +13,7 @@
 //     straight into the MFMA B operand (128 B per pixel) and is reused by every tap of its class, x comes from LDS.
 // Fixed-order merges everywhere: bit-reproducible.
 #include "common.hpp"
+#include "convpaths.hpp"
 #include "phase.hpp"
 #include <type_traits>
 

@@ -13,6 +13,7 @@
 // writes 16 x 64 x 3 outputs as contiguous 12-byte pixels.  No MAC is spent on inserted zeros, none on the 61 unused
 // output channels a 64-wide GEMM tile would pad.
 #include "common.hpp"
+#include "convpaths.hpp"
 #include "prof.hpp"
 
 namespace ctvae {

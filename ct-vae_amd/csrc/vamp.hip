@@ -7,6 +7,7 @@
 // dimensions), keeps s[b,:] in LDS for the logsumexp and leaves the softmax weights for the backward pass, which has one
 // producer per output element (samples for z / mu / lv, components for pmu / plv): deterministic, no atomics.
 #include "common.hpp"
+#include "ops.hpp"
 #include "prof.hpp"
 
 namespace ctvae {

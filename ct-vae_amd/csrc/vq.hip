@@ -10,6 +10,7 @@
 //  * the reference's slice quirk is reproduced: codebook i reads channels [i, i+D/C) (mcq_vae.py:104,117).
 // All HBM/L2-bound; algorithmic bytes = latents read + quantized written + indices.
 #include "common.hpp"
+#include "ops.hpp"
 #include "prof.hpp"
 
 namespace ctvae {

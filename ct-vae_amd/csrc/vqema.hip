@@ -21,6 +21,7 @@
 // (fmaf(g, old, fl32((1-g) * acc)), the product formed in float64), E one division.  g and eps are by-value arguments, so
 // this launch is never captured.
 #include "common.hpp"
+#include "ops.hpp"
 #include "prof.hpp"
 
 namespace ctvae {

@@ -27,6 +27,7 @@
 // where those latents are.  The host has checked every entry; the kernel skips an entry outside the ranges all the same, so no
 // word outside the three buffers' listed rows is ever written.
 #include "common.hpp"
+#include "ops.hpp"
 #include "prof.hpp"
 
 namespace ctvae {

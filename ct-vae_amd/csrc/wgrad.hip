@@ -11,6 +11,7 @@
 #include <vector>
 
 #include "common.hpp"
+#include "convpaths.hpp"
 #include "prof.hpp"
 #include "finish.hpp"
 #include "pair.hpp"
@@ -244,16 +245,6 @@ int defer_begin(float* arena, size_t arena_floats) {
   return 0;
 }
 
-static int defer_run_pending(DeferCtx& d, hipStream_t st);
-
-int defer_flush(hipStream_t st) {
-  DeferCtx& d = defer_ctx();
-  if (!d.active) return kErrBadArg;
-  d.active = false;
-  d.cur = nullptr;
-  return defer_run_pending(d, st);
-}
-
 static int defer_run_pending(DeferCtx& d, hipStream_t st) {
   for (size_t i0 = 0; i0 < d.jobs.size(); i0 += kDeferJobsPerLaunch) {
     DeferTable t{};
@@ -274,6 +265,14 @@ static int defer_run_pending(DeferCtx& d, hipStream_t st) {
   }
   d.jobs.clear();
   return 0;
+}
+
+int defer_flush(hipStream_t st) {
+  DeferCtx& d = defer_ctx();
+  if (!d.active) return kErrBadArg;
+  d.active = false;
+  d.cur = nullptr;
+  return defer_run_pending(d, st);
 }
 
 // record one call's reductions instead of running them; false: this call is not being deferred (or must not be)
@@ -363,24 +362,6 @@ static int choose_splits(const ConvGeom& g, int KT, int NT, size_t ws_floats, in
   while (S > 1 && wgrad_workspace_floats(g, S) > ws_floats) --S;
   return S;
 }
-
-bool thin_wgrad_supported(const ConvGeom& g);
-size_t thin_wgrad_workspace_floats(const ConvGeom& g);
-int launch_thin_wgrad(const ConvGeom& g, const float* X, const float* dY, float* ws, float** part_out, float** pbias_out,
-                      int* nparts_w, int* nparts_b, bool want_bias, hipStream_t st, const InXform* xf);
-
-bool upconv_wgrad_supported(const ConvGeom& g);
-int launch_upconv_wgrad(const ConvGeom& g, const float* X, const float* dY, float* ws, float** part_out, float** pbias_out,
-                        int* nparts, bool want_bias, hipStream_t st, const DyXform* dyx, const InXform* xf);
-bool img_enc_supported(const ConvGeom& g);
-int launch_img_enc_wgrad(const ConvGeom& g, const float* X, const float* dY, float* ws, float** part_out, float** pbias_out,
-                         int* nparts, bool want_bias, hipStream_t st, const DyXform* dyx);
-
-bool wino_wgrad_supported(const ConvGeom& g, size_t ws_floats, int* splits);
-int launch_wino_wgrad(const ConvGeom& g, const float* X, const float* dY, float* ws, size_t ws_floats, int* nparts,
-                      bool want_bias, float** pbias_out, hipStream_t st);
-
-bool wino_enabled();
 
 int launch_wgrad(const ConvGeom& g, const float* X, const float* dY, float* dW, float* dbias, float* ws,
                  size_t ws_bytes, int accumulate, hipStream_t st, const InXform* xf, const DyXform* dyx, PairCtx* pc) {

@@ -20,6 +20,7 @@
 // The data gradient of the same layer is the same computation with the filter taps mirrored and Ci/Co swapped: only
 // the weight transform differs (tap table + transposed read).
 #include "common.hpp"
+#include "convpaths.hpp"
 #include "prof.hpp"
 
 namespace ctvae {
