@@ -1182,6 +1182,32 @@ int ctvae_vq_ema_update(float* codebooks, float* N, float* M, long* acc_n, float
   return launch_vq_ema_update(codebooks, N, M, acc_n, acc_s, C, K, Dc, decay, eps, (hipStream_t)stream);
 }
 
+int ctvae_code_prior_sample_max_history(void) { return code_prior_sample_max_history(); }
+
+int ctvae_code_prior_count(const long* inds, long* pos, long* left, long* up, long* prev, long* invalid, int B, int C, int H, int W,
+                           int K, void* stream) {
+  return launch_code_prior_count(inds, pos, left, up, prev, invalid, B, C, H, W, K, (hipStream_t)stream);
+}
+
+int ctvae_code_prior_score(const long* inds, const long* pos, const long* left, const long* up, const long* prev,
+                           const long* pos_tot, const long* left_tot, const long* up_tot, const long* prev_tot, const double* lambda,
+                           double* logp, double* resp, int* bad, int B, int C, int H, int W, int K, void* stream) {
+  return launch_code_prior_score(inds, pos, left, up, prev, pos_tot, left_tot, up_tot, prev_tot, lambda, logp, resp, bad, B, C, H, W,
+                                 K, (hipStream_t)stream);
+}
+
+int ctvae_code_prior_sample(const long* pos, const long* left, const long* up, const long* prev, const long* pos_tot,
+                            const long* left_tot, const long* up_tot, const long* prev_tot, const double* lambda, const double* u,
+                            long* inds, int n, int C, int H, int W, int K, void* stream) {
+  return launch_code_prior_sample(pos, left, up, prev, pos_tot, left_tot, up_tot, prev_tot, lambda, u, inds, n, C, H, W, K,
+                                  (hipStream_t)stream);
+}
+
+int ctvae_code_prior_embed(const long* inds, const float* codebooks, float* out, int n, int C, int H, int W, int K, int Dc,
+                           void* stream) {
+  return launch_code_prior_embed(inds, codebooks, out, n, C, H, W, K, Dc, (hipStream_t)stream);
+}
+
 size_t ctvae_grad_segment_chunk_floats(void) { return grad_segment_chunk_floats(); }
 
 int ctvae_grad_segment_stats(const float* grads, long n, float scale, float norm_type, const long* segments, int nseg,

@@ -262,6 +262,19 @@ int launch_vq_ema_stats(const float* lat, const long* inds_, long* acc_n, float*
 int launch_vq_ema_update(float* cb, float* N, float* M, long* acc_n, float* acc_s, int C, int K, int Dc, float decay, float eps,
                          hipStream_t st);
 
+// codeprior.hip
+int code_prior_sample_max_history();
+int launch_code_prior_count(const long* inds, long* pos, long* left, long* up, long* prev, long* invalid, int B, int C, int H, int W,
+                            int K, hipStream_t st);
+int launch_code_prior_score(const long* inds, const long* pos, const long* left, const long* up, const long* prev,
+                            const long* pos_tot, const long* left_tot, const long* up_tot, const long* prev_tot, const double* lambda,
+                            double* logp, double* resp, int* bad, int B, int C, int H, int W, int K, hipStream_t st);
+int launch_code_prior_sample(const long* pos, const long* left, const long* up, const long* prev, const long* pos_tot,
+                             const long* left_tot, const long* up_tot, const long* prev_tot, const double* lambda, const double* u,
+                             long* inds, int n, int C, int H, int W, int K, hipStream_t st);
+int launch_code_prior_embed(const long* inds, const float* codebooks, float* out, int n, int C, int H, int W, int K, int Dc,
+                            hipStream_t st);
+
 // vqusage.hip
 size_t vq_usage_pass_indices();
 int launch_vq_usage(const long* inds, long* counts, long* invalid, int B, int C, int HW, int K, hipStream_t st);

@@ -167,6 +167,18 @@ record and the JSONL log (what has no image to stand on is left out) and, with a
 random stream and adds nothing to checkpoints, so training is bit for bit the same with and without it.  Refused when the
 experiment is built: a bad value, ``sigma: mse`` (the command's alone) and any other model.  Without the key there is no buffer,
 no launch, no file and no log key.
+``exp_params.code_prior`` (a mapping with ``type: markov`` and the optional ``em_iters`` / ``uniform_floor``;
+``codeprior.code_prior_setting``): an interpolated Markov prior over the code grids of the models in
+``codeprior.CODE_PRIOR_MODELS``, on rank 0 with no collective, a report of ``_validate``.  Armed, the index buffer
+(``codeprior.CodeGridBuffer``) is cleared and the quantiser's ``usage_observer`` hands it the indices of every validation search --
+chained behind ``codebook_stats``' observer when that is armed too, so both see every search; ``write_code_prior`` counts the rows
+with an even ordinal (``ctvae_code_prior_count``), fits lambda on the odd ones (``ctvae_code_prior_score`` per EM round) and reports
+THOSE rows: ``val_code_prior_nats`` / ``_bits`` / ``_uniform_nats`` / ``_nats_<c>`` / ``_weight_<expert>`` / ``_rows`` / ``_invalid`` (fewer
+than 2 rows: ``val_code_prior_error``) and, with a ``sample_dir``, ``Priors/code_prior_<name>_Epoch_<e>.npz``; with ``val_sampling``
+``sample_code_prior_images`` writes ``Samples/sample_code_prior_<name>_Epoch_<e>.png`` from a generator of its own, seeded from
+``epoch_seed(e)``, next to the unchanged ``sample_<name>_...png``.  It adds nothing to checkpoints, moves no random stream and
+writes no model state, so training is bit for bit the same with and without it.  Refused when the experiment is built: a bad
+value and any other model.  Without the key there is no buffer, no launch, no file and no log key.
 """
 import contextlib
 import json
@@ -175,7 +187,7 @@ import time
 
 import torch
 
-from . import causalgraph, imagegrid
+from . import causalgraph, codeprior, imagegrid
 from . import kernels as K
 from .ddp import GradBucketAllReduce
 from .evalrun import eval_mode, seeded_torch_rng, unpack_batch
@@ -365,6 +377,15 @@ class VAEXperiment:
                 cfg = self.loglik_cfg      # (pixels None: the first batch says how many elements an image has)
                 self.val_loglik = loglik.ImportanceLogLik(vae_model.latent_dim, None, cfg["sigma"], cfg["samples"], cfg["chunk"],
                                                           next(vae_model.parameters()).device)
+        # code prior (codeprior.MarkovCodePrior): validated on every rank, the index buffer on rank 0 only
+        self.code_prior = codeprior.code_prior_setting(params.get("code_prior"))
+        self.val_code_prior = None              # the epoch's validation indices (codeprior.CodeGridBuffer)
+        self.last_code_prior = None             # the prior the last validation epoch fitted (None: none, or too few rows)
+        if self.code_prior is not None:
+            if not codeprior.prior_supported(vae_model):
+                raise ValueError(codeprior.needs_supported_model(vae_model))
+            if self._rank0():
+                self.val_code_prior = codeprior.CodeGridBuffer(next(vae_model.parameters()).device)
         # reconstruction quality (reconstats.ReconStats): validated on every rank, built on rank 0 only; CT-MCQ-VAE gets one
         # accumulator per picture mode
         self.recon_stats, self.recon_range, self.recon_worst = recon_settings(params)
@@ -932,6 +953,48 @@ class VAEXperiment:
             imagegrid.save_image(self.model.decode(z), p, normalize=True, nrow=12)
         return p
 
+    def write_code_prior(self, grids, epoch: int) -> dict:
+        """What ``code_prior`` leaves of one validation epoch.  The rows of ``grids`` (a ``codeprior.CodeGridBuffer``) with an even
+        ordinal are counted, lambda is fitted on the rows with an odd ordinal, and THOSE rows are reported (the weights have seen
+        them; ``fit_code_prior``'s test-split number is the clean one): ``val_code_prior_nats`` (mean nats per code),
+        ``val_code_prior_bits``, ``val_code_prior_uniform_nats`` (ln K), ``val_code_prior_nats_<c>`` per codebook,
+        ``val_code_prior_weight_<expert>`` (the mean over the codebooks), ``val_code_prior_rows`` (the rows counted) and
+        ``val_code_prior_invalid``; also one JSONL line, and with a ``sample_dir`` ``Priors/code_prior_<name>_Epoch_<e>.npz``.  Fewer
+        than 2 rows leave ``val_code_prior_error``, a string, in place of all that, and the epoch goes on."""
+        cfg = self.code_prior
+        X = grids.view()
+        self.last_code_prior = None
+        if X.size(0) < 2:
+            return self._write_epoch_record({"val_code_prior_error": f"a code prior needs at least 2 rows (one to count, one to "
+                                                                     f"fit the weights on), got {X.size(0)}"})
+        prior = codeprior.MarkovCodePrior(int(self.model.num_embeddings), *grids.shape, grids.device)
+        try:
+            codeprior.fit_halves(prior, X, cfg["em_iters"], cfg["uniform_floor"])
+        except ValueError as e:
+            return self._write_epoch_record({"val_code_prior_error": str(e)})
+        self.last_code_prior = prior
+        rec = codeprior.record(prior.summary(X[1::2].contiguous()), prior.rows, prior.invalid)
+        if self.sample_dir is not None:
+            d = os.path.join(self.sample_dir, codeprior.CODE_PRIOR_DIR)
+            os.makedirs(d, exist_ok=True)
+            prior.save(os.path.join(d, f"code_prior_{self.run_name}_Epoch_{epoch}.npz"))
+        return self._write_epoch_record(rec)
+
+    def sample_code_prior_images(self, n: int, epoch: int):
+        """``Samples/sample_code_prior_<name>_Epoch_<e>.png`` next to ``sample_images``' own samples: ``n`` ancestral draws from the
+        prior this epoch fitted, decoded.  The draws come from a generator of their own: no other random stream moves.  Returns
+        the path, or None when this epoch fitted no prior."""
+        if self.last_code_prior is None:
+            return None
+        g = torch.Generator(device=self.last_code_prior.device)
+        g.manual_seed(self.epoch_seed(epoch))
+        os.makedirs(os.path.join(self.sample_dir, "Samples"), exist_ok=True)
+        p = os.path.join(self.sample_dir, "Samples", f"sample_code_prior_{self.run_name}_Epoch_{epoch}.png")
+        with torch.no_grad():
+            inds = self.last_code_prior.sample(n, g)
+            imagegrid.save_image(self.last_code_prior.decode_samples(self.model, inds), p, normalize=True, nrow=12)
+        return p
+
     def write_recon_stats(self, accumulators, epoch: int) -> dict:
         """What ``recon_stats`` leaves of one validation epoch: per accumulator one copy, the ``val_recon_*`` scalars
         (``reconstats.summarize``; what has no image to stand on is left out), also as one JSONL line, and with a ``sample_dir`` and
@@ -1060,11 +1123,31 @@ class VAEXperiment:
         with self._observing_results(observe):
             yield lambda: self.write_loglik(acc, epoch)
 
+    @contextlib.contextmanager
+    def _code_prior_report(self, epoch):
+        """The indices of every validation search -- a tensor the quantiser already holds -- are copied into the index buffer.
+        The observer that is already set (``codebook_stats``') keeps seeing every search, before this one."""
+        self.val_code_prior.clear()
+        vq = self.model.vq_layer
+        before = vq.usage_observer
+
+        def observe(inds, latents):
+            if before is not None:
+                before(inds, latents)
+            self.val_code_prior.append(inds)
+
+        vq.usage_observer = observe
+        try:
+            yield lambda: self.write_code_prior(self.val_code_prior, epoch)
+        finally:
+            vq.usage_observer = before
+
     def _val_reports(self):
         """The reports this run has on this rank, in the order of their keys in the epoch record."""
         reports = ((self._graph_report, self.val_graphs and self._rank0()), (self._codebook_report, self.val_codebook is not None),
                    (self._latent_report, self.val_latents is not None), (self._recon_report, self.val_recon is not None),
-                   (self._prior_report, self.val_prior is not None), (self._loglik_report, self.val_loglik is not None))
+                   (self._prior_report, self.val_prior is not None), (self._loglik_report, self.val_loglik is not None),
+                   (self._code_prior_report, self.val_code_prior is not None))         # (behind _codebook_report: it chains)
         return [report for report, on in reports if on]
 
     def _validate(self, epoch, val_batches, test_batches):
@@ -1090,6 +1173,8 @@ class VAEXperiment:
                 self.sample_images(first, epoch)
                 if self.val_prior is not None:
                     self.sample_mixture_images(min(32, unpack_batch(first)[0].size(0)), epoch)
+                if self.val_code_prior is not None:
+                    self.sample_code_prior_images(min(32, unpack_batch(first)[0].size(0)), epoch)
         return rec
 
     def fit(self, train_batches, val_batches=None, max_epochs=1, on_epoch_end=None, start_epoch=0, test_batches=None):

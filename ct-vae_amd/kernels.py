@@ -3489,3 +3489,188 @@ def loglik_merge(lw, S, state, flags, row0):
     _req_cuda(lw, state, flags)
     if B:
         native.call("ctvae_loglik_merge", lw.data_ptr(), B, S, state.data_ptr(), flags.data_ptr(), row0, cap)
+
+
+# ---------------------------------------------------------------------------------------------------
+# interpolated Markov code prior (csrc/codeprior.hip; codeprior.MarkovCodePrior)
+# ---------------------------------------------------------------------------------------------------
+CODE_PRIOR_EXPERTS = ("uniform", "position", "left", "up", "previous")
+CODE_PRIOR_TABLES = ("pos", "left", "up", "prev")
+CODE_PRIOR_MAX_K = 512
+CODE_PRIOR_MAX_TOTAL = 1 << 53               # a row total must stay below: it is converted to float64 exactly
+
+
+def code_prior_sample_max_history() -> int:
+    """The W * C the sampler covers: the row of context codes it keeps in LDS."""
+    return int(native.load().ctvae_code_prior_sample_max_history())
+
+
+def _cp_tensor(what, name, t, dtype, shape=None):
+    """A dense device tensor of ``dtype`` (and ``shape``), or a ValueError that names the argument."""
+    if not torch.is_tensor(t) or t.dtype != dtype:
+        raise ValueError(f"{what}: {name} must be a {dtype} tensor, got {getattr(t, 'dtype', type(t).__name__)}")
+    if shape is not None and tuple(t.shape) != tuple(shape):
+        raise ValueError(f"{what}: {name} must be {list(shape)}, got {list(t.shape)}")
+    if not t.is_contiguous():
+        raise ValueError(f"{what}: {name} must be contiguous")
+    if not t.is_cuda:
+        raise ValueError(f"{what}: {name} must be a device tensor (there is no CPU fallback)")
+
+
+def _cp_grid(what, name, inds):
+    """(B, C, H, W) of an int64 index grid [B, C, H, W] with no empty extent."""
+    _cp_tensor(what, name, inds, torch.int64)
+    if inds.dim() != 4 or inds.numel() == 0:
+        raise ValueError(f"{what}: {name} must be [B, C, H, W] with no empty extent, got {list(inds.shape)}")
+    if inds.numel() >= 1 << 31:
+        raise ValueError(f"{what}: {name} holds {inds.numel()} tokens, one launch covers fewer than 2^31")
+    return tuple(inds.shape)
+
+
+def code_prior_limits(what, K, C, H, W):
+    for name, v in (("K", K), ("C", C), ("H", H), ("W", W)):
+        if isinstance(v, bool) or not isinstance(v, int):
+            raise ValueError(f"{what}: {name} must be an integer, got {v!r}")
+    if not 1 <= K <= CODE_PRIOR_MAX_K:
+        raise ValueError(f"{what}: K must lie in 1..{CODE_PRIOR_MAX_K}, got {K}")
+    for name, v in (("C", C), ("H", H), ("W", W)):
+        if v < 1:
+            raise ValueError(f"{what}: {name} must be at least 1, got {v}")
+
+
+def _cp_tables(what, tables, C, H, W, device):
+    """The checks of the four count tables ``(pos, left, up, prev)``; returns K."""
+    if not isinstance(tables, (tuple, list)) or len(tables) != 4:
+        raise ValueError(f"{what}: tables must be the four tensors (pos, left, up, prev)")
+    pos = tables[0]
+    if not torch.is_tensor(pos) or pos.dim() != 3:
+        raise ValueError(f"{what}: pos must be [C, H*W, K], got {list(getattr(pos, 'shape', ()))}")
+    K = int(pos.size(2))
+    code_prior_limits(what, K, C, H, W)
+    shapes = ((C, H * W, K),) + ((C, K + 1, K),) * 3
+    for name, t, shape in zip(CODE_PRIOR_TABLES, tables, shapes):
+        _cp_tensor(what, name, t, torch.int64, shape)
+        if t.device != device:
+            raise ValueError(f"{what}: {name} lies on {t.device}, not on {device}")
+    return K
+
+
+def _cp_totals(what, totals, C, H, W, K, device):
+    if not isinstance(totals, (tuple, list)) or len(totals) != 4:
+        raise ValueError(f"{what}: totals must be the four tensors (pos_tot, left_tot, up_tot, prev_tot)")
+    shapes = ((C, H * W),) + ((C, K + 1),) * 3
+    for name, t, shape in zip(CODE_PRIOR_TABLES, totals, shapes):
+        _cp_tensor(what, name + "_tot", t, torch.int64, shape)
+        if t.device != device:
+            raise ValueError(f"{what}: {name}_tot lies on {t.device}, not on {device}")
+    top = torch.stack([t.max() for t in totals])           # one read for the four tables
+    low = torch.stack([t.min() for t in totals])
+    top, low = top.tolist(), low.tolist()
+    for name, hi, lo in zip(CODE_PRIOR_TABLES, top, low):
+        if hi >= CODE_PRIOR_MAX_TOTAL or lo < 0:
+            raise ValueError(f"{what}: {name}_tot must lie in [0, 2^53), got a row total of {hi if hi >= CODE_PRIOR_MAX_TOTAL else lo}")
+
+
+def _cp_lambda(what, lam, C, device):
+    _cp_tensor(what, "lambda", lam, torch.float64, (C, len(CODE_PRIOR_EXPERTS)))
+    if lam.device != device:
+        raise ValueError(f"{what}: lambda lies on {lam.device}, not on {device}")
+
+
+def code_prior_tables(K, C, H, W, device):
+    """Zeroed ``(pos [C, H*W, K], left, up, prev [C, K+1, K])`` int64 tables and the ``invalid`` word."""
+    code_prior_limits("code_prior_tables", K, C, H, W)
+    z = lambda *s: torch.zeros(*s, dtype=torch.int64, device=device)
+    return (z(C, H * W, K), z(C, K + 1, K), z(C, K + 1, K), z(C, K + 1, K)), z(1)
+
+
+def code_prior_totals(tables):
+    """The row totals of the four tables: exact int64 sums."""
+    return tuple(t.sum(dim=2) for t in tables)
+
+
+def code_prior_count(inds, tables, invalid):
+    """``ctvae_code_prior_count``: every token of ``inds`` (int64 [B, C, H, W], as ``vq_compute_inds`` returns it) is added to the
+    four int64 tables ``(pos [C, H*W, K], left, up, prev [C, K+1, K])``; a token whose own code or a context code lies outside
+    [0, K) adds 1 to ``invalid`` (one int64 word) instead.  A wrong dtype, shape, device or contiguity is a ValueError that names
+    the argument, before any launch."""
+    what = "code_prior_count"
+    B, C, H, W = _cp_grid(what, "inds", inds)
+    K = _cp_tables(what, tables, C, H, W, inds.device)
+    _cp_tensor(what, "invalid", invalid, torch.int64)
+    if invalid.numel() != 1 or invalid.device != inds.device:
+        raise ValueError(f"{what}: invalid must be one int64 word on {inds.device}, got {list(invalid.shape)} on {invalid.device}")
+    native.call("ctvae_code_prior_count", inds.data_ptr(), *(t.data_ptr() for t in tables), invalid.data_ptr(), B, C, H, W, K)
+
+
+def code_prior_score(inds, tables, totals, lam):
+    """``ctvae_code_prior_score``: ``(logp float64 [B, C], resp float64 [B, C, 5], bad int32 [B])`` of ``inds`` int64 [B, C, H, W]
+    under the tables, their row ``totals`` (int64, below 2^53) and ``lam`` float64 [C, 5]."""
+    what = "code_prior_score"
+    B, C, H, W = _cp_grid(what, "inds", inds)
+    K = _cp_tables(what, tables, C, H, W, inds.device)
+    _cp_totals(what, totals, C, H, W, K, inds.device)
+    _cp_lambda(what, lam, C, inds.device)
+    J = len(CODE_PRIOR_EXPERTS)
+    logp = torch.empty(B, C, dtype=torch.float64, device=inds.device)
+    resp = torch.empty(B, C, J, dtype=torch.float64, device=inds.device)
+    bad = torch.empty(B, dtype=torch.int32, device=inds.device)
+    native.call("ctvae_code_prior_score", inds.data_ptr(), *(t.data_ptr() for t in tables), *(t.data_ptr() for t in totals),
+                lam.data_ptr(), logp.data_ptr(), resp.data_ptr(), bad.data_ptr(), B, C, H, W, K)
+    return logp, resp, bad
+
+
+def code_prior_sample(tables, totals, lam, u, H, W):
+    """``ctvae_code_prior_sample``: int64 ``inds`` [n, C, H, W] from ``u`` float64 [n, H*W, C, 2] in [0, 1)."""
+    what = "code_prior_sample"
+    _cp_tensor(what, "u", u, torch.float64)
+    if u.dim() != 4 or u.size(3) != 2 or u.numel() == 0:
+        raise ValueError(f"{what}: u must be [n, H*W, C, 2] with no empty extent, got {list(u.shape)}")
+    n, HW, C = int(u.size(0)), int(u.size(1)), int(u.size(2))
+    for name, v in (("H", H), ("W", W)):
+        if isinstance(v, bool) or not isinstance(v, int) or v < 1:
+            raise ValueError(f"{what}: {name} must be an integer of at least 1, got {v!r}")
+    if H * W != HW:
+        raise ValueError(f"{what}: u must be [n, H*W, C, 2] for H={H}, W={W}, got {list(u.shape)}")
+    if u.numel() // 2 >= 1 << 31:
+        raise ValueError(f"{what}: u asks for {u.numel() // 2} tokens, one launch covers fewer than 2^31")
+    K = _cp_tables(what, tables, C, H, W, u.device)
+    if W * C > code_prior_sample_max_history():
+        raise ValueError(f"{what}: W * C = {W * C} is not covered: the sampler keeps a row of at most "
+                         f"{code_prior_sample_max_history()} context codes")
+    _cp_totals(what, totals, C, H, W, K, u.device)
+    _cp_lambda(what, lam, C, u.device)
+    if u.data_ptr() % 16:
+        raise ValueError(f"{what}: u must start on a 16-byte boundary")
+    inds = torch.empty(n, C, H, W, dtype=torch.int64, device=u.device)
+    native.call("ctvae_code_prior_sample", *(t.data_ptr() for t in tables), *(t.data_ptr() for t in totals), lam.data_ptr(),
+                u.data_ptr(), inds.data_ptr(), n, C, H, W, K)
+    return inds
+
+
+def code_prior_embed(inds, codebooks):
+    """``ctvae_code_prior_embed``: fp32 NHWC [n, H, W, C * Dc] with code ``c`` in channels [c * Dc, (c + 1) * Dc), a copy of the rows
+    of ``codebooks`` -- fp32 [C, K, Dc], or the list of C [K, Dc] weights stored back to back that
+    ``MultipleCodebookVectorQuantizer._codebooks()`` checks."""
+    what = "code_prior_embed"
+    n, C, H, W = _cp_grid(what, "inds", inds)
+    if isinstance(codebooks, (tuple, list)):
+        if len(codebooks) != C:
+            raise ValueError(f"{what}: codebooks holds {len(codebooks)} codebooks, inds has C={C}")
+        for i, w in enumerate(codebooks):
+            _cp_tensor(what, f"codebooks[{i}]", w, torch.float32, tuple(codebooks[0].shape))
+            if w.dim() != 2 or w.data_ptr() != codebooks[0].data_ptr() + i * codebooks[0].numel() * 4:
+                raise ValueError(f"{what}: codebooks[{i}] must be [K, Dc] and stored back to back with the others")
+        K, Dc = codebooks[0].shape
+        first = codebooks[0]
+    else:
+        _cp_tensor(what, "codebooks", codebooks, torch.float32)
+        if codebooks.dim() != 3 or codebooks.size(0) != C or codebooks.numel() == 0:
+            raise ValueError(f"{what}: codebooks must be [C={C}, K, Dc], got {list(codebooks.shape)}")
+        _, K, Dc = codebooks.shape
+        first = codebooks
+    if first.device != inds.device:
+        raise ValueError(f"{what}: codebooks lies on {first.device}, not on {inds.device}")
+    out = torch.empty(n, H, W, C * Dc, dtype=torch.float32, device=inds.device)
+    native.call("ctvae_code_prior_embed", inds.data_ptr(), first.data_ptr(), out.data_ptr(), n, C, H, W, int(K), int(Dc))
+    return out

@@ -69,6 +69,13 @@ every validation epoch (experiment.py, latentprior.py): ``val_prior_mixture_logl
 ``_rows`` / ``_nonfinite`` in the epoch records and ``metrics_rank0.jsonl``, ``Priors/latent_prior_<name>_Epoch_<e>.npz`` and, with
 ``val_sampling``, ``Samples/sample_mixture_<name>_Epoch_<e>.png`` in the log directory; ``python -m ctvae_amd.fit_prior`` does the same
 for a checkpoint over the training split.  A refused value or model is a SystemExit that names ``exp_params.sample_prior``.
+``exp_params.code_prior: {type: markov}`` (with ``em_iters``, an int >= 1, default 20, and ``uniform_floor``, a float inside (0, 1),
+default 1e-3) fits an interpolated Markov prior to the validation code grids of MCQVAE / VQVAE in every validation epoch
+(experiment.py, codeprior.py): ``val_code_prior_nats`` / ``_bits`` / ``_uniform_nats`` / ``_nats_<c>`` / ``_weight_<expert>`` / ``_rows`` /
+``_invalid`` in the epoch records and ``metrics_rank0.jsonl``, ``Priors/code_prior_<name>_Epoch_<e>.npz`` and, with ``val_sampling``,
+``Samples/sample_code_prior_<name>_Epoch_<e>.png`` in the log directory; ``python -m ctvae_amd.fit_code_prior`` does the same for a
+checkpoint over the training split and scores the test split.  A refused value or model is a SystemExit that names
+``exp_params.code_prior``.
 ``exp_params.recon_stats: true`` (with ``recon_stats_range``, the data range R of the pictures, a float > 0, default 1.0, and
 ``recon_stats_worst``, an integer 0 <= K <= 32, default 8) adds the reconstruction quality per validation image to every validation
 epoch: ``val_recon_psnr`` / ``_ssim`` / ``_mae`` / ``_max_err``, the 5th percentiles and minima ``_psnr_p05`` / ``_ssim_p05`` / ``_psnr_min``
@@ -381,6 +388,21 @@ def exp_sample_prior(config):
     return cfg
 
 
+def exp_code_prior(config):
+    """``exp_params.code_prior`` as None (absent: off) or the complete mapping (``codeprior.code_prior_setting``).  A refused value
+    and a model the prior does not serve are a SystemExit that names the key."""
+    from . import codeprior
+    try:
+        cfg = codeprior.code_prior_setting(config['exp_params'].get('code_prior'))
+    except ValueError as e:
+        raise SystemExit(f"exp_params.{e}")
+    name = config['model_params'].get('name')
+    cls = vae_models.get(name)
+    if cfg is not None and (cls is None or not codeprior.prior_supported(cls)):
+        raise SystemExit(f"exp_params.{codeprior.needs_supported_model(cls, name=repr(name))} (model_params.name)")
+    return cfg
+
+
 def exp_val_loglik(config):
     """``exp_params.val_loglik`` as None (absent: off) or the complete mapping (``loglik.loglik_setting``).  A refused value and a
     model the estimate does not serve are a SystemExit that names the key."""
@@ -475,6 +497,7 @@ def main(argv=None):
     recon_on, _, _ = exp_recon_stats(config)               # likewise
     exp_sample_prior(config)                               # likewise
     exp_val_loglik(config)                                 # likewise
+    exp_code_prior(config)                                 # likewise
 
     rank =int(os.environ.get("RANK", "0"))
     world = int(os.environ.get("WORLD_SIZE", "1"))

@@ -1,5 +1,5 @@
 """The front end of the commands that work on a trained checkpoint (``apply_action``, ``causal_graph``, ``latent_stats``,
-``recon_stats``, ``fit_prior``, ``log_likelihood``): the arguments they share and the way from those to a model with its weights and its data.
+``recon_stats``, ``fit_prior``, ``log_likelihood``, ``fit_code_prior``): the arguments they share and the way from those to a model with its weights and its data.
 
 A command's ``main`` reads, in this order: ``add_arguments`` and its own ``ap.add_argument`` lines; ``configure``, which reads the
 YAML and refuses a model the command does not serve -- host only; the checks of its own flags; ``load``, which refuses a bad

@@ -959,6 +959,43 @@ int ctvae_vq_ema_update(float* codebooks, float* N, float* M, long* acc_n, float
 int ctvae_vq_lookup_commit(const float* latents, const float* codebooks, const int64_t* inds, float* quantized, float* vq_loss,
                            float beta, int B, int HW, int D, int K, int C, float* ws, size_t ws_bytes, void* stream);
 
+/* Interpolated Markov prior over the code grids of the quantising models (exp_params.code_prior; codeprior.py).  An image is
+ * int64 codes i[c][h][w] in [0, K); tokens are ordered raster over (h, w), codebooks innermost.  p(k | context) =
+ * sum_j lambda[c][j] P_j(k | row_j) over J = 5 experts in this order: uniform (1/K), position (row h*W + w of pos[C][H*W][K]),
+ * left (row i[c][h][w-1] of left[C][K+1][K], the boundary row K when w = 0), up (i[c][h-1][w], K when h = 0; up[C][K+1][K]),
+ * previous codebook (i[c-1][h][w], K when c = 0; prev[C][K+1][K]).  P_j(k | row) = count[row][k] / total[row]; a row whose
+ * total is 0 is 1/K.  The tables and their row totals (pos_tot[C][H*W], left_tot / up_tot / prev_tot [C][K+1]) are int64,
+ * lambda is float64 [C][5].  Covered: 1 <= K <= 512, C, H, W >= 1, at most 2^31 - 1 tokens per launch; totals below 2^53 (the
+ * caller's to check).  Everything else returns the bad-argument code without a launch.  Pointers and shape integers only.
+ *   ctvae_code_prior_count   adds every token of inds [B][C][H][W] to the four tables.  Integer atomics only: exact,
+ *                            independent of the order; two calls accumulate.  A token whose own code or any context code lies
+ *                            outside [0, K) adds 1 to the int64 word `invalid` and is written nowhere else.
+ *   ctvae_code_prior_score   logp[b][c] = sum of log p over the tokens of codebook c of image b, resp[b][c][j] = sum of the
+ *                            responsibilities r_j = lambda_j P_j / p over the same tokens (float64), bad[b] (int32) = 1 when the
+ *                            image holds an index outside [0, K): its logp and resp are then zeros.  One workgroup per image,
+ *                            float64 throughout, a fixed order of additions and no float atomic: a row's result does not depend
+ *                            on the batch it arrived in.
+ *   ctvae_code_prior_sample  inds [n][C][H][W] by ancestral sampling from u float64 [n][H*W][C][2] (16-byte aligned): per token,
+ *                            the expert is the smallest j with u1 < lambda[c][0] + ... + lambda[c][j] (added left to right; J-1
+ *                            when none); expert 0 or a row of total 0 gives min(K-1, floor(u2 * K)); otherwise t =
+ *                            min(total-1, floor(u2 * (double)total)) and the code is the smallest whose inclusive cumulative
+ *                            count exceeds t.  One multiplication per decision, nothing to contract: a float64 restatement
+ *                            gives the same integers.  One wavefront per image; W * C <=
+ *                            ctvae_code_prior_sample_max_history() (the row of context codes it keeps in LDS).
+ *   ctvae_code_prior_embed   out[n][h][w][c*Dc + d] = codebooks[c][inds[n][c][h][w]][d] as raw 32-bit words (codebooks [C][K][Dc]
+ *                            back to back, out fp32 NHWC [n][H][W][C*Dc]); an index outside [0, K) gives zeros. */
+int ctvae_code_prior_sample_max_history(void);
+int ctvae_code_prior_count(const long* inds, long* pos, long* left, long* up, long* prev, long* invalid, int B, int C, int H, int W,
+                           int K, void* stream);
+int ctvae_code_prior_score(const long* inds, const long* pos, const long* left, const long* up, const long* prev,
+                           const long* pos_tot, const long* left_tot, const long* up_tot, const long* prev_tot, const double* lambda,
+                           double* logp, double* resp, int* bad, int B, int C, int H, int W, int K, void* stream);
+int ctvae_code_prior_sample(const long* pos, const long* left, const long* up, const long* prev, const long* pos_tot,
+                            const long* left_tot, const long* up_tot, const long* prev_tot, const double* lambda, const double* u,
+                            long* inds, int n, int C, int H, int W, int K, void* stream);
+int ctvae_code_prior_embed(const long* inds, const float* codebooks, float* out, int n, int C, int H, int W, int K, int Dc,
+                           void* stream);
+
 /* Gradient tracking: per-parameter norms and 64-bin histograms from the flat gradient buffer (Lightning's track_grad_norm, wandb's
  * watch).  `grads` (n floats) is read only.  A segment is five 64-bit words (base, rows, period, col_lo, width) and names the
  * elements base + r * period + col_lo + c, r < rows, c < width (a contiguous parameter: one row; the heads of a grouped Linear
