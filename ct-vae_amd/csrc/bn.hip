@@ -14,6 +14,7 @@
 #include "finish.hpp"
 #include "pair.hpp"
 #include "prof.hpp"
+#include "bnowner.hpp"
 
 namespace ctvae {
 // d act / d t of a launch-uniform activation at pre-activation t, for element-wise kernels: identity / LeakyReLU / ReLU as one
@@ -580,23 +581,14 @@ __device__ __forceinline__ void slice_sum4(f32x4 (&v)[CPW], const float* __restr
   }
 }
 
-// Channel group of a workgroup.  The groups of one 128-byte line of an NHWC row (32 channels) each write / read 8 or 16 bytes
-// of it: dealt to the XCDs in launch order (id % 8) they would leave pieces of every line in eight L2s -- partial-line
-// write-backs and eight fills per line.  Whole lines per XCD instead: id = (line % 8) + 8 * (slot + slots * (line / 8)).
-__device__ __forceinline__ int fused_group(int id, int C, int cpw) {
-  const int slots = 32 / cpw, lines = C / 32;
-  if (lines == 0 || lines % 8 != 0) return id;   // fewer than 32 channels: one partial line, nothing to deal out
-  const int x = id & 7, t = id >> 3, slot = t % slots, jh = t / slots;
-  return (jh * 8 + x) * slots + slot;
-}
-
-// workgroup = CPW channels x all R rows (R <= 4 * TPB); thread = four consecutive rows of each of its CPW channels
+// workgroup = CPW channels x all R rows (R <= 4 * TPB); thread = four consecutive rows of each of its CPW channels.  Which
+// channels: bnowner.hpp bn_owner_group (one contiguous channel run per XCD)
 template <int TPB, int CPW, int SU>
 __global__ __launch_bounds__(TPB) void bn_fused_fwd_kernel(const BnFusedFwd p) {
   typedef float rowv __attribute__((ext_vector_type(CPW)));
   __shared__ float sm[(TPB / 64) * CPW];
   BNF_PH(0);
-  const int tid = threadIdx.x, c0 = fused_group(blockIdx.x, p.C, CPW) * CPW, R = p.R, C = p.C;
+  const int tid = threadIdx.x, c0 = bn_owner_group(blockIdx.x, p.C, CPW) * CPW, R = p.R, C = p.C;
   const int r4 = 4 * tid;
   const bool live = r4 < R;
   // everything the tail needs is requested before the slices: nothing below waits for a second memory round trip
@@ -691,7 +683,7 @@ __global__ __launch_bounds__(TPB) void bn_fused_bwd_kernel(const BnFusedBwd p) {
   typedef float rowv __attribute__((ext_vector_type(CPW)));
   __shared__ float sm[(TPB / 64) * 2 * CPW];
   BNB_PH(0);
-  const int tid = threadIdx.x, c0 = fused_group(blockIdx.x, p.C, CPW) * CPW, R = p.R, C = p.C;
+  const int tid = threadIdx.x, c0 = bn_owner_group(blockIdx.x, p.C, CPW) * CPW, R = p.R, C = p.C;
   const int r4 = 4 * tid;
   const bool live = r4 < R;
   rowv yv[4];        // [row] along channels
@@ -768,13 +760,10 @@ bool bn_fused_ok(int R, int C) {
   return R > 0 && R % 4 == 0 && C % 4 == 0 && R <= 4096 && (long)R * C <= max_elems;
 }
 
-// threads = R / 4 rounded up to 64 / 256 / 1024; two channels per workgroup where four would leave most of the chip idle
-// (fewer than kBnFusedTwoBelow channels)
-constexpr int kBnFusedTwoBelow = 256;
-
+// threads = R / 4 rounded up to 64 / 256 / 1024; channels per workgroup: bnowner.hpp bn_owner_cpw
 #define CTVAE_BN_FUSED_LAUNCH(KERNEL, P, ST)                                                                      \
   do {                                                                                                            \
-    const bool two = (P).C < kBnFusedTwoBelow;                                                                    \
+    const bool two = bn_owner_cpw((P).C) == 2;                                                                    \
     const dim3 grid((P).C / (two ? 2 : 4));                                                                       \
     if ((P).R <= 256) {                                                                                           \
       if (two) hipLaunchKernelGGL((KERNEL<64, 2, 8>), grid, dim3(64), 0, ST, P);                                  \
